@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: WaveNet training-step throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--global-batch G]
+  python bench.py --gpus N --steps K --warmup W [--global-batch G] [--dump-outputs DIR] [--full]
 
 A "step" is one full data-parallel training step as train.py:225-228 compiles it (src/model.py:309-348):
 shift-by-one, forward, loss, backward, SUM all-reduce of the flat gradient over RCCL, per-tensor clipnorm +
@@ -14,20 +14,30 @@ batch 8, global batch 8 N -- global batch 64 at N = 8, as configs[2] names it).
   --gpus N > 1 without an enclosing torch.distributed.run: this script starts the N ranks itself (child
   processes of `python -m torch.distributed.run`, before anything here touches the GPU) and relays rank 0's line.
   --global-batch G: STRONG scaling -- the global batch is fixed at G, every rank takes G / N utterances
-  (north_star: global batch 64); without it the line is weak scaling and a short strong-scaling measurement at
-  global batch 64 is reported beside it ("strong_scaling").
+  (north_star: global batch 64); without it the line is weak scaling.
+  --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller -- the step's logs
+  (log_<name>.npy, float64) and the model it updated (params.npy, grads.npy, adam_m.npy, adam_v.npy, float32) -- so
+  that two builds can be compared output for output on the same seeded inputs.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step), the per-step spread, the range guard's trips in the
+timed steps and the kernel families of the plan.  --full adds the measurements that take runs of their own:
+  exact_fp32_mfma -- the same step with the exact-fp32 MFMA kernels (debug knob 1)
+  dp_mode      -- (N = 1) the same step under a one-rank RCCL process group
+  strong_scaling -- (weak scaling only) a short measurement at global batch 64
+  phases_ms    -- where the step goes, from HIP events at the phase boundaries in extra untimed steps
   roofline     -- SURVEY.md 8(d): the residual-block STACK forward.  achieved = N_blocks * 4 B T (2R + S) /
                   t_stack_fwd, t_stack_fwd = HIP events on the launch stream from the first block launch to the
                   end of the folded contraction over the blocks' gated activations (the skip tensors of the reference's
                   signature are produced and consumed there; training passes fold the head's first conv into it),
                   against the 8 TB/s HBM3E peak.  "fused_block_kernel" beside it: the dominant kernel on
                   its own counter bytes.
+  other_configs -- (N = 1) train-step time and stack fraction of the other BASELINE configs
   cpu_baseline -- the CPU oracle (restated reference, PyTorch CPU) timed on this host's cores on a bounded
                   sample of the same workload
   generation   -- (N = 1) autoregressive generation speed on the same network, SURVEY.md 8(f)-1: queued sampler with
                   stochastic / deterministic draws and the sliding window, per utterance and aggregate at batch 8
+The --no-* options leave single legs of --full out.
 """
 import argparse
 import json
@@ -56,6 +66,11 @@ def parse_args(argv=None):
   ap.add_argument('--global-batch', type=int, default=0,
                   help='strong scaling: fixed global batch, split over the ranks (0 = weak scaling)')
   ap.add_argument('--length', type=int, default=16000, help='predicted samples per utterance')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help="write the last timed step's logs and the updated model to DIR/<name>.npy")
+  ap.add_argument('--full', action='store_true',
+                  help='also run the measurements beside the headline (exact fp32, dp_mode, strong scaling, phases, '
+                       'roofline, other configs, CPU baseline, generation)')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--no-strong-leg', action='store_true', help='skip the extra global-batch-64 measurement')
   ap.add_argument('--no-generation', action='store_true', help='skip the generation-speed leg (N = 1 only)')
@@ -242,6 +257,19 @@ def cpu_baseline(budget_s: float = 20.0):
                     f'8 utterances (batch 1x16000) with the PyTorch-CPU oracle, {dt * 1e3:.0f} ms/step'}
 
 
+def dump_outputs(dirname, model, logs):
+  """What the timed path hands its caller after its last step: the step's logs and the model it updated (weights, the
+  step's flat gradient, Adam's moments), 4 x 5 MB for configs[1]."""
+  import re
+  import numpy as np
+  os.makedirs(dirname, exist_ok=True)
+  for name, v in logs.items():
+    np.save(os.path.join(dirname, 'log_' + re.sub(r'\W', '_', name) + '.npy'), np.asarray(v, dtype=np.float64))
+  for name, t in (('params', model.flat_params), ('grads', model.flat_grads),
+                  ('adam_m', model.optimizer.m), ('adam_v', model.optimizer.v)):
+    np.save(os.path.join(dirname, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def _profile_rows(pattern):
   """Newest committed rocprofv3 summary matching profiles/<pattern> as a list of csv rows."""
   import csv
@@ -346,107 +374,111 @@ def main():
   x = synthetic_waveforms(B, T + 1, seed=1234 + rank, device=dev)
   # the timed region carries no measurement hooks: W warm-up steps, then exactly K steps between two barriers
   dt, per_step, logs = timed_steps(model, x, args.steps, args.warmup)
-  # roofline inputs from EXTRA, untimed steps: HIP events on the launch stream around the block chain (per-launch
-  # average of the fused block kernel), around the whole stack (first block launch -> end of the folded contraction) and
-  # around the fold's per-pass weight-space preparation (V = W_s W_f0 and its fp16 images), which runs before the stack
+  guard_trips = model.train_guard_trips                   # steps of the timed run repeated in exact fp32 by the range guard
+  if rank == 0 and args.dump_outputs:
+    dump_outputs(args.dump_outputs, model, logs)
   kernel_families = model.kernel_report()
-  n_prof = max(3, min(args.steps, 10))
-  n_l, avg_ms, n_s, stack_ms, prep_ms = stack_profile(model, x, n_prof, nblk)
-  if world > 1:
-    sync()
   ms_per_step = dt / args.steps * 1e3
   value = world * B * T * args.steps / dt
 
-  # where the step goes (untimed extra steps): phase marks inside wn_train_fwd_bwd (HIP events on the launch
-  # stream) + torch events around the gradient all-reduce and the optimizer
-  phases = None
-  from wavenets_amd import dp as _dp
-  if rank == 0:
-    _lib.check(L.wn_phase_enable(model._plan, 1))
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-    acc = [0.0] * 7
-    nph = 3
-    mse_metric = MeanSquaredError()
-    for _ in range(nph):
-      ev[0].record()
-      loss_p, samp_p, y_p = model.loss_and_grads(x, want_sample=True)   # the sample draw rides in the loss phase
-      ev[1].record()
-      _dp.allreduce_gradients(model.flat_grads, loss_p)      # no-op for a single replica
-      ev[2].record()
-      model.optimizer.apply_gradients(model)
-      ev[3].record()
-      mse_p = mse_metric.update_state_device(y_p, samp_p)      # the library's reduction, as train_step queues it
-      ev[4].record()
-      torch.cuda.synchronize()
-      ms4 = (C.c_float * 4)()
-      _lib.check(L.wn_phase_read(model._plan, ms4))
-      for i in range(4):
-        acc[i] += ms4[i]
-      acc[4] += ev[1].elapsed_time(ev[2])
-      acc[5] += ev[2].elapsed_time(ev[3])
-      acc[6] += ev[3].elapsed_time(ev[4])
-    _lib.check(L.wn_phase_enable(model._plan, 0))
-    names = ['forward', 'loss', 'backward_data', 'weight_gradients', 'allreduce', 'optimizer', 'metric']
-    phases = {n: round(a / nph, 4) for n, a in zip(names, acc)}
-  elif world > 1:                                         # the other ranks take part in the collectives
-    for _ in range(3):
-      loss_p, _, _ = model.loss_and_grads(x, want_sample=True)
-      _dp.allreduce_gradients(model.flat_grads, loss_p)
-      model.optimizer.apply_gradients(model)
-  sync()
+  if args.full:
+    # roofline inputs from EXTRA, untimed steps: HIP events on the launch stream around the block chain (per-launch
+    # average of the fused block kernel), around the whole stack (first block launch -> end of the folded contraction) and
+    # around the fold's per-pass weight-space preparation (V = W_s W_f0 and its fp16 images), which runs before the stack
+    n_prof = max(3, min(args.steps, 10))
+    n_l, avg_ms, n_s, stack_ms, prep_ms = stack_profile(model, x, n_prof, nblk)
+    if world > 1:
+      sync()
 
-  # N = 1: the DATA-PARALLEL form of the same step on the real backend -- a process group of one rank on "nccl" (= RCCL):
-  # dp.allreduce_bucket then runs librccl's all-reduce on the gradient bucket, and train_step takes its data-parallel
-  # path (scalars out of the all-reduced bucket tail through a pinned copy + event; ONE collective per step) instead of
-  # the single-replica early read.  `dp_mode.ms_per_step` is what that path costs against the headline.
-  dp_mode = None
-  if world == 1 and not args.no_dp_leg:
-    try:
-      import socket
-      sk = socket.socket()
-      sk.bind(('127.0.0.1', 0))
-      port = sk.getsockname()[1]
-      sk.close()
-      dist.init_process_group('nccl', init_method=f'tcp://127.0.0.1:{port}', rank=0, world_size=1, device_id=dev)
-      nd = max(3, min(args.steps, 20))
-      dp_mode = {'backend': 'nccl (RCCL)', 'world_size': 1}
-      for key, early in (('one_collective_tail_read', None), ('early_read_second_small_collective', True)):
-        model.early_logs = early
-        dtd, _, _ = timed_steps(model, x, nd, 3)
-        dp_mode[key] = {'ms_per_step': dtd / nd * 1e3, 'steps': nd, 'vs_headline': (dtd / nd * 1e3) / ms_per_step}
-      dp_mode['ms_per_step'] = dp_mode['one_collective_tail_read']['ms_per_step']     # the default data-parallel path
-      dp_mode['guard_trips'] = model.train_guard_trips
-    except Exception as e:                                 # report, do not lose the headline
-      dp_mode = {'error': f'{type(e).__name__}: {e}'[:300]}
-    finally:
-      model.early_logs = None
-      if dist.is_initialized():
-        dist.destroy_process_group()
+    # where the step goes (untimed extra steps): phase marks inside wn_train_fwd_bwd (HIP events on the launch
+    # stream) + torch events around the gradient all-reduce and the optimizer
+    phases = None
+    from wavenets_amd import dp as _dp
+    if rank == 0:
+      _lib.check(L.wn_phase_enable(model._plan, 1))
+      ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+      acc = [0.0] * 7
+      nph = 3
+      mse_metric = MeanSquaredError()
+      for _ in range(nph):
+        ev[0].record()
+        loss_p, samp_p, y_p = model.loss_and_grads(x, want_sample=True)   # the sample draw rides in the loss phase
+        ev[1].record()
+        _dp.allreduce_gradients(model.flat_grads, loss_p)      # no-op for a single replica
+        ev[2].record()
+        model.optimizer.apply_gradients(model)
+        ev[3].record()
+        mse_p = mse_metric.update_state_device(y_p, samp_p)      # the library's reduction, as train_step queues it
+        ev[4].record()
+        torch.cuda.synchronize()
+        ms4 = (C.c_float * 4)()
+        _lib.check(L.wn_phase_read(model._plan, ms4))
+        for i in range(4):
+          acc[i] += ms4[i]
+        acc[4] += ev[1].elapsed_time(ev[2])
+        acc[5] += ev[2].elapsed_time(ev[3])
+        acc[6] += ev[3].elapsed_time(ev[4])
+      _lib.check(L.wn_phase_enable(model._plan, 0))
+      names = ['forward', 'loss', 'backward_data', 'weight_gradients', 'allreduce', 'optimizer', 'metric']
+      phases = {n: round(a / nph, 4) for n, a in zip(names, acc)}
+    elif world > 1:                                         # the other ranks take part in the collectives
+      for _ in range(3):
+        loss_p, _, _ = model.loss_and_grads(x, want_sample=True)
+        _dp.allreduce_gradients(model.flat_grads, loss_p)
+        model.optimizer.apply_gradients(model)
+    sync()
 
-  # the same step with the exact-fp32 MFMA kernels (debug knob 1), reported beside the default
-  guard_trips = model.train_guard_trips                   # steps of this run repeated in exact fp32 by the range guard
-  L.wn_debug_set(1, 1)
-  nf = max(2, min(args.steps // 3, 10))
-  dt_fp32, _, _ = timed_steps(model, x, nf, 1)
-  dt_fp32 /= nf
-  L.wn_debug_set(1, 0)
+    # N = 1: the DATA-PARALLEL form of the same step on the real backend -- a process group of one rank on "nccl" (= RCCL):
+    # dp.allreduce_bucket then runs librccl's all-reduce on the gradient bucket, and train_step takes its data-parallel
+    # path (scalars out of the all-reduced bucket tail through a pinned copy + event; ONE collective per step) instead of
+    # the single-replica early read.  `dp_mode.ms_per_step` is what that path costs against the headline.
+    dp_mode = None
+    if world == 1 and not args.no_dp_leg:
+      try:
+        import socket
+        sk = socket.socket()
+        sk.bind(('127.0.0.1', 0))
+        port = sk.getsockname()[1]
+        sk.close()
+        dist.init_process_group('nccl', init_method=f'tcp://127.0.0.1:{port}', rank=0, world_size=1, device_id=dev)
+        nd = max(3, min(args.steps, 20))
+        dp_mode = {'backend': 'nccl (RCCL)', 'world_size': 1}
+        for key, early in (('one_collective_tail_read', None), ('early_read_second_small_collective', True)):
+          model.early_logs = early
+          dtd, _, _ = timed_steps(model, x, nd, 3)
+          dp_mode[key] = {'ms_per_step': dtd / nd * 1e3, 'steps': nd, 'vs_headline': (dtd / nd * 1e3) / ms_per_step}
+        dp_mode['ms_per_step'] = dp_mode['one_collective_tail_read']['ms_per_step']     # the default data-parallel path
+        dp_mode['guard_trips'] = model.train_guard_trips
+      except Exception as e:                                 # report, do not lose the headline
+        dp_mode = {'error': f'{type(e).__name__}: {e}'[:300]}
+      finally:
+        model.early_logs = None
+        if dist.is_initialized():
+          dist.destroy_process_group()
 
-  # strong-scaling leg (north_star: global batch 64 split over the ranks): a short run beside the weak line
-  strong_leg = None
-  if not strong and not args.no_strong_leg and STRONG_GLOBAL_BATCH % world == 0:
-    Bs = STRONG_GLOBAL_BATCH // world
-    if Bs == B:
-      strong_leg = {'global_batch': STRONG_GLOBAL_BATCH, 'per_gpu_batch': Bs, 'ms_per_step': ms_per_step, 'value': value,
-                    'steps': args.steps, 'note': 'same run as the headline (per-GPU batch coincides)'}
-    else:
-      del model
-      torch.cuda.empty_cache()
-      model = make_model()
-      xs = synthetic_waveforms(Bs, T + 1, seed=4321 + rank, device=dev)
-      ns = max(3, min(args.steps, 10))
-      dts, _, _ = timed_steps(model, xs, ns, 2)
-      strong_leg = {'global_batch': STRONG_GLOBAL_BATCH, 'per_gpu_batch': Bs, 'ms_per_step': dts / ns * 1e3,
-                    'value': STRONG_GLOBAL_BATCH * T * ns / dts, 'steps': ns}
+    # the same step with the exact-fp32 MFMA kernels (debug knob 1), reported beside the default
+    L.wn_debug_set(1, 1)
+    nf = max(2, min(args.steps // 3, 10))
+    dt_fp32, _, _ = timed_steps(model, x, nf, 1)
+    dt_fp32 /= nf
+    L.wn_debug_set(1, 0)
+
+    # strong-scaling leg (north_star: global batch 64 split over the ranks): a short run beside the weak line
+    strong_leg = None
+    if not strong and not args.no_strong_leg and STRONG_GLOBAL_BATCH % world == 0:
+      Bs = STRONG_GLOBAL_BATCH // world
+      if Bs == B:
+        strong_leg = {'global_batch': STRONG_GLOBAL_BATCH, 'per_gpu_batch': Bs, 'ms_per_step': ms_per_step, 'value': value,
+                      'steps': args.steps, 'note': 'same run as the headline (per-GPU batch coincides)'}
+      else:
+        del model
+        torch.cuda.empty_cache()
+        model = make_model()
+        xs = synthetic_waveforms(Bs, T + 1, seed=4321 + rank, device=dev)
+        ns = max(3, min(args.steps, 10))
+        dts, _, _ = timed_steps(model, xs, ns, 2)
+        strong_leg = {'global_batch': STRONG_GLOBAL_BATCH, 'per_gpu_batch': Bs, 'ms_per_step': dts / ns * 1e3,
+                      'value': STRONG_GLOBAL_BATCH * T * ns / dts, 'steps': ns}
 
   if rank == 0:
     per_ms = sorted(p * 1e3 for p in per_step)
@@ -454,6 +486,24 @@ def main():
     def pct(q):
       return per_ms[min(len(per_ms) - 1, int(round(q * (len(per_ms) - 1))))]
 
+    out = {
+        'metric': 'audio samples/sec (training step, 16 kHz mu-law)',
+        'value': value, 'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'strong' if strong else 'weak',
+        'vs_baseline': None, 'dtype': 'f32 (fp16 hi|lo split operands, fp32 accumulate)', 'data': 'synthetic',
+        'range_guard_trips': guard_trips,
+        'ms_per_step_median': pct(0.5), 'ms_per_step_p10': pct(0.1), 'ms_per_step_p90': pct(0.9),
+        'math': 'fp32 tensors; contractions as fp16 hi/lo split, 3 products on v_mfma_f32_32x32x16_f16 with fp32 '
+                'accumulate (|err| <= 6e-7 on O(1) results, parity-tested at 1e-4); exact-fp32 MFMA selectable',
+        'kernel_families': kernel_families,
+        'config': {'workload': 'configs[1]: 30-layer (3x10) mu-law-256 WaveNet, 64 residual / 256 skip ch, '
+                               f'head [128,256], batch {B}x{T} per GPU, full train step '
+                               '(fwd+loss+bwd+allreduce+clipnorm-Adam+sample_waveform draw+MSE metric, as train.py:225-228 compiles it)',
+                   'global_batch': world * B, 'samples_per_utterance': T, 'parallelism': f'dp{world}'},
+        'per_gpu_samples_per_s': value / world,
+        'final_loss': logs['loss'],
+    }
+  if rank == 0 and args.full:
     # HBM bytes per launch of the dominant kernel and MFMA busy share from the committed rocprofv3 PMC passes
     # (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE); bench.py cannot run the counter passes itself
     traffic, mfma_busy = None, None
@@ -476,28 +526,14 @@ def main():
     t_stack = stack_ms + (0.0 if prep_overlapped else prep_ms)
     achieved = stack_bytes / (t_stack * 1e-3) / 1e9 if t_stack > 0 else 0.0
     kern_gbs = (traffic / (avg_ms * 1e-3) / 1e9) if (traffic and avg_ms > 0) else None
-    out = {
-        'metric': 'audio samples/sec (training step, 16 kHz mu-law)',
-        'value': value, 'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'strong' if strong else 'weak',
-        'vs_baseline': None, 'dtype': 'f32 (fp16 hi|lo split operands, fp32 accumulate)', 'data': 'synthetic',
+    out.update({
         'ms_per_step_exact_fp32_mfma': dt_fp32 * 1e3, 'value_exact_fp32_mfma': world * B * T / dt_fp32,
-        'range_guard_trips': guard_trips,
-        'ms_per_step_median': pct(0.5), 'ms_per_step_p10': pct(0.1), 'ms_per_step_p90': pct(0.9),
-        'math': 'fp32 tensors; contractions as fp16 hi/lo split, 3 products on v_mfma_f32_32x32x16_f16 with fp32 '
-                'accumulate (|err| <= 6e-7 on O(1) results, parity-tested at 1e-4); exact-fp32 MFMA selectable',
         'exact_fp32_mfma': {'ms_per_step': dt_fp32 * 1e3, 'value': world * B * T / dt_fp32,
                             'note': 'the same step with v_mfma_f32_32x32x2_f32 contractions (no operand split): what a step '
                                     'costs when the range guard repeats it; range_guard_trips counts such repeats in the timed run'},
         'dp_mode': dp_mode,
-        'phases_ms': phases, 'kernel_families': kernel_families,
-        'config': {'workload': 'configs[1]: 30-layer (3x10) mu-law-256 WaveNet, 64 residual / 256 skip ch, '
-                               f'head [128,256], batch {B}x{T} per GPU, full train step '
-                               '(fwd+loss+bwd+allreduce+clipnorm-Adam+sample_waveform draw+MSE metric, as train.py:225-228 compiles it)',
-                   'global_batch': world * B, 'samples_per_utterance': T, 'parallelism': f'dp{world}'},
-        'per_gpu_samples_per_s': value / world,
+        'phases_ms': phases,
         'strong_scaling': strong_leg,
-        'final_loss': logs['loss'],
         'roofline': {'bound': 'hbm',
                      'kernel': 'residual-block stack forward: 30 x wn_layer_fwd_f16_kernel + the folded contraction over all '
                                "blocks' gated activations (wn_gemm_planes16s_kernel: skip sum and, in training passes, the head's "
@@ -520,7 +556,7 @@ def main():
                              "is part of the timed stack, as is the fold's per-pass weight preparation (forked at the stack's "
                              "start event onto a side stream, joined before the contraction)",
                      'fold_prep_overlapped': prep_overlapped},
-    }
+    })
     if world == 1 and not args.no_other_configs:
       del model
       torch.cuda.empty_cache()
@@ -529,6 +565,7 @@ def main():
       out['cpu_baseline'] = cpu_baseline(args.cpu_budget)
     if world == 1 and not args.no_generation:
       out['generation'] = generation_leg(dev)
+  if rank == 0:
     print(json.dumps(out))
   if world > 1:
     dist.barrier()

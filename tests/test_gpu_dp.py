@@ -176,7 +176,7 @@ def test_bench_multi_rank_plumbing_rehearsal():
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
   env = dict(os.environ, WN_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
   cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--global-batch', '4', '--steps', '2', '--warmup', '1',
-         '--length', '3500', '--no-cpu-baseline', '--no-generation', '--no-other-configs']
+         '--length', '3500', '--full', '--no-cpu-baseline', '--no-generation', '--no-other-configs']
   res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
   assert res.returncode == 0, res.stderr[-2000:]
   line = [ln for ln in res.stdout.splitlines() if ln.startswith('{') and '"metric"' in ln][-1]
@@ -185,6 +185,37 @@ def test_bench_multi_rank_plumbing_rehearsal():
   assert out['config']['global_batch'] == 4 and out['config']['parallelism'] == 'dp2'
   assert out['value'] > 0 and abs(out['value'] - 4 * 3500 * 2 / (out['ms_per_step'] * 2e-3)) < 1e-6 * out['value']
   assert out['roofline']['frac'] > 0 and 'cpu_baseline' not in out
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+  """A plain `bench.py` run (no --full) times exactly --steps steps, prints the contract fields and none of the extra
+  legs, and --dump-outputs writes the last timed step's logs and the updated model as float32 / float64 .npy files."""
+  import json
+  import subprocess
+  import sys
+  import numpy as np
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  out_dir = tmp_path / 'outputs'
+  cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+         '--length', '3500', '--dump-outputs', str(out_dir)]
+  res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+  assert res.returncode == 0, res.stderr[-2000:]
+  line = [ln for ln in res.stdout.splitlines() if ln.startswith('{') and '"metric"' in ln][-1]
+  out = json.loads(line)
+  for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+    assert key in out, key
+  assert out['steps'] == 3 and out['n_gpus'] == 1
+  assert abs(out['value'] - 8 * 3500 / (out['ms_per_step'] * 1e-3)) < 1e-6 * out['value']
+  for key in ('roofline', 'phases_ms', 'dp_mode', 'exact_fp32_mfma', 'strong_scaling', 'other_configs', 'cpu_baseline',
+              'generation'):
+    assert key not in out, key
+  files = {p.name: np.load(p) for p in out_dir.iterdir()}
+  n = files['params.npy'].size
+  assert n > 0 and all(files[f].shape == (n,) and files[f].dtype == np.float32
+                       for f in ('params.npy', 'grads.npy', 'adam_m.npy', 'adam_v.npy'))
+  assert files['log_loss.npy'].dtype == np.float64 and float(files['log_loss.npy']) == out['final_loss']
+  assert all(np.isfinite(a).all() for a in files.values())
+  assert sum(a.nbytes for a in files.values()) <= 64 << 20
 
 
 def test_one_plan_shared_by_two_threads_and_streams():

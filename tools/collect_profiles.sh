@@ -16,7 +16,7 @@ run() { # name, program...
   echo "== $name"; timeout -k 10 280 rocprofv3 --output-format csv "${@:1:$#}" || { echo "FAILED $name"; exit 1; }
 }
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_LDS"
-run bench_ks --kernel-trace --stats -d $OUT/bench_ks -o bench -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-generation --no-other-configs --no-strong-leg > $OUT/bench_ks.log 2>&1
+run bench_ks --kernel-trace --stats -d $OUT/bench_ks -o bench -- python3 $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-generation --no-other-configs --no-strong-leg > $OUT/bench_ks.log 2>&1
 for cfg in train cfg4; do
   prog=$ROOT/tools/prof_${cfg}.py
   run ${cfg}_ks --kernel-trace --stats -d $OUT/${cfg}_ks -o $cfg -- python3 $prog > $OUT/${cfg}_ks.log 2>&1
