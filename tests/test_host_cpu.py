@@ -198,3 +198,22 @@ def test_generation_chain_prefetch_registers_are_untouched_until_their_wait():
       i = j
     i += 1
   assert kernels >= 3
+
+
+def test_split_precision_arithmetic_is_written_once():
+  """The fp16 hi|lo split, the power-of-two operand scale and the three-product MFMA sequence set the accuracy contract
+  and the generation <-> training-forward bit identity: they live in wn_split16.h alone, so that no kernel carries a
+  copy that can drift."""
+  csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'wavenets_amd', 'csrc')
+  needles = ('(_Float16)', 'frexpf(', '__builtin_amdgcn_mfma_f32_32x32x16_f16')
+  found = []
+  for name in sorted(os.listdir(csrc)):
+    if name == 'wn_split16.h':
+      continue
+    with open(os.path.join(csrc, name), errors='replace') as f:
+      text = f.read()
+    found += [(name, n) for n in needles if n in text]
+  assert found == []
+  with open(os.path.join(csrc, 'wn_split16.h')) as f:
+    header = f.read()
+  assert all(n in header for n in needles)

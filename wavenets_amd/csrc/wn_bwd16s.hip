@@ -12,47 +12,11 @@
 //
 // Replaces two launches of the streamed rows GEMM per block boundary (128 + 110 us, profiles/r03_cfg4_*): g_x(b+1) is not
 // re-read and one launch's ramp disappears.
-#include <hip/hip_fp16.h>
+#include "wn_split16.h"
 
-#include "wn_kernels.h"
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+using namespace wn_split16;
 
 namespace {
-
-__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ void split8s(const f32x4& q0, const f32x4& q1, float s, h8& hi, h8& lo) {
-  const float v[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const _Float16 h = (_Float16)(v[e] * s);
-    hi[e] = h;
-    lo[e] = (_Float16)__builtin_fmaf(v[e], s, -(float)h);
-  }
-}
-// (see wn_layer16s.hip: scalar base + 32-bit lane offset, M0 = LDS address; inline assembly keeps the addresses scalar)
-__device__ __forceinline__ void dma16(const void* sbase, unsigned voff, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr_of(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)p;
-}
-__device__ __forceinline__ f32x4 ldg4(const __attribute__((address_space(1))) char* p) {
-  return *(const __attribute__((address_space(1))) f32x4*)p;
-}
-__device__ __forceinline__ void pow2_scale(float m, float& sc, float& inv) {
-  sc = 1.0f;
-  inv = 1.0f;
-  if (m > 0.f && m < 3.0e38f) {
-    int e;
-    (void)frexpf(m, &e);
-    e = max(-100, min(100, e));
-    sc = ldexpf(1.0f, -e);
-    inv = ldexpf(1.0f, e);
-  }
-}
 
 constexpr int R = 128, D = 128, F0 = 128;
 constexpr int NC1 = 16;                       // chunks of the reversed conv: K = KS * 2D = 512 = 32 k-steps, two per chunk
@@ -66,31 +30,6 @@ constexpr int LDS = NBUF * CHUNK + WAVES * REGION;   // 81920: two workgroups pe
 constexpr int PT = CHUNK / 16 / THREADS;      // 4 weight requests per thread and chunk
 constexpr int PX = 2;                         // requests per lane and activation k-step
 static_assert(NCH % NBUF == 0 && STAGE <= REGION, "ring / stage geometry");
-
-// one 32 x 32 D-layout tile -> wave-private LDS stage -> 128-byte row segments (scalar base + lane offset, see wn_layer16s.hip)
-template <bool FULL>
-__device__ __forceinline__ void store_tile(const f32x16& v, float* stage, float* dst, unsigned voff, unsigned ld_bytes,
-                                           int rows_valid, int lane) {
-  const int tl = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int rq = 0; rq < 4; ++rq) {
-    f32x4 o;
-    o.x = v[4 * rq + 0]; o.y = v[4 * rq + 1]; o.z = v[4 * rq + 2]; o.w = v[4 * rq + 3];
-    *reinterpret_cast<f32x4*>(stage + tl * PITCH + 8 * rq + 4 * h) = o;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  const float* rd = stage + (lane >> 3) * PITCH + (lane & 7) * 4;
-  char* base0 = reinterpret_cast<char*>(dst);
-  asm volatile("" : "+s"(base0));
-  __attribute__((address_space(1))) char* base = (__attribute__((address_space(1))) char*)base0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f32x4 o = *reinterpret_cast<const f32x4*>(rd + i * 8 * PITCH);
-    if (FULL || i * 8 + (lane >> 3) < rows_valid)
-      *(__attribute__((address_space(1))) f32x4*)(base + (uint64_t)((unsigned)(i * 8) * ld_bytes) + voff) = o;
-  }
-  asm volatile("" ::: "memory");
-}
 
 }  // namespace
 
@@ -203,9 +142,7 @@ __global__ __launch_bounds__(256, 2) void wn_bwd_s128_kernel(WnBwdPairArgs a) {
             fr[(blk + 1) & 1][0] = wl[((blk + 1) * 2 + 0) * 64];
             fr[(blk + 1) & 1][1] = wl[((blk + 1) * 2 + 1) * 64];
           }
-          acc[j] = mfma16(fr[blk & 1][1], bh, acc[j]);
-          acc[j] = mfma16(fr[blk & 1][0], bl, acc[j]);
-          acc[j] = mfma16(fr[blk & 1][0], bh, acc[j]);
+          mfma3(fr[blk & 1][0], fr[blk & 1][1], bh, bl, acc[j]);
           // requests of this step, one per product block: the look-ahead weight chunk first, then (both activation
           // buffers of the step have been read by now) the k-steps two steps ahead
           if constexpr (blk < PT) wpiece((c + 2) % NCH, blk);
@@ -234,10 +171,10 @@ __global__ __launch_bounds__(256, 2) void wn_bwd_s128_kernel(WnBwdPairArgs a) {
     const unsigned voff128 = (unsigned)(lane >> 3) * 512u + (unsigned)(lane & 7) * 16u;
     if (rows_valid == 32) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) store_tile<true>(gx[j], stage, a.gx_out + row0 * R + 32 * j, voff128, 512u, rows_valid, lane);
+      for (int j = 0; j < 4; ++j) store_tile<PITCH, true>(gx[j], stage, a.gx_out + row0 * R + 32 * j, voff128, 512u, rows_valid, lane);
     } else if (rows_valid > 0) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) store_tile<false>(gx[j], stage, a.gx_out + row0 * R + 32 * j, voff128, 512u, rows_valid, lane);
+      for (int j = 0; j < 4; ++j) store_tile<PITCH, false>(gx[j], stage, a.gx_out + row0 * R + 32 * j, voff128, 512u, rows_valid, lane);
     }
     wmax_x = fmaxf(wmax_x, tmax);
     // per-tile power-of-two scale of the second product's B operands (the tensor's max-abs is not known while it is produced)
@@ -315,9 +252,7 @@ __global__ __launch_bounds__(256, 2) void wn_bwd_s128_kernel(WnBwdPairArgs a) {
             fr[(blk + 1) & 1][0] = wl[((blk + 1) * 2 + 0) * 64];
             fr[(blk + 1) & 1][1] = wl[((blk + 1) * 2 + 1) * 64];
           }
-          acc[j] = mfma16(fr[blk & 1][1], bh, acc[j]);
-          acc[j] = mfma16(fr[blk & 1][0], bl, acc[j]);
-          acc[j] = mfma16(fr[blk & 1][0], bh, acc[j]);
+          mfma3(fr[blk & 1][0], fr[blk & 1][1], bh, bl, acc[j]);
           // (past the tile's end: the next tile's first chunks; on the last pass harmless re-reads nobody uses)
           if constexpr (blk < PT) wpiece((c + 2) % NCH, blk);
           if constexpr (blk == 4 && (cc == 0 || cc == 1 || cc == 4 || cc == 5)) fdma(cc < 2 ? 2 * cc : 2 * cc - 4);
@@ -349,11 +284,11 @@ __global__ __launch_bounds__(256, 2) void wn_bwd_s128_kernel(WnBwdPairArgs a) {
         }
       }
       if (rows_valid == 32) {
-        store_tile<true>(of, stage, a.gu_out + row0 * 256 + 32 * j, voff256, 1024u, rows_valid, lane);
-        store_tile<true>(og, stage, a.gu_out + row0 * 256 + 128 + 32 * j, voff256, 1024u, rows_valid, lane);
+        store_tile<PITCH, true>(of, stage, a.gu_out + row0 * 256 + 32 * j, voff256, 1024u, rows_valid, lane);
+        store_tile<PITCH, true>(og, stage, a.gu_out + row0 * 256 + 128 + 32 * j, voff256, 1024u, rows_valid, lane);
       } else if (rows_valid > 0) {
-        store_tile<false>(of, stage, a.gu_out + row0 * 256 + 32 * j, voff256, 1024u, rows_valid, lane);
-        store_tile<false>(og, stage, a.gu_out + row0 * 256 + 128 + 32 * j, voff256, 1024u, rows_valid, lane);
+        store_tile<PITCH, false>(of, stage, a.gu_out + row0 * 256 + 32 * j, voff256, 1024u, rows_valid, lane);
+        store_tile<PITCH, false>(og, stage, a.gu_out + row0 * 256 + 128 + 32 * j, voff256, 1024u, rows_valid, lane);
       }
     });
     wmax_u = fmaxf(wmax_u, umax);

@@ -16,39 +16,11 @@
 // 128-byte row segments.  Operand scaling: the first product uses the running max-abs of g_u(b+1) like the unfused
 // kernel (bit-identical g_x); the second one cannot know the max-abs of the tensor it is producing, so every tile is
 // scaled by the exact power of two of max(its own max |g_x|, running max-abs of dL/da).
-#include <hip/hip_fp16.h>
+#include "wn_split16.h"
 
-#include "wn_kernels.h"
-
-typedef _Float16 bp_h8 __attribute__((ext_vector_type(8)));
+using namespace wn_split16;
 
 namespace {
-
-__device__ __forceinline__ f32x16 bp_mfma(bp_h8 a, bp_h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-
-__device__ __forceinline__ void bp_split8(const f32x4& q0, const f32x4& q1, float s, bp_h8& hi, bp_h8& lo) {
-  const float v[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const _Float16 h = (_Float16)(v[e] * s);
-    hi[e] = h;
-    lo[e] = (_Float16)__builtin_fmaf(v[e], s, -(float)h);
-  }
-}
-
-__device__ __forceinline__ f32x4 bp_ldg4(const float* p) { return *(const __attribute__((address_space(1))) f32x4*)(p); }
-
-__device__ __forceinline__ void bp_pow2_scale(float m, float& sc, float& inv) {
-  sc = 1.0f;
-  inv = 1.0f;
-  if (m > 0.f && m < 3.0e38f) {
-    int e;
-    (void)frexpf(m, &e);
-    e = max(-100, min(100, e));
-    sc = ldexpf(1.0f, -e);
-    inv = ldexpf(1.0f, e);
-  }
-}
 
 constexpr int BP_NK1 = 16;                       // k-steps of the reversed conv (KS * 2D / 16)
 constexpr int BP_NKR = 4;                        // k-steps over g_x (R / 16), operands from registers
@@ -93,11 +65,11 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
     wn_images_to_lds<512, BP_W1 / 16, BP_W2 / 16>(a.wx16, smem, BP_W1 / 16, a.wu16, smem + BP_W1, BP_W2 / 16, tid);
   }
   __syncthreads();
-  const bp_h8* w1 = reinterpret_cast<const bp_h8*>(smem) + lane;
-  const bp_h8* w2 = reinterpret_cast<const bp_h8*>(smem + BP_W1) + lane;
+  const h8* w1 = reinterpret_cast<const h8*>(smem) + lane;
+  const h8* w2 = reinterpret_cast<const h8*>(smem + BP_W1) + lane;
 
   float sc1, inv1;
-  bp_pow2_scale(a.am_gu_in ? *a.am_gu_in : 0.f, sc1, inv1);
+  pow2_scale(a.am_gu_in ? *a.am_gu_in : 0.f, sc1, inv1);
   const float gfmax = a.am_gf ? *a.am_gf : 0.f;
 
   const int tiles_per_b = (a.T + 31) >> 5;
@@ -122,8 +94,8 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
     const bool ok = c.t < a.T && ts < a.T;
     const float* base = seg == 2 ? a.gf : a.gu_in;
     const float* src = base + ((int64_t)c.b * a.T + (ok ? ts : 0)) * 128 + 4 * h + 16 * kk;
-    q0 = bp_ldg4(src);
-    q1 = bp_ldg4(src + 8);
+    q0 = ldg4(src);
+    q1 = ldg4(src + 8);
     okout = ok;
   };
 
@@ -150,7 +122,7 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int rq = 0; rq < 4; ++rq) addc[j][rq] = bp_ldg4(a.gx_res + row * 64 + 32 * j + 8 * rq + 4 * h);
+      for (int rq = 0; rq < 4; ++rq) addc[j][rq] = ldg4(a.gx_res + row * 64 + 32 * j + 8 * rq + 4 * h);
 
     // ---- g_x(b+1) = reversed dilated conv of g_u(b+1) ----
     f32x16 acc[2];
@@ -161,17 +133,15 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
     for (int m0 = 0; m0 < BP_NK1; m0 += BP_PF) {
       wn_static_for<BP_PF>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
-        bp_h8 bh, bl;
-        bp_split8(xr[k][0], xr[k][1], okr[k] ? sc1 : 0.f, bh, bl);
+        h8 bh, bl;
+        split8s(xr[k][0], xr[k][1], okr[k] ? sc1 : 0.f, bh, bl);
         __builtin_amdgcn_sched_barrier(0);
         load_x(cur, m0 + k + BP_PF, xr[k][0], xr[k][1], okr[k]);    // m0 + k + 4 <= 19 < 24: always this tile
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const bp_h8 ah = w1[(((m0 + k) * 2 + j) * 2 + 0) * 64];
-          const bp_h8 al = w1[(((m0 + k) * 2 + j) * 2 + 1) * 64];
-          acc[j] = bp_mfma(al, bh, acc[j]);
-          acc[j] = bp_mfma(ah, bl, acc[j]);
-          acc[j] = bp_mfma(ah, bh, acc[j]);
+          const h8 ah = w1[(((m0 + k) * 2 + j) * 2 + 0) * 64];
+          const h8 al = w1[(((m0 + k) * 2 + j) * 2 + 1) * 64];
+          mfma3(ah, al, bh, bl, acc[j]);
         }
         __builtin_amdgcn_sched_barrier(0);
       });
@@ -197,8 +167,8 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int rq = 0; rq < 4; ++rq) {
-        sg[j][rq] = bp_ldg4(a.ag + row * 64 + 32 * j + 8 * rq + 4 * h);
-        zz[j][rq] = bp_ldg4(a.z + row * a.ldz + 32 * j + 8 * rq + 4 * h);
+        sg[j][rq] = ldg4(a.ag + row * 64 + 32 * j + 8 * rq + 4 * h);
+        zz[j][rq] = ldg4(a.z + row * a.ldz + 32 * j + 8 * rq + 4 * h);
       }
     if (cur.rows_valid > 0) {
       bp_store32(gx[0], stage, a.gx_out + cur.row0 * 64, 64, cur.rows_valid, lane);
@@ -209,7 +179,7 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) tmax = fmaxf(tmax, __shfl_xor(tmax, o));
     float sc2, inv2;
-    bp_pow2_scale(fmaxf(tmax, gfmax), sc2, inv2);
+    pow2_scale(fmaxf(tmax, gfmax), sc2, inv2);
 
     // ---- g_z = W_r g_x (registers: a D tile IS the B operand over its channel index) + V dL/da (memory) ----
 #pragma unroll
@@ -222,22 +192,20 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
       f32x4 q0, q1;
       q0.x = gx[jz][r0 + 0]; q0.y = gx[jz][r0 + 1]; q0.z = gx[jz][r0 + 2]; q0.w = gx[jz][r0 + 3];
       q1.x = gx[jz][r0 + 4]; q1.y = gx[jz][r0 + 5]; q1.z = gx[jz][r0 + 6]; q1.w = gx[jz][r0 + 7];
-      bp_h8 bh, bl;
-      bp_split8(q0, q1, sc2, bh, bl);
+      h8 bh, bl;
+      split8s(q0, q1, sc2, bh, bl);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const bp_h8 ah = w2[((ks * 2 + j) * 2 + 0) * 64];
-        const bp_h8 al = w2[((ks * 2 + j) * 2 + 1) * 64];
-        acc[j] = bp_mfma(al, bh, acc[j]);
-        acc[j] = bp_mfma(ah, bl, acc[j]);
-        acc[j] = bp_mfma(ah, bh, acc[j]);
+        const h8 ah = w2[((ks * 2 + j) * 2 + 0) * 64];
+        const h8 al = w2[((ks * 2 + j) * 2 + 1) * 64];
+        mfma3(ah, al, bh, bl, acc[j]);
       }
     });
     for (int m0 = BP_NK1; m0 < BP_NKM; m0 += BP_PF) {
       wn_static_for<BP_PF>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
-        bp_h8 bh, bl;
-        bp_split8(xr[k][0], xr[k][1], okr[k] ? sc2 : 0.f, bh, bl);
+        h8 bh, bl;
+        split8s(xr[k][0], xr[k][1], okr[k] ? sc2 : 0.f, bh, bl);
         __builtin_amdgcn_sched_barrier(0);
         const int mn = m0 + k + BP_PF;
         if (mn < BP_NKM) load_x(cur, mn, xr[k][0], xr[k][1], okr[k]);
@@ -245,11 +213,9 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
         const int ks2 = BP_NKR + (m0 + k - BP_NK1);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const bp_h8 ah = w2[((ks2 * 2 + j) * 2 + 0) * 64];
-          const bp_h8 al = w2[((ks2 * 2 + j) * 2 + 1) * 64];
-          acc[j] = bp_mfma(al, bh, acc[j]);
-          acc[j] = bp_mfma(ah, bl, acc[j]);
-          acc[j] = bp_mfma(ah, bh, acc[j]);
+          const h8 ah = w2[((ks2 * 2 + j) * 2 + 0) * 64];
+          const h8 al = w2[((ks2 * 2 + j) * 2 + 1) * 64];
+          mfma3(ah, al, bh, bl, acc[j]);
         }
         __builtin_amdgcn_sched_barrier(0);
       });

@@ -9,9 +9,9 @@
 //                       and every backward-data product.
 //  * wn_wgrad         : dW[k][n] = sum_t X[t - shift][k] * G[t][n]  (time is the MFMA K
 //                       dimension), split over time into partial slabs + deterministic reduce.
-#include <hip/hip_fp16.h>
+#include "wn_split16.h"
 
-#include "wn_kernels.h"
+using namespace wn_split16;
 
 // ------------------------------------------------------------------------------------------
 // weight preparation
@@ -440,8 +440,6 @@ __device__ __forceinline__ void wn_wgrad_body(const WnWgUnit& a) {
 // consecutive time steps t0 + 8h .. +7 of its channel for each operand tile; loads stay one dword per
 // lane, 128 contiguous bytes per half wave.  gsc / inv_gsc: exact power-of-two scaling of the
 // gradient operand (running max-abs of its tensor), undone on the accumulators.
-typedef _Float16 wg_h8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ void wn_wgrad_body16(const WnWgUnit& a, float gsc, float inv_gsc) {
   const int lane = threadIdx.x & 63;
   const int tl = lane & 31, h = lane >> 5;
@@ -502,24 +500,13 @@ __device__ __forceinline__ void wn_wgrad_body16(const WnWgUnit& a, float gsc, fl
       for (int j = 0; j < WG_TN; ++j) bv[j][e] = (tv && nin[j]) ? pg[(int64_t)e * a.ldg + 32 * j] : 0.f;
     }
   };
-  // hi = rn(v), lo = rn(v - hi): round-to-nearest keeps the split error at 2^-22 |v| and unbiased (a
-  // packed round-toward-zero split is ~0.15 ms per step faster but its truncation error is visible
-  // after Adam's normalisation on near-zero gradient entries)
-  auto split8 = [&](const float (&v)[8], wg_h8& hi, wg_h8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const _Float16 hh = (_Float16)v[e];
-      hi[e] = hh;
-      lo[e] = (_Float16)(v[e] - (float)hh);
-    }
-  };
   auto compute_chunk = [&](const float (&av)[WG_TM][8], const float (&bv)[WG_TN][8]) {
-    wg_h8 ah[WG_TM], al[WG_TM];
+    h8 ah[WG_TM], al[WG_TM];
 #pragma unroll
     for (int i = 0; i < WG_TM; ++i) split8(av[i], ah[i], al[i]);
 #pragma unroll
     for (int j = 0; j < WG_TN; ++j) {
-      wg_h8 bh, bl;
+      h8 bh, bl;
       float sv[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -529,9 +516,7 @@ __device__ __forceinline__ void wn_wgrad_body16(const WnWgUnit& a, float gsc, fl
       split8(sv, bh, bl);
 #pragma unroll
       for (int i = 0; i < WG_TM; ++i) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);
+        mfma3(ah[i], al[i], bh, bl, acc[i][j]);
       }
     }
   };
@@ -610,16 +595,7 @@ __global__ __launch_bounds__(256, 2) void wn_wgrad_batched_kernel(const WnWgJob*
   u.bias = j.bias_off >= 0 ? row + j.bias_off : nullptr;
   if constexpr (F16) {
     float gsc = 1.0f, inv = 1.0f;
-    if (j.gmax_off >= 0) {
-      const float m = ws[j.gmax_off];
-      if (m > 0.f && m < 3.0e38f) {
-        int e;
-        (void)frexpf(m, &e);
-        e = max(-100, min(100, e));
-        gsc = ldexpf(1.0f, -e);
-        inv = ldexpf(1.0f, e);
-      }
-    }
+    if (j.gmax_off >= 0) pow2_scale(ws[j.gmax_off], gsc, inv);
     wn_wgrad_body16(u, gsc, inv);
   } else {
     wn_wgrad_body(u);

@@ -11,34 +11,9 @@
 //   * gradient operands are pre-scaled by an exact power of two taken from a device-side
 //     running max-abs of the tensor (written by the producing kernel), so that their fp16 lo
 //     parts do not sink into the fp16 subnormal range; the accumulators are scaled back exactly.
-#include <hip/hip_fp16.h>
+#include "wn_split16.h"
 
-#include "wn_kernels.h"
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x16 wn_mfma16g(h8 a, h8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void wn_split8g(const f32x4& q0, const f32x4& q1, float s, h8& hi, h8& lo) {
-  // hi = fp16(q * s); lo = fp16(q * s - hi) with the product unrounded (explicit fma: one operation
-  // fewer in a loop that is VALU-bound on this split, and independent of the contraction mode)
-  const float v[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const _Float16 h = (_Float16)(v[e] * s);
-    hi[e] = h;
-    lo[e] = (_Float16)__builtin_fmaf(v[e], s, -(float)h);
-  }
-}
-
-// global-address-space 16-byte load.  Pointers that went through a per-segment select lose their
-// address space and hipcc emits flat_load: flat loads also count on lgkmcnt, so every LDS fragment
-// wait would drain the activation prefetch, and the compiler waits vmcnt(0) while one is pending.
-__device__ __forceinline__ f32x4 wn_ldg4(const float* p) {
-  return *(const __attribute__((address_space(1))) f32x4*)(p);
-}
+using namespace wn_split16;
 
 // chunk = CH (k-step, row-tile) blocks of 2 KiB  ->  KSC = CH / JT k-steps per chunk
 template <int JT>
@@ -88,7 +63,7 @@ __device__ __forceinline__ void wn_g16_epilogue(const WnGemmArgs& a, f32x16 (&ac
           const int n = c0 + 32 * jj + 8 * rq + 4 * h;   // channel inside [0, D)
           float z[4] = {0.f, 0.f, 0.f, 0.f};
           if (tin) {
-            const f32x4 bf = wn_ldg4(a.bias + n), bg = wn_ldg4(a.bias + D + n);
+            const f32x4 bf = ldg4(a.bias + n), bg = ldg4(a.bias + D + n);
             const float bfv[4] = {bf.x, bf.y, bf.z, bf.w}, bgv[4] = {bg.x, bg.y, bg.z, bg.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -144,17 +119,17 @@ __device__ __forceinline__ void wn_g16_epilogue(const WnGemmArgs& a, f32x16 (&ac
               v[0] = acc[j < JT ? j : 0][4 * rq + 0] * inv_sc; v[1] = acc[j < JT ? j : 0][4 * rq + 1] * inv_sc;
               v[2] = acc[j < JT ? j : 0][4 * rq + 2] * inv_sc; v[3] = acc[j < JT ? j : 0][4 * rq + 3] * inv_sc;
               if (a.bias) {
-                const f32x4 bv = wn_ldg4(a.bias + n0);
+                const f32x4 bv = ldg4(a.bias + n0);
                 v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
               }
               if (a.rowbias) {
-                const f32x4 rb = wn_ldg4(a.rowbias + (int64_t)b * a.ld_rowbias + n0);
+                const f32x4 rb = ldg4(a.rowbias + (int64_t)b * a.ld_rowbias + n0);
                 v[0] += rb.x; v[1] += rb.y; v[2] += rb.z; v[3] += rb.w;
               }
               if (a.addc) {
                 f32x4 cv;
                 if constexpr (PRE == 1) cv = pre->addc[j < JT ? j : 0][rq];
-                else cv = wn_ldg4(a.addc + row * a.ld_addc + n0);
+                else cv = ldg4(a.addc + row * a.ld_addc + n0);
                 v[0] += cv.x; v[1] += cv.y; v[2] += cv.z; v[3] += cv.w;
               }
               if (epi == WN_EPI_PLAIN) {
@@ -163,7 +138,7 @@ __device__ __forceinline__ void wn_g16_epilogue(const WnGemmArgs& a, f32x16 (&ac
               } else if (epi == WN_EPI_DACT) {
                 f32x4 yv;
                 if constexpr (PRE == 3) yv = pre->aux[j < JT ? j : 0][rq];
-                else yv = wn_ldg4(a.aux + row * a.ld_aux + n0);
+                else yv = ldg4(a.aux + row * a.ld_aux + n0);
                 v[0] *= wn_dact_from_y(yv.x, a.act); v[1] *= wn_dact_from_y(yv.y, a.act);
                 v[2] *= wn_dact_from_y(yv.z, a.act); v[3] *= wn_dact_from_y(yv.w, a.act);
               } else {
@@ -172,8 +147,8 @@ __device__ __forceinline__ void wn_g16_epilogue(const WnGemmArgs& a, f32x16 (&ac
                   gv = pre->aux[j < JT ? j : 0][rq];
                   zv = pre->aux2[j < JT ? j : 0][rq];
                 } else {
-                  gv = wn_ldg4(a.aux + row * a.ld_aux + n0);
-                  zv = wn_ldg4(a.aux2 + row * a.ld_aux2 + n0);
+                  gv = ldg4(a.aux + row * a.ld_aux + n0);
+                  zv = ldg4(a.aux2 + row * a.ld_aux2 + n0);
                 }
                 // each pass evaluates only the derivative it stores (filter half, then gate half)
                 if (part == 0) {
@@ -235,13 +210,7 @@ __global__ __launch_bounds__(512, 2) void wn_gemm_rows16_kernel(WnGemmArgs a, co
   if (absmax_in0) {
     float m = *absmax_in0;
     if (absmax_in1) m = fmaxf(m, *absmax_in1);
-    if (m > 0.f && m < 3.0e38f) {
-      int e;
-      (void)frexpf(m, &e);               // m = f * 2^e, f in [0.5, 1)
-      e = max(-100, min(100, e));
-      sc = ldexpf(1.0f, -e);             // scaled values lie in [-1, 1)
-      inv_sc = ldexpf(1.0f, e);
-    }
+    pow2_scale(m, sc, inv_sc);
   }
 
   const int tiles_per_b = (a.T + 31) >> 5;
@@ -374,10 +343,8 @@ __global__ __launch_bounds__(512, 2) void wn_gemm_rows16_kernel(WnGemmArgs a, co
           fr[(blk + 1) & 1][1] = wl[((blk + 1) * 2 + 1) * 64];
         }
         h8 bh, bl;
-        wn_split8g(xq[k][0], xq[k][1], okv[k] ? sc : 0.f, bh, bl);       // masked rows / k-steps contribute zero
-        acc[j] = wn_mfma16g(fr[blk & 1][1], bh, acc[j]);
-        acc[j] = wn_mfma16g(fr[blk & 1][0], bl, acc[j]);
-        acc[j] = wn_mfma16g(fr[blk & 1][0], bh, acc[j]);
+        split8s(xq[k][0], xq[k][1], okv[k] ? sc : 0.f, bh, bl);       // masked rows / k-steps contribute zero
+        mfma3(fr[blk & 1][0], fr[blk & 1][1], bh, bl, acc[j]);
         __builtin_amdgcn_sched_barrier(0);
       });
       // this chunk's activation buffer is free again once its LDS reads have returned
@@ -445,13 +412,7 @@ __global__ __launch_bounds__(512, 1) void wn_gemm_rows16_wide_kernel(WnGemmArgs 
   if (absmax_in0) {
     float m = *absmax_in0;
     if (absmax_in1) m = fmaxf(m, *absmax_in1);
-    if (m > 0.f && m < 3.0e38f) {
-      int e;
-      (void)frexpf(m, &e);
-      e = max(-100, min(100, e));
-      sc = ldexpf(1.0f, -e);
-      inv_sc = ldexpf(1.0f, e);
-    }
+    pow2_scale(m, sc, inv_sc);
   }
 
   const int tiles_per_b = (a.T + 31) >> 5;
@@ -542,16 +503,14 @@ __global__ __launch_bounds__(512, 1) void wn_gemm_rows16_wide_kernel(WnGemmArgs 
           fr[0][0] = wl[0];
           fr[0][1] = wl[64];
           h8 bh, bl;
-          wn_split8g(x0, x1, okr[i] ? sc : 0.f, bh, bl);               // masked rows / k-steps contribute zero
+          split8s(x0, x1, okr[i] ? sc : 0.f, bh, bl);               // masked rows / k-steps contribute zero
           wn_static_for<JT>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             if constexpr (j + 1 < JT) {
               fr[(j + 1) & 1][0] = wl[((j + 1) * 2 + 0) * 64];
               fr[(j + 1) & 1][1] = wl[((j + 1) * 2 + 1) * 64];
             }
-            acc[j] = wn_mfma16g(fr[j & 1][1], bh, acc[j]);
-            acc[j] = wn_mfma16g(fr[j & 1][0], bl, acc[j]);
-            acc[j] = wn_mfma16g(fr[j & 1][0], bh, acc[j]);
+            mfma3(fr[j & 1][0], fr[j & 1][1], bh, bl, acc[j]);
             __builtin_amdgcn_sched_barrier(0);
           });
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // this chunk's buffers are free again
@@ -585,13 +544,7 @@ __global__ __launch_bounds__(64) void wn_gemm_rows16_thin_kernel(WnGemmArgs a, c
   if (absmax_in0) {
     float m = *absmax_in0;
     if (absmax_in1) m = fmaxf(m, *absmax_in1);
-    if (m > 0.f && m < 3.0e38f) {
-      int e;
-      (void)frexpf(m, &e);
-      e = max(-100, min(100, e));
-      sc = ldexpf(1.0f, -e);
-      inv_sc = ldexpf(1.0f, e);
-    }
+    pow2_scale(m, sc, inv_sc);
   }
   const int tiles_per_b = (a.T + 31) >> 5;
   const int tile = blockIdx.x;
@@ -637,8 +590,8 @@ __global__ __launch_bounds__(64) void wn_gemm_rows16_thin_kernel(WnGemmArgs a, c
       if (ks >= ks_end[s - 1]) { xr = xrow_s[s]; ok = xok_s[s]; kk = ks - ks_end[s - 1]; }
     if (ok) {
       if (plane_ks0 > 0 && ks < ks_end[0]) xr += (int64_t)(kk / plane_ks0) * plane_st0 - (int64_t)(kk / plane_ks0) * plane_ks0 * 16;
-      q0 = wn_ldg4(xr + 16 * kk);
-      q1 = wn_ldg4(xr + 16 * kk + 8);
+      q0 = ldg4(xr + 16 * kk);
+      q1 = ldg4(xr + 16 * kk + 8);
     }
   };
   // hi|lo fragments of (k-step, column tile jb); k-steps past the end are clamped (their activations are zero)
@@ -663,10 +616,8 @@ __global__ __launch_bounds__(64) void wn_gemm_rows16_thin_kernel(WnGemmArgs a, c
     wn_static_for<PD>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       h8 bh, bl;
-      wn_split8g(xv[i][0], xv[i][1], sc, bh, bl);
-      acc[0] = wn_mfma16g(wf[i][1], bh, acc[0]);
-      acc[0] = wn_mfma16g(wf[i][0], bl, acc[0]);
-      acc[0] = wn_mfma16g(wf[i][0], bh, acc[0]);
+      split8s(xv[i][0], xv[i][1], sc, bh, bl);
+      mfma3(wf[i][0], wf[i][1], bh, bl, acc[0]);
       load_w(ks0 + i + PD, wf[i][0], wf[i][1]);
       load_x(ks0 + i + PD, xv[i][0], xv[i][1]);
       __builtin_amdgcn_sched_barrier(0);
@@ -718,13 +669,7 @@ __global__ __launch_bounds__(512, 2) void wn_gemm_rows16_resident_kernel(WnGemmA
   if (absmax_in0) {
     float m = *absmax_in0;
     if (absmax_in1) m = fmaxf(m, *absmax_in1);
-    if (m > 0.f && m < 3.0e38f) {
-      int e;
-      (void)frexpf(m, &e);
-      e = max(-100, min(100, e));
-      sc = ldexpf(1.0f, -e);
-      inv_sc = ldexpf(1.0f, e);
-    }
+    pow2_scale(m, sc, inv_sc);
   }
   // Segment fields are read straight from the kernel-argument block by wave-uniform selects (scalar
   // loads).  Copies of them in local arrays or captured locals end up in scratch memory once the
@@ -758,8 +703,8 @@ __global__ __launch_bounds__(512, 2) void wn_gemm_rows16_resident_kernel(WnGemmA
     const int ts = c.t - sh;
     const bool ok = c.t < a.T && ts >= 0 && ts < a.T;
     const float* src = bx + ((int64_t)c.b * a.T + (ok ? ts : 0)) * ld + 4 * h + 16 * kk;
-    q0 = wn_ldg4(src);
-    q1 = wn_ldg4(src + 8);
+    q0 = ldg4(src);
+    q1 = ldg4(src + 8);
     okout = ok;
   };
   const int64_t tstride = (int64_t)gridDim.x * G::WAVES;
@@ -790,10 +735,10 @@ __global__ __launch_bounds__(512, 2) void wn_gemm_rows16_resident_kernel(WnGemmA
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
           const int n0 = 32 * j + 8 * rq + 4 * h;
-          if constexpr (PREK == 1) pre.addc[j][rq] = wn_ldg4(a.addc + row * a.ld_addc + n0);
+          if constexpr (PREK == 1) pre.addc[j][rq] = ldg4(a.addc + row * a.ld_addc + n0);
           if constexpr (PREK == 2) {
-            pre.aux[j][rq] = wn_ldg4(a.aux + row * a.ld_aux + n0);
-            pre.aux2[j][rq] = wn_ldg4(a.aux2 + row * a.ld_aux2 + n0);
+            pre.aux[j][rq] = ldg4(a.aux + row * a.ld_aux + n0);
+            pre.aux2[j][rq] = ldg4(a.aux2 + row * a.ld_aux2 + n0);
           }
         }
     }
@@ -806,7 +751,7 @@ __global__ __launch_bounds__(512, 2) void wn_gemm_rows16_resident_kernel(WnGemmA
       wn_static_for<PF>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         h8 bh, bl;
-        wn_split8g(xr_[k][0], xr_[k][1], okr[k] ? sc : 0.f, bh, bl);    // masked rows contribute zero
+        split8s(xr_[k][0], xr_[k][1], okr[k] ? sc : 0.f, bh, bl);    // masked rows contribute zero
         __builtin_amdgcn_sched_barrier(0);
         const int ksn = ks0 + k + PF;
         if (ksn < nks_total) load_x(cur, ksn, xr_[k][0], xr_[k][1], okr[k]);
@@ -815,9 +760,7 @@ __global__ __launch_bounds__(512, 2) void wn_gemm_rows16_resident_kernel(WnGemmA
         for (int j = 0; j < JT; ++j) {
           const h8 ah = wl[(((ks0 + k) * JT + j) * 2 + 0) * 64];
           const h8 al = wl[(((ks0 + k) * JT + j) * 2 + 1) * 64];
-          acc[j] = wn_mfma16g(al, bh, acc[j]);
-          acc[j] = wn_mfma16g(ah, bl, acc[j]);
-          acc[j] = wn_mfma16g(ah, bh, acc[j]);
+          mfma3(ah, al, bh, bl, acc[j]);
         }
         __builtin_amdgcn_sched_barrier(0);
       });

@@ -12,13 +12,13 @@
 //     never stops at a tile boundary (the old kernel drained and refilled its ring per tile);
 //   * a wave owns RT = 2 row tiles (64 time steps): every weight fragment read from LDS feeds two products, and the image
 //     is streamed from L2 once per 256 rows instead of once per 128 (the old kernel's variant of this spilled);
-//   * every request is an inline-assembly LDS-DMA from a scalar base (wn_stream.h), the only waits are counted vmcnt.
+//   * every request is an inline-assembly LDS-DMA from a scalar base (wn_split16.h), the only waits are counted vmcnt.
 // Measured: configs[1] (K = 1920) 294 -> 270 us, configs[3] (K = 3840) 0.73 -> 0.71 ms: the pipeline was not what held this
 // contraction back (two k-steps of operands per wave in flight are right at bandwidth x latency).
-#include "wn_stream.h"
+#include "wn_split16.h"
 #include "wn_sample.h"
 
-using namespace wn_stream;
+using namespace wn_split16;
 
 namespace {
 
@@ -67,16 +67,7 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
   const bool has_bias = a.bias != nullptr;
   __syncthreads();
   float sc = 1.0f, inv_sc = 1.0f;
-  if (ACT == -2 && a.absmax_in) {
-    const float m = *a.absmax_in;
-    if (m > 0.f && m < 3.0e38f) {
-      int e;
-      (void)frexpf(m, &e);               // m = f * 2^e, f in [0.5, 1)
-      e = max(-100, min(100, e));
-      sc = ldexpf(1.0f, -e);             // scaled values lie in [-1, 1)
-      inv_sc = ldexpf(1.0f, e);
-    }
-  }
+  if (ACT == -2 && a.absmax_in) pow2_scale(*a.absmax_in, sc, inv_sc);
 
   const int kpp = a.plane_k >> 4;                      // k-steps per plane
   const int nsteps = a.nplanes * kpp;                  // >= 3 (launcher)
@@ -187,9 +178,7 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
         }
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-          acc[rt][j] = mfma16(fr[j & 1][1], bh[rt], acc[rt][j]);
-          acc[rt][j] = mfma16(fr[j & 1][0], bl[rt], acc[rt][j]);
-          acc[rt][j] = mfma16(fr[j & 1][0], bh[rt], acc[rt][j]);
+          mfma3(fr[j & 1][0], fr[j & 1][1], bh[rt], bl[rt], acc[rt][j]);
         }
         // one request group of the look-ahead k-step per product block
         if constexpr (j < PT) wpiece(j);

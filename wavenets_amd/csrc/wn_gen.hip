@@ -18,22 +18,10 @@
 // The per-element MFMA sequence (bias, taps in k order, lo*hi, hi*lo, hi*hi) is the one of
 // wn_layer16.hip, merely cut between two launches, so every value is bit-identical to what the
 // sliding-window path computes for the same sample.
-#include <hip/hip_fp16.h>
-
-#include "wn_kernels.h"
+#include "wn_split16.h"
 #include "wn_sample.h"
 
-typedef _Float16 gn_h8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void gn_split8(const f32x4& q0, const f32x4& q1, gn_h8& hi, gn_h8& lo) {
-  const float v[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const _Float16 h = (_Float16)v[e];
-    hi[e] = h;
-    lo[e] = (_Float16)(v[e] - (float)h);
-  }
-}
+using namespace wn_split16;
 
 template <int R32, int D32, int KS>
 struct GnShape {
@@ -57,8 +45,8 @@ __device__ __forceinline__ void gn_pre_body(const WnGenStepArgs& a, int tile, in
   const int ur = utt < a.B ? utt : 0;
   const WnGenBlock blk = a.blocks[b];
   // weight fragments of the older taps: all requested at once (one L2 round trip)
-  const gn_h8* wd = reinterpret_cast<const gn_h8*>(a.ws + blk.w16d_off) + lane;
-  gn_h8 wf[KS0][JU][2];
+  const h8* wd = reinterpret_cast<const h8*>(a.ws + blk.w16d_off) + lane;
+  h8 wf[KS0][JU][2];
 #pragma unroll
   for (int ks = 0; ks < KS0; ++ks)
 #pragma unroll
@@ -98,13 +86,11 @@ __device__ __forceinline__ void gn_pre_body(const WnGenStepArgs& a, int tile, in
   wn_static_for<KS0>([&](auto sc) {
     constexpr int ks = decltype(sc)::value;
     constexpr int tap = ks / KSR, kk = ks % KSR;
-    gn_h8 bh, bl;
-    gn_split8(xq[tap][2 * kk], xq[tap][2 * kk + 1], bh, bl);
+    h8 bh, bl;
+    split8(xq[tap][2 * kk], xq[tap][2 * kk + 1], bh, bl);
 #pragma unroll
     for (int j = 0; j < JU; ++j) {
-      u[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[ks][j][1], bh, u[j], 0, 0, 0);
-      u[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[ks][j][0], bl, u[j], 0, 0, 0);
-      u[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[ks][j][0], bh, u[j], 0, 0, 0);
+      mfma3(wf[ks][j][0], wf[ks][j][1], bh, bl, u[j]);
     }
   });
   // lane-major image [b][tile][JU * 4 quads][64 lanes] of float4: contiguous KiB per quad (LDS-DMA friendly)
@@ -151,8 +137,8 @@ __global__ __launch_bounds__(64) void wn_gen_pre_kernel(WnGenStepArgs a) {
 // the plain way the compiler reads, waits, multiplies, reads, ... and every k-step pays an LDS round trip (measured on
 // the conv1 waves: 1220 -> 550 cycles for the 12 products).
 template <int NK>
-__device__ __forceinline__ void gn_mac(f32x16& acc, const gn_h8 (&w)[NK][2], const gn_h8* zl) {
-  gn_h8 bh[2], bl[2];
+__device__ __forceinline__ void gn_mac(f32x16& acc, const h8 (&w)[NK][2], const h8* zl) {
+  h8 bh[2], bl[2];
   bh[0] = zl[0];
   bl[0] = zl[64];
   wn_static_for<NK>([&](auto kc) {
@@ -162,9 +148,7 @@ __device__ __forceinline__ void gn_mac(f32x16& acc, const gn_h8 (&w)[NK][2], con
       bl[(ks + 1) & 1] = zl[((ks + 1) * 2 + 1) * 64];
       __builtin_amdgcn_sched_barrier(0);            // keep the two reads above the products below
     }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ks][1], bh[ks & 1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ks][0], bl[ks & 1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ks][0], bh[ks & 1], acc, 0, 0, 0);
+    mfma3(w[ks][0], w[ks][1], bh[ks & 1], bl[ks & 1], acc);
   });
 }
 #define WN_GEN_HELPERS_PER_XCD 2
@@ -172,7 +156,7 @@ __device__ __forceinline__ void gn_mac(f32x16& acc, const gn_h8 (&w)[NK][2], con
 // at every use inside a loop, which would cut the distance of a 3-blocks-ahead fetch to one block.  vmcnt retires in
 // order, so "at most N younger operations outstanding" is exact as long as every iteration issues the same number of
 // vector memory operations -- the fetches past the last block are therefore still issued, all lanes on one line.
-__device__ __forceinline__ void gn_ld16(gn_h8& dst, const void* p) {
+__device__ __forceinline__ void gn_ld16(h8& dst, const void* p) {
   asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
 }
 __device__ __forceinline__ void gn_ld16(f32x4& dst, const void* p) {
@@ -259,9 +243,9 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
     for (int hf = 0; hf < 2; ++hf) {
       const f32x4 q0 = {x[8 * hf + 0], x[8 * hf + 1], x[8 * hf + 2], x[8 * hf + 3]};
       const f32x4 q1 = {x[8 * hf + 4], x[8 * hf + 5], x[8 * hf + 6], x[8 * hf + 7]};
-      gn_h8 bh, bl;
-      gn_split8(q0, q1, bh, bl);
-      gn_h8* dst = reinterpret_cast<gn_h8*>(xop + (2 * j + hf) * 2048) + lane;
+      h8 bh, bl;
+      split8(q0, q1, bh, bl);
+      h8* dst = reinterpret_cast<h8*>(xop + (2 * j + hf) * 2048) + lane;
       dst[0] = bh;
       dst[64] = bl;
     }
@@ -275,7 +259,7 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
     // (no barrier between phase A and the gate).  Only the lanes' fetch addresses differ from a plain tile: every output
     // element is the same dot product over the same operands in the same order.
     // per iteration: 2 KSR + 4 loads (fetch), then 2 stores (z row) -- see the wait in phase A
-    gn_h8 wa[NS][KSR][2];
+    h8 wa[NS][KSR][2];
     f32x4 u0q[NS][4];                                 // the u0 images of the tile (dead columns read column 0's lines)
     const int ulane = live ? lane : h * 32;
     const int half16 = 16 * (wave & 1);               // which 16 rows of the image tiles
@@ -283,8 +267,8 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
     auto fetch_a = [&](auto sc, int b, int64_t w16d_off) {
       constexpr int s = decltype(sc)::value;
       const bool real = b < nblocks;                  // past the end: every lane on one line of the parameters
-      const gn_h8* wd = real ? reinterpret_cast<const gn_h8*>(a.ws + w16d_off) + (int64_t)KS0 * JU * 128 + wlane
-                             : reinterpret_cast<const gn_h8*>(a.params);
+      const h8* wd = real ? reinterpret_cast<const h8*>(a.ws + w16d_off) + (int64_t)KS0 * JU * 128 + wlane
+                             : reinterpret_cast<const h8*>(a.params);
       const int m = real ? 64 : 0;
 #pragma unroll
       for (int kk = 0; kk < KSR; ++kk) {
@@ -332,7 +316,7 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
           for (int rq = 0; rq < 4; ++rq) {
             u[4 * rq + 0] = u0q[s][rq].x; u[4 * rq + 1] = u0q[s][rq].y; u[4 * rq + 2] = u0q[s][rq].z; u[4 * rq + 3] = u0q[s][rq].w;
           }
-          gn_mac<KSR>(u, wa[s], reinterpret_cast<const gn_h8*>(xop) + lane);
+          gn_mac<KSR>(u, wa[s], reinterpret_cast<const h8*>(xop) + lane);
           if (wave == 0) GN_TS(0, b, 2);
           // the gate: accumulators 0..7 are filter channels 16 w + {4h.., 8 + 4h..}, 8..15 their gate channels
           const f32x4 f0 = {u[0], u[1], u[2], u[3]}, f1 = {u[4], u[5], u[6], u[7]};
@@ -342,9 +326,9 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
           z0.z = wn_tanh_fast(f0.z) * wn_sigmoid_fast(g0.z); z0.w = wn_tanh_fast(f0.w) * wn_sigmoid_fast(g0.w);
           z1.x = wn_tanh_fast(f1.x) * wn_sigmoid_fast(g1.x); z1.y = wn_tanh_fast(f1.y) * wn_sigmoid_fast(g1.y);
           z1.z = wn_tanh_fast(f1.z) * wn_sigmoid_fast(g1.z); z1.w = wn_tanh_fast(f1.w) * wn_sigmoid_fast(g1.w);
-          gn_h8 bh, bl;
-          gn_split8(z0, z1, bh, bl);
-          gn_h8* zd = reinterpret_cast<gn_h8*>(zop + (b & 1) * ZOP_BYTES + wave * 2048) + lane;
+          h8 bh, bl;
+          split8(z0, z1, bh, bl);
+          h8* zd = reinterpret_cast<h8*>(zop + (b & 1) * ZOP_BYTES + wave * 2048) + lane;
           zd[0] = bh;
           zd[64] = bl;
           if (wave == 0) GN_TS(0, b, 4);
@@ -371,11 +355,11 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
     __builtin_amdgcn_s_setprio(3);
     // ================= conv1 waves: carry the block input x; phase C (o tile `cw`) =================
     // per iteration: 4 stores (ring) at the top, 2 KS2 loads (fetch) at the bottom -- see the wait in phase C
-    gn_h8 wc[NS][KS2][2];
+    h8 wc[NS][KS2][2];
     float* const bias_l = reinterpret_cast<float*>(ubuf);   // [block][R]; wave cw fills and reads columns 32 cw .. 32 cw + 31
     auto fetch_c = [&](auto sc, bool real, int64_t w16r_off) {
       constexpr int s = decltype(sc)::value;
-      const gn_h8* wr = real ? reinterpret_cast<const gn_h8*>(a.ws + w16r_off) + lane : reinterpret_cast<const gn_h8*>(a.params);
+      const h8* wr = real ? reinterpret_cast<const h8*>(a.ws + w16r_off) + lane : reinterpret_cast<const h8*>(a.params);
       const int m = real ? 64 : 0;
 #pragma unroll
       for (int ks = 0; ks < KS2; ++ks) {
@@ -464,7 +448,7 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
             const f32x4 bv = *reinterpret_cast<const f32x4*>(bias_l + b * R + 32 * cw + 8 * rq + 4 * h);
             o[4 * rq + 0] = bv.x; o[4 * rq + 1] = bv.y; o[4 * rq + 2] = bv.z; o[4 * rq + 3] = bv.w;
           }
-          gn_mac<KS2>(o, wc[s], reinterpret_cast<const gn_h8*>(zop + (b & 1) * ZOP_BYTES) + lane);
+          gn_mac<KS2>(o, wc[s], reinterpret_cast<const h8*>(zop + (b & 1) * ZOP_BYTES) + lane);
 #pragma unroll
           for (int r = 0; r < 16; ++r) x[r] = a.residual ? o[r] + x[r] : o[r];
           if (b + 1 < nblocks) put_xop(x, cw);
@@ -495,11 +479,11 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
     // tile t1 between (1) and (2) of block b + 1 -- z_b stays valid there because the z operands are double-buffered.
     const int t0 = 2 * sw, t1 = 2 * sw + 1;
     const bool has1 = t1 < a.skip_tiles;
-    gn_h8 w0[KS2][2], w1[KS2][2];
+    h8 w0[KS2][2], w1[KS2][2];
     // vector memory operations of a skip wave: 2 KS2 loads per pre_skip, always issued (see the waits)
-    auto pre_skip = [&](gn_h8 (&w)[KS2][2], int b, int t) {
+    auto pre_skip = [&](h8 (&w)[KS2][2], int b, int t) {
       const bool real = b < nblocks;
-      const gn_h8* wsi = real ? reinterpret_cast<const gn_h8*>(a.ws + a.skip_w16_off) + lane : reinterpret_cast<const gn_h8*>(a.params);
+      const h8* wsi = real ? reinterpret_cast<const h8*>(a.ws + a.skip_w16_off) + lane : reinterpret_cast<const h8*>(a.params);
       const int64_t m = real ? 64 : 0;
 #pragma unroll
       for (int ks = 0; ks < KS2; ++ks) {
@@ -509,20 +493,20 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
       }
     };
     // the other tile's fetch (if there is a second tile) is the only younger operation
-    auto landed = [&](gn_h8 (&w)[KS2][2]) {
+    auto landed = [&](h8 (&w)[KS2][2]) {
       if (has1) gn_vmwait<2 * KS2>(); else gn_vmwait<0>();
 #pragma unroll
       for (int ks = 0; ks < KS2; ++ks) { gn_landed(w[ks][0]); gn_landed(w[ks][1]); }
     };
-    auto mac = [&](f32x16& acc, const gn_h8 (&w)[KS2][2], int half) {
-      gn_mac<KS2>(acc, w, reinterpret_cast<const gn_h8*>(zop + half * ZOP_BYTES) + lane);
+    auto mac = [&](f32x16& acc, const h8 (&w)[KS2][2], int half) {
+      gn_mac<KS2>(acc, w, reinterpret_cast<const h8*>(zop + half * ZOP_BYTES) + lane);
     };
     f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
     // The two loops below contain no conditional fetch: a fetch under a branch makes the fetched registers a phi of two
     // definitions, and the copies that resolve it would read registers whose load is still in flight.
-    auto settle = [&](gn_h8 (&w)[KS2][2]) {          // as in the chain role
+    auto settle = [&](h8 (&w)[KS2][2]) {          // as in the chain role
       gn_vmwait<0>();
 #pragma unroll
       for (int ks = 0; ks < KS2; ++ks) { gn_landed(w[ks][0]); gn_landed(w[ks][1]); }
@@ -641,9 +625,9 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
     for (int ks = wave; ks < nks; ks += 8) {
       const f32x4 q0 = *reinterpret_cast<const f32x4*>(row + 16 * ks);
       const f32x4 q1 = *reinterpret_cast<const f32x4*>(row + 16 * ks + 8);
-      gn_h8 bh, bl;
-      gn_split8(q0, q1, bh, bl);
-      gn_h8* dst = reinterpret_cast<gn_h8*>(smem + ks * 2048) + lane;
+      h8 bh, bl;
+      split8(q0, q1, bh, bl);
+      h8* dst = reinterpret_cast<h8*>(smem + ks * 2048) + lane;
       dst[0] = bh;
       dst[64] = bl;
     }
@@ -659,10 +643,10 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      const gn_h8* wimg = reinterpret_cast<const gn_h8*>(a.ws + a.w16_off[li]) + lane;
-      const gn_h8* xl = reinterpret_cast<const gn_h8*>(ib) + lane;
+      const h8* wimg = reinterpret_cast<const h8*>(a.ws + a.w16_off[li]) + lane;
+      const h8* xl = reinterpret_cast<const h8*>(ib) + lane;
       // weight fragments four k-steps ahead (register ring, static slots)
-      gn_h8 wf[4][2];
+      h8 wf[4][2];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int64_t blk = ((int64_t)min(i, nks - 1) * nt + wave) * 2;
@@ -673,11 +657,9 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
         wn_static_for<4>([&](auto ic) {
           constexpr int i = decltype(ic)::value;
           if (ks0 + i < nks) {                          // wave-uniform
-            const gn_h8 bh = xl[((ks0 + i) * 2 + 0) * 64];
-            const gn_h8 bl = xl[((ks0 + i) * 2 + 1) * 64];
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i][1], bh, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i][0], bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i][0], bh, acc, 0, 0, 0);
+            const h8 bh = xl[((ks0 + i) * 2 + 0) * 64];
+            const h8 bl = xl[((ks0 + i) * 2 + 1) * 64];
+            mfma3(wf[i][0], wf[i][1], bh, bl, acc);
             const int64_t blk = ((int64_t)min(ks0 + i + 4, nks - 1) * nt + wave) * 2;
             wf[i][0] = wimg[(blk + 0) * 64];
             wf[i][1] = wimg[(blk + 1) * 64];
@@ -722,9 +704,9 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
         for (int hf = 0; hf < 2; ++hf) {
           const f32x4 q0 = {v[8 * hf + 0], v[8 * hf + 1], v[8 * hf + 2], v[8 * hf + 3]};
           const f32x4 q1 = {v[8 * hf + 4], v[8 * hf + 5], v[8 * hf + 6], v[8 * hf + 7]};
-          gn_h8 bh, bl;
-          gn_split8(q0, q1, bh, bl);
-          gn_h8* dst = reinterpret_cast<gn_h8*>(ob + (2 * wave + hf) * 2048) + lane;
+          h8 bh, bl;
+          split8(q0, q1, bh, bl);
+          h8* dst = reinterpret_cast<h8*>(ob + (2 * wave + hf) * 2048) + lane;
           dst[0] = bh;
           dst[64] = bl;
         }

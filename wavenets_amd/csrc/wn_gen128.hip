@@ -13,14 +13,13 @@
 // Bit for bit the arithmetic of wn_layer_fwd_s128_kernel (the sliding window's kernel) per output element: accumulators
 // start at the bias (+ conditioning bias), k-steps ascending with lo*hi, hi*lo, hi*hi each, the same gate functions, the
 // 1x1 the same way from the z tiles, x_out = o + residual in fp32.  tests: queued == sliding window.
-#include "wn_stream.h"
+#include "wn_split16.h"
 
-using namespace wn_stream;
+using namespace wn_split16;
 
 namespace {
 
 __device__ __forceinline__ h8 ldg_h8(const void* p) { return *(const __attribute__((address_space(1))) h8*)(p); }
-__device__ __forceinline__ f32x4 ldg4(const float* p) { return *(const __attribute__((address_space(1))) f32x4*)(p); }
 
 }  // namespace
 
@@ -91,9 +90,7 @@ __global__ __launch_bounds__(512, 2) void wn_gen_block128_kernel(WnLayerFwdArgs 
     const f32x4 q0 = xs[(c * 2 + 0) * 64 + lane], q1 = xs[(c * 2 + 1) * 64 + lane];
     h8 bh, bl;
     split8(q0, q1, bh, bl);
-    u = mfma16(wd[c][1], bh, u);
-    u = mfma16(wd[c][0], bl, u);
-    u = mfma16(wd[c][0], bh, u);
+    mfma3(wd[c][0], wd[c][1], bh, bl, u);
   }
   // ---- gate: tiles 4..7 hold the gate channels of tiles 0..3 ----
   if (wave >= 4) {
@@ -149,9 +146,7 @@ __global__ __launch_bounds__(512, 2) void wn_gen_block128_kernel(WnLayerFwdArgs 
       q1.z = zs[(jz * 16 + r0 + 6) * 64 + lane]; q1.w = zs[(jz * 16 + r0 + 7) * 64 + lane];
       h8 bh, bl;
       split8(q0, q1, bh, bl);
-      o = mfma16(wr[ks][1], bh, o);
-      o = mfma16(wr[ks][0], bl, o);
-      o = mfma16(wr[ks][0], bh, o);
+      mfma3(wr[ks][0], wr[ks][1], bh, bl, o);
     }
     // ---- residual, range guard, x_out ----
     if (rok) {
@@ -271,9 +266,7 @@ __global__ __launch_bounds__(512, 2) void wn_gen_chain128_kernel(WnGen128Args a)
       const f32x4 q0 = xs[(c * 2 + 0) * 64 + lane], q1 = xs[(c * 2 + 1) * 64 + lane];
       h8 bh, bl;
       split8(q0, q1, bh, bl);
-      u = mfma16(wd[c][1], bh, u);
-      u = mfma16(wd[c][0], bl, u);
-      u = mfma16(wd[c][0], bh, u);
+      mfma3(wd[c][0], wd[c][1], bh, bl, u);
     }
     if (wave >= 4) {
 #pragma unroll
@@ -318,9 +311,7 @@ __global__ __launch_bounds__(512, 2) void wn_gen_chain128_kernel(WnGen128Args a)
         q1.z = zs[(jz * 16 + r0 + 6) * 64 + lane]; q1.w = zs[(jz * 16 + r0 + 7) * 64 + lane];
         h8 bh, bl;
         split8(q0, q1, bh, bl);
-        o = mfma16(wr[ks][1], bh, o);
-        o = mfma16(wr[ks][0], bl, o);
-        o = mfma16(wr[ks][0], bh, o);
+        mfma3(wr[ks][0], wr[ks][1], bh, bl, o);
       }
       // residual = this lane's own pieces of the newest tap in LDS; x_out goes back into the same pieces (the next block's
       // newest tap) and to the next block's ring slot
@@ -357,9 +348,7 @@ __global__ __launch_bounds__(512, 2) void wn_gen_chain128_kernel(WnGen128Args a)
         q1.z = zs[(jz * 16 + r0 + 6) * 64 + lane]; q1.w = zs[(jz * 16 + r0 + 7) * 64 + lane];
         h8 bh, bl;
         split8(q0, q1, bh, bl);
-        sacc = mfma16(wr[ks][1], bh, sacc);
-        sacc = mfma16(wr[ks][0], bl, sacc);
-        sacc = mfma16(wr[ks][0], bh, sacc);
+        mfma3(wr[ks][0], wr[ks][1], bh, bl, sacc);
       }
     }
     // (the next iteration's barrier after staging orders these LDS writes before the conv reads them; zs is rewritten
@@ -450,17 +439,10 @@ __global__ __launch_bounds__(512, 2) void wn_gen_relay128_kernel(WnGen128Args a)
   h8* const zh = reinterpret_cast<h8*>(smem + NK1 * 2048 + 1024 * 16);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tl = lane & 31, h = lane >> 5;
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  // quad q (0, 1) of k-step ks of lane l: the split8 of wn_stream.h on one half of the operand
+  // quad q (0, 1) of k-step ks of lane l: the split8 on one half of the operand
   auto put_quad = [&](h8* base, int ks, int q, int l, const f32x4& v) {
-    const float f[4] = {v.x, v.y, v.z, v.w};
     h4 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const _Float16 hh = (_Float16)f[e];
-      hi[e] = hh;
-      lo[e] = (_Float16)(f[e] - (float)hh);
-    }
+    split4(v, hi, lo);
     h4* b4 = reinterpret_cast<h4*>(base);
     b4[((ks * 2 + 0) * 64 + l) * 2 + q] = hi;
     b4[((ks * 2 + 1) * 64 + l) * 2 + q] = lo;
@@ -478,9 +460,7 @@ __global__ __launch_bounds__(512, 2) void wn_gen_relay128_kernel(WnGen128Args a)
         bl[(ks + 1) & 1] = bop[((K0 + ks + 1) * 2 + 1) * 64 + lane];
         __builtin_amdgcn_sched_barrier(0);
       }
-      acc = mfma16(w_of(K0 + ks, 1), bh[ks & 1], acc);
-      acc = mfma16(w_of(K0 + ks, 0), bl[ks & 1], acc);
-      acc = mfma16(w_of(K0 + ks, 0), bh[ks & 1], acc);
+      mfma3(w_of(K0 + ks, 0), w_of(K0 + ks, 1), bh[ks & 1], bl[ks & 1], acc);
     });
   };
   const int b = (int)blockIdx.x / a.ntiles, tile = (int)blockIdx.x % a.ntiles;   // block-major: predecessors first

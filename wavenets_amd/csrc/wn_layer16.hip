@@ -13,27 +13,9 @@
 //   * every output tile (x_out, z, tanh, sigmoid) is transposed through a wave-private LDS
 //     stage and leaves as full 256-byte row segments (1 KiB per wave store instruction)
 //   * no barrier inside the tile loop: waves only share the read-only weights.
-#include <hip/hip_fp16.h>
+#include "wn_split16.h"
 
-#include "wn_kernels.h"
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x16 wn_mfma16(h8 a, h8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-// split 8 fp32 values (two float4 quads) into fp16 hi / lo fragments
-__device__ __forceinline__ void wn_split8(const f32x4& q0, const f32x4& q1, h8& hi, h8& lo) {
-  const float v[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const _Float16 h = (_Float16)v[e];
-    hi[e] = h;
-    lo[e] = (_Float16)(v[e] - (float)h);
-  }
-}
+using namespace wn_split16;
 
 template <int R32, int D32, int KS>
 struct WnL16 {
@@ -187,15 +169,13 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
           constexpr int tap = ks / (R / 16), kk = ks % (R / 16);
           f32x4 q0 = xq[tap][2 * kk], q1 = xq[tap][2 * kk + 1];
           if (!xvalid[tap]) { q0 = f32x4{0.f, 0.f, 0.f, 0.f}; q1 = q0; }
-          wn_split8(q0, q1, bh, bl);
+          split8(q0, q1, bh, bl);
         }
         if constexpr (blk + 2 < NB) {
           fr[(blk + 2) % 3][0] = wd[((blk + 2) * 2 + 0) * 64];
           fr[(blk + 2) % 3][1] = wd[((blk + 2) * 2 + 1) * 64];
         }
-        u[j] = wn_mfma16(fr[blk % 3][1], bh, u[j]);
-        u[j] = wn_mfma16(fr[blk % 3][0], bl, u[j]);
-        u[j] = wn_mfma16(fr[blk % 3][0], bh, u[j]);
+        mfma3(fr[blk % 3][0], fr[blk % 3][1], bh, bl, u[j]);
         __builtin_amdgcn_sched_barrier(0);
       });
     }
@@ -254,15 +234,13 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
           f32x4 q0, q1;
           q0.x = u[jz][r0 + 0]; q0.y = u[jz][r0 + 1]; q0.z = u[jz][r0 + 2]; q0.w = u[jz][r0 + 3];
           q1.x = u[jz][r0 + 4]; q1.y = u[jz][r0 + 5]; q1.z = u[jz][r0 + 6]; q1.w = u[jz][r0 + 7];
-          wn_split8(q0, q1, bh, bl);
+          split8(q0, q1, bh, bl);
         }
         if constexpr (blk + 2 < NB) {
           fr[(blk + 2) % 3][0] = wr[((blk + 2) * 2 + 0) * 64];
           fr[(blk + 2) % 3][1] = wr[((blk + 2) * 2 + 1) * 64];
         }
-        o[j] = wn_mfma16(fr[blk % 3][1], bh, o[j]);
-        o[j] = wn_mfma16(fr[blk % 3][0], bl, o[j]);
-        o[j] = wn_mfma16(fr[blk % 3][0], bh, o[j]);
+        mfma3(fr[blk % 3][0], fr[blk % 3][1], bh, bl, o[j]);
         __builtin_amdgcn_sched_barrier(0);
       });
     }

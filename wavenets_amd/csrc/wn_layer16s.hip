@@ -15,11 +15,9 @@
 // Measured skeleton (tools/stream_probe.hip: the same DMA / barrier / store structure without the arithmetic): the L2-resident
 // weight stream costs nothing beside the HBM streams (48 B/clk/CU alone, +3 % beside them) and the structure runs at the
 // HBM rate of its activation traffic (5.2 TB/s).
-#include <hip/hip_fp16.h>
+#include "wn_split16.h"
 
-#include "wn_kernels.h"
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+using namespace wn_split16;
 
 #ifdef WN_S128_DIAG
 // phase stamps of the timing build (DIAG & 64): [workgroup][wave][pass 0..1][phase 0..9], read by wn_debug_s128_ts
@@ -27,33 +25,6 @@ __device__ unsigned long long wn_s128_ts[512 * 4 * 2 * 10];
 #endif
 
 namespace {
-
-__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void split8(const f32x4& q0, const f32x4& q1, h8& hi, h8& lo) {
-  const float v[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const _Float16 h = (_Float16)v[e];
-    hi[e] = h;
-    lo[e] = (_Float16)(v[e] - (float)h);
-  }
-}
-
-// LDS-DMA of 16 bytes per lane: global address = scalar base + 32-bit lane offset, LDS address = M0 + lane * 16.
-// Written as inline assembly on purpose: through the builtin hipcc forms every address as a 64-bit VGPR pair, hoists the
-// pairs of all 22 requests of a tile out of the tile loop, spills them, and reloads each one with s_waitcnt vmcnt(0) in front
-// of its request -- which drains the pipeline this kernel is built around.  (The compiler does not count these requests
-// in its own vmcnt bookkeeping: its waits for its own loads only become more conservative.)
-__device__ __forceinline__ void dma16(const void* sbase, unsigned voff, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(lds_addr) : "memory");   // (m0 is reserved: the compiler never keeps a value in it)
-}
-__device__ __forceinline__ unsigned lds_addr_of(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)p;
-}
 
 template <int KS>
 struct G {
@@ -71,38 +42,6 @@ struct G {
   static constexpr int PX = 2;                         // activation-DMA instructions per lane and k-step
   static_assert(STAGE <= REGION, "the output stage lives in the activation ring");
 };
-
-// one 32 x 32 D-layout accumulator tile -> wave-private LDS stage -> 128-byte row segments in HBM.
-// dst = wave-uniform address of the tile's first row (+ column offset), voff = this lane's byte offset inside a group of
-// eight rows: the stores are scalar base + 32-bit lane offset.  The base goes through an empty asm so that it stays ONE
-// scalar: otherwise hipcc re-associates (tensor + lane offset) + row, hoists that 64-bit VGPR pair of every output tensor
-// out of the tile loop, spills it, and reloads it with s_waitcnt vmcnt(0) in the middle of the stores.
-// FULL: all 32 rows exist (no per-row predicate, no branches).
-template <int PITCH, bool FULL, bool NOSTORE = false, bool ADD = false>
-__device__ __forceinline__ void store_tile(const f32x16& v, float* stage, float* dst, unsigned voff, unsigned ld_bytes,
-                                           int rows_valid, int lane, const f32x4* add = nullptr) {
-  const int tl = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int rq = 0; rq < 4; ++rq) {
-    f32x4 o;
-    o.x = v[4 * rq + 0]; o.y = v[4 * rq + 1]; o.z = v[4 * rq + 2]; o.w = v[4 * rq + 3];
-    *reinterpret_cast<f32x4*>(stage + tl * PITCH + 8 * rq + 4 * h) = o;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  const float* rd = stage + (lane >> 3) * PITCH + (lane & 7) * 4;
-  char* base0 = reinterpret_cast<char*>(dst);
-  asm volatile("" : "+s"(base0));
-  // (the asm drops the address space: restore it, or the stores become flat_store)
-  __attribute__((address_space(1))) char* base = (__attribute__((address_space(1))) char*)base0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f32x4 o = *reinterpret_cast<const f32x4*>(rd + i * 8 * PITCH);
-    if constexpr (ADD) { o.x += add[i].x; o.y += add[i].y; o.z += add[i].z; o.w += add[i].w; }
-    if (NOSTORE ? (o.x == 1.2345e-30f) : (FULL || i * 8 + (lane >> 3) < rows_valid))      // (NOSTORE: timing ablation)
-      *(__attribute__((address_space(1))) f32x4*)(base + (uint64_t)((unsigned)(i * 8) * ld_bytes) + voff) = o;
-  }
-  asm volatile("" ::: "memory");
-}
 
 }  // namespace
 
@@ -250,9 +189,7 @@ __global__ __launch_bounds__(256, 2) void wn_layer_fwd_s128_kernel(WnLayerFwdArg
           fr[(j + 1) & 1][1] = wl[((j + 1) * 2 + 1) * 64];
         }
         if constexpr (!(DIAG & 4)) {
-          u[j] = mfma16(fr[j & 1][1], bh, u[j]);
-          u[j] = mfma16(fr[j & 1][0], bl, u[j]);
-          u[j] = mfma16(fr[j & 1][0], bh, u[j]);
+          mfma3(fr[j & 1][0], fr[j & 1][1], bh, bl, u[j]);
         } else {
           u[j][0] += (float)fr[j & 1][1][0] * (float)bh[0] + (float)fr[j & 1][0][1] * (float)bl[1];
         }
@@ -360,9 +297,7 @@ __global__ __launch_bounds__(256, 2) void wn_layer_fwd_s128_kernel(WnLayerFwdArg
             fr[(blk + 1) & 1][1] = wl[((blk + 1) * 2 + 1) * 64];
           }
           if constexpr (!(DIAG & 4)) {
-            o[j] = mfma16(fr[blk & 1][1], bh, o[j]);
-            o[j] = mfma16(fr[blk & 1][0], bl, o[j]);
-            o[j] = mfma16(fr[blk & 1][0], bh, o[j]);
+            mfma3(fr[blk & 1][0], fr[blk & 1][1], bh, bl, o[j]);
           } else {
             o[j][0] += (float)fr[blk & 1][1][0] * (float)bh[0] + (float)fr[blk & 1][0][1] * (float)bl[1];
           }

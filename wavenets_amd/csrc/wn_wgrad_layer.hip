@@ -14,29 +14,9 @@
 // conflict-free 16-byte LDS reads shared by all waves.  Every fp32 product is the usual 3-product
 // split on v_mfma_f32_32x32x16_f16 with fp32 accumulation; gradient operands are pre-scaled by an
 // exact power of two from their running max-abs (see wn_gemm16.hip).
-#include <hip/hip_fp16.h>
+#include "wn_split16.h"
 
-#include "wn_kernels.h"
-
-typedef _Float16 wl_h8 __attribute__((ext_vector_type(8)));
-
-namespace {
-
-__device__ __forceinline__ void wl_scale_from_max(const float* slot, float& sc, float& inv) {
-  sc = 1.0f;
-  inv = 1.0f;
-  if (!slot) return;
-  const float m = *slot;
-  if (m > 0.f && m < 3.0e38f) {
-    int e;
-    (void)frexpf(m, &e);
-    e = max(-100, min(100, e));
-    sc = ldexpf(1.0f, -e);
-    inv = ldexpf(1.0f, e);
-  }
-}
-
-}  // namespace
+using namespace wn_split16;
 
 // C32 = R / 32 = D / 32 (1 or 2).  Channel order of a stage: x[t-d] (R) | x[t] (R) | du (2D) | z (D) | go (R);
 // INNER: x[t-d] (R) | x[t] (R) | du (R)
@@ -63,9 +43,11 @@ __global__ __launch_bounds__(256, 2) void wn_wgrad_layer_kernel(const WnWgLayer*
   const int r0 = sp * len, r1 = min(T, r0 + len);
   const int d = Ld.dilation;
 
-  float su, inv_u, sh, inv_h;
-  wl_scale_from_max(Ld.gmax_u_off >= 0 ? ws + Ld.gmax_u_off : nullptr, su, inv_u);
-  wl_scale_from_max(Ld.gmax_h_off >= 0 ? ws + Ld.gmax_h_off : nullptr, sh, inv_h);
+  const float* const gmax_u = Ld.gmax_u_off >= 0 ? ws + Ld.gmax_u_off : nullptr;
+  const float* const gmax_h = Ld.gmax_h_off >= 0 ? ws + Ld.gmax_h_off : nullptr;
+  float su = 1.0f, inv_u = 1.0f, sh = 1.0f, inv_h = 1.0f;
+  if (gmax_u) pow2_scale(*gmax_u, su, inv_u);
+  if (gmax_h) pow2_scale(*gmax_h, sh, inv_h);
 
   // ---- this thread's units: (channel, half of the chunk).  Unit 0 is a du channel (row stride 2R);
   //      units 1.. are channels of x[t-d] | x[t] | z | go (row stride R: the plan guarantees ldz == R),
@@ -135,18 +117,14 @@ __global__ __launch_bounds__(256, 2) void wn_wgrad_layer_kernel(const WnWgLayer*
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
       if (!uvalid[i]) continue;
-      wl_h8 hi, lo;
+      h8 hi, lo;
       float s8 = 0.f;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const _Float16 hh = (_Float16)(v[i][e] * uscale[i]);
-        hi[e] = hh;
-        lo[e] = (_Float16)__builtin_fmaf(v[i][e], uscale[i], -(float)hh);
-        s8 += v[i][e];
-      }
+      for (int e = 0; e < 8; ++e) s8 += v[i][e];
+      split8s(v[i], uscale[i], hi, lo);
       if (ugrad[i]) bsum[i] += s8;
-      *reinterpret_cast<wl_h8*>(st + uch[i] * 32 + uhh[i] * 16) = hi;
-      *reinterpret_cast<wl_h8*>(st + PLANE + uch[i] * 32 + uhh[i] * 16) = lo;
+      *reinterpret_cast<h8*>(st + uch[i] * 32 + uhh[i] * 16) = hi;
+      *reinterpret_cast<h8*>(st + PLANE + uch[i] * 32 + uhh[i] * 16) = lo;
     }
   };
 
@@ -166,28 +144,24 @@ __global__ __launch_bounds__(256, 2) void wn_wgrad_layer_kernel(const WnWgLayer*
 
   auto compute = [&](int stage) {
     const unsigned char* st = smem + stage * STAGE + tl * 32 + h * 16;
-    auto frag = [&](int cb, wl_h8& hi, wl_h8& lo) {
-      hi = *reinterpret_cast<const wl_h8*>(st + cb * 32);
-      lo = *reinterpret_cast<const wl_h8*>(st + PLANE + cb * 32);
+    auto frag = [&](int cb, h8& hi, h8& lo) {
+      hi = *reinterpret_cast<const h8*>(st + cb * 32);
+      lo = *reinterpret_cast<const h8*>(st + PLANE + cb * 32);
     };
-    wl_h8 ah, al;
+    h8 ah, al;
     if (has_d) frag(32 * xt, ah, al);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       if (!has_d) break;
-      wl_h8 bh, bl;
+      h8 bh, bl;
       frag(2 * R + 32 * (j0 + j), bh, bl);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[j], 0, 0, 0);
+      mfma3(ah, al, bh, bl, acc[j]);
     }
     if (has_r) {
-      wl_h8 zh, zl, gh, gl;
+      h8 zh, zl, gh, gl;
       frag(4 * R + 32 * zt, zh, zl);
       frag(5 * R + 32 * gt, gh, gl);
-      accr = __builtin_amdgcn_mfma_f32_32x32x16_f16(zl, gh, accr, 0, 0, 0);
-      accr = __builtin_amdgcn_mfma_f32_32x32x16_f16(zh, gl, accr, 0, 0, 0);
-      accr = __builtin_amdgcn_mfma_f32_32x32x16_f16(zh, gh, accr, 0, 0, 0);
+      mfma3(zh, zl, gh, gl, accr);
     }
   };
 

@@ -13,11 +13,9 @@
 // ~5000 workgroups per step -- and (round 2) for head layers of widths 128 / 256 on their own time split: one
 // workgroup per (layer, utterance, 1/32 of the utterance) = 256 workgroups per layer computing the WHOLE K x N
 // product of their rows, so every operand row is read exactly once.
-#include <hip/hip_fp16.h>
+#include "wn_split16.h"
 
-#include "wn_kernels.h"
-
-typedef _Float16 wp_h8 __attribute__((ext_vector_type(8)));
+using namespace wn_split16;
 
 // TK_ = row tiles per wave.
 template <int LDX, int LDG, int KT, int NT, int LDW = 32 * NT, int TK_ = 2>
@@ -41,16 +39,7 @@ __global__ __launch_bounds__(64 * (KT / TK_) * (NT / 2)) void wn_wgrad_pair_kern
   const int shift = J.shift;
 
   float gsc = 1.0f, inv = 1.0f;
-  if (J.gmax_off >= 0) {
-    const float m = ws[J.gmax_off];
-    if (m > 0.f && m < 3.0e38f) {
-      int e;
-      (void)frexpf(m, &e);
-      e = max(-100, min(100, e));
-      gsc = ldexpf(1.0f, -e);
-      inv = ldexpf(1.0f, e);
-    }
-  }
+  if (J.gmax_off >= 0) pow2_scale(ws[J.gmax_off], gsc, inv);
 
   // ---- this thread's two units: one X channel and one G channel, each for one half of the chunk ----
   const bool xunit = tid < 2 * KC, gunit = tid < 2 * NC;
@@ -82,29 +71,20 @@ __global__ __launch_bounds__(64 * (KT / TK_) * (NT / 2)) void wn_wgrad_pair_kern
   auto store_chunk = [&](int stage, const float (&xv)[8], const float (&gv)[8]) {
     unsigned char* st = smem + stage * STAGE;
     if (xunit) {
-      wp_h8 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const _Float16 hh = (_Float16)xv[e];
-        hi[e] = hh;
-        lo[e] = (_Float16)(xv[e] - (float)hh);
-      }
-      *reinterpret_cast<wp_h8*>(st + cx * 32 + hx * 16) = hi;
-      *reinterpret_cast<wp_h8*>(st + PLANE + cx * 32 + hx * 16) = lo;
+      h8 hi, lo;
+      split8(xv, hi, lo);
+      *reinterpret_cast<h8*>(st + cx * 32 + hx * 16) = hi;
+      *reinterpret_cast<h8*>(st + PLANE + cx * 32 + hx * 16) = lo;
     }
     if (gunit) {
-      wp_h8 hi, lo;
+      h8 hi, lo;
       float s8 = 0.f;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const _Float16 hh = (_Float16)(gv[e] * gsc);
-        hi[e] = hh;
-        lo[e] = (_Float16)__builtin_fmaf(gv[e], gsc, -(float)hh);
-        s8 += gv[e];
-      }
+      for (int e = 0; e < 8; ++e) s8 += gv[e];
+      split8s(gv, gsc, hi, lo);
       bsum += s8;
-      *reinterpret_cast<wp_h8*>(st + (KC + cg) * 32 + hg * 16) = hi;
-      *reinterpret_cast<wp_h8*>(st + PLANE + (KC + cg) * 32 + hg * 16) = lo;
+      *reinterpret_cast<h8*>(st + (KC + cg) * 32 + hg * 16) = hi;
+      *reinterpret_cast<h8*>(st + PLANE + (KC + cg) * 32 + hg * 16) = lo;
     }
   };
 
@@ -120,41 +100,37 @@ __global__ __launch_bounds__(64 * (KT / TK_) * (NT / 2)) void wn_wgrad_pair_kern
   auto compute = [&](int stage) {
     const unsigned char* st = smem + stage * STAGE + tl * 32 + h * 16;
     if constexpr (TK <= 2) {
-      wp_h8 ah[TK], al[TK];
+      h8 ah[TK], al[TK];
 #pragma unroll
       for (int i = 0; i < TK; ++i) {
-        ah[i] = *reinterpret_cast<const wp_h8*>(st + (32 * (wk * TK + i)) * 32);
-        al[i] = *reinterpret_cast<const wp_h8*>(st + PLANE + (32 * (wk * TK + i)) * 32);
+        ah[i] = *reinterpret_cast<const h8*>(st + (32 * (wk * TK + i)) * 32);
+        al[i] = *reinterpret_cast<const h8*>(st + PLANE + (32 * (wk * TK + i)) * 32);
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        const wp_h8 bh = *reinterpret_cast<const wp_h8*>(st + (KC + 32 * (wn * TN + j)) * 32);
-        const wp_h8 bl = *reinterpret_cast<const wp_h8*>(st + PLANE + (KC + 32 * (wn * TN + j)) * 32);
+        const h8 bh = *reinterpret_cast<const h8*>(st + (KC + 32 * (wn * TN + j)) * 32);
+        const h8 bl = *reinterpret_cast<const h8*>(st + PLANE + (KC + 32 * (wn * TN + j)) * 32);
 #pragma unroll
         for (int i = 0; i < TK; ++i) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);
+          mfma3(ah[i], al[i], bh, bl, acc[i][j]);
         }
       }
     } else {
       // more row tiles per wave: the G fragments stay, the X fragments are fetched per row tile (register pressure:
       // 16 * TK * TN accumulators; same products in the same order per output element)
-      wp_h8 bh[TN], bl[TN];
+      h8 bh[TN], bl[TN];
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        bh[j] = *reinterpret_cast<const wp_h8*>(st + (KC + 32 * (wn * TN + j)) * 32);
-        bl[j] = *reinterpret_cast<const wp_h8*>(st + PLANE + (KC + 32 * (wn * TN + j)) * 32);
+        bh[j] = *reinterpret_cast<const h8*>(st + (KC + 32 * (wn * TN + j)) * 32);
+        bl[j] = *reinterpret_cast<const h8*>(st + PLANE + (KC + 32 * (wn * TN + j)) * 32);
       }
 #pragma unroll
       for (int i = 0; i < TK; ++i) {
-        const wp_h8 ah = *reinterpret_cast<const wp_h8*>(st + (32 * (wk * TK + i)) * 32);
-        const wp_h8 al = *reinterpret_cast<const wp_h8*>(st + PLANE + (32 * (wk * TK + i)) * 32);
+        const h8 ah = *reinterpret_cast<const h8*>(st + (32 * (wk * TK + i)) * 32);
+        const h8 al = *reinterpret_cast<const h8*>(st + PLANE + (32 * (wk * TK + i)) * 32);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[j], acc[i][j], 0, 0, 0);
+          mfma3(ah, al, bh[j], bl[j], acc[i][j]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }

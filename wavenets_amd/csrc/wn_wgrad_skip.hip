@@ -9,11 +9,9 @@
 // workgroup instead of once per job.  Split-precision MFMA (fp16 hi/lo, 3 products), time is the
 // MFMA K dimension (16 rows per step).  Partial sums go to the [split][nparams] slab of the batched
 // weight-gradient path and are reduced with it.
-#include <hip/hip_fp16.h>
+#include "wn_split16.h"
 
-#include "wn_kernels.h"
-
-typedef _Float16 ws_h8 __attribute__((ext_vector_type(8)));
+using namespace wn_split16;
 
 struct WnWgSkipArgs {
   const float* z; int32_t ldz;          // block-major [N][rows][D]: ldz = D, plane stride = rows * D
@@ -49,16 +47,7 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_skip_kernel(WnWgSkipArgs a) {
   const int64_t r1 = min(a.rows, r0 + len);
 
   float gsc = 1.0f, inv = 1.0f;
-  if (a.gmax) {
-    const float m = *a.gmax;
-    if (m > 0.f && m < 3.0e38f) {
-      int e;
-      (void)frexpf(m, &e);
-      e = max(-100, min(100, e));
-      gsc = ldexpf(1.0f, -e);
-      inv = ldexpf(1.0f, e);
-    }
-  }
+  if (a.gmax) pow2_scale(*a.gmax, gsc, inv);
 
   f32x16 acc[NT];
 #pragma unroll
@@ -101,36 +90,26 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_skip_kernel(WnWgSkipArgs a) {
       }
     }
   };
-  auto split8 = [&](const float (&v)[8], float s, ws_h8& hi, ws_h8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const _Float16 hh = (_Float16)(v[e] * s);
-      hi[e] = hh;
-      lo[e] = (_Float16)__builtin_fmaf(v[e], s, -(float)hh);     // product unrounded (explicit fma)
-    }
-  };
 
   int buf = 0;
   auto compute = [&](const float (&zv)[8], const float (&gv)[8]) {
-    ws_h8 zh, zl, gh, gl;
-    split8(zv, 1.0f, zh, zl);
+    h8 zh, zl, gh, gl;
+    split8s(zv, 1.0f, zh, zl);
     if (makes_g) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) bsum += gv[e];
-      split8(gv, gsc, gh, gl);
-      ws_h8* dst = reinterpret_cast<ws_h8*>(smem + buf * (8 * 2048) + wave * 2048);
+      split8s(gv, gsc, gh, gl);
+      h8* dst = reinterpret_cast<h8*>(smem + buf * (8 * 2048) + wave * 2048);
       dst[lane] = gh;
       dst[64 + lane] = gl;
     }
     __syncthreads();
-    const ws_h8* src = reinterpret_cast<const ws_h8*>(smem + buf * (8 * 2048));
+    const h8* src = reinterpret_cast<const h8*>(smem + buf * (8 * 2048));
     if (wave_has_k) {
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-        const ws_h8 bh = src[j * 128 + lane], bl = src[j * 128 + 64 + lane];
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(zl, bh, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(zh, bl, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(zh, bh, acc[j], 0, 0, 0);
+        const h8 bh = src[j * 128 + lane], bl = src[j * 128 + 64 + lane];
+        mfma3(zh, zl, bh, bl, acc[j]);
       }
     }
     buf ^= 1;

@@ -17,39 +17,25 @@
 // stage and re-requested at once) while this chunk's 48 products per wave run -- a request then has two product phases
 // (~1.5 us) to land instead of one: with one chunk in flight the kernel waited on every chunk (3.5-4.0 TB/s).
 // Wave w owns output row tiles {2 (w & 3), +1} x column tiles {4 (w >> 2) .. +3}: 8 accumulator tiles.
-#include <hip/hip_fp16.h>
+#include "wn_split16.h"
 
-#include "wn_kernels.h"
+using namespace wn_split16;
 
-typedef _Float16 wt_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 wt_h4 __attribute__((ext_vector_type(4)));
 typedef short wt_s4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
 constexpr int WT_ROWS = 32;                                            // time steps per chunk
 
-__device__ __forceinline__ f32x4 wt_ldg4(const float* p) { return *(const __attribute__((address_space(1))) f32x4*)(p); }
-
 // 8 consecutive time steps (rows 16 ks + 8 h .. + 7) of channel chbase + (lane & 31): two transposed reads of 4
 template <int PITCH>
-__device__ __forceinline__ wt_h8 wt_frag(const unsigned char* lanebase, int off) {
+__device__ __forceinline__ h8 wt_frag(const unsigned char* lanebase, int off) {
   const wt_s4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wt_s4*)(lanebase + off));
   const wt_s4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wt_s4*)(lanebase + off + 4 * PITCH));
-  wt_h8 r;
-  const wt_h4 ha = *reinterpret_cast<const wt_h4*>(&a), hb = *reinterpret_cast<const wt_h4*>(&b);
+  h8 r;
+  const h4 ha = *reinterpret_cast<const h4*>(&a), hb = *reinterpret_cast<const h4*>(&b);
   r[0] = ha[0]; r[1] = ha[1]; r[2] = ha[2]; r[3] = ha[3]; r[4] = hb[0]; r[5] = hb[1]; r[6] = hb[2]; r[7] = hb[3];
   return r;
-}
-
-__device__ __forceinline__ void wt_split4(const f32x4& v, float s, wt_h4& hi, wt_h4& lo) {
-  const float f[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const _Float16 hh = (_Float16)(f[e] * s);
-    hi[e] = hh;
-    lo[e] = (_Float16)__builtin_fmaf(f[e], s, -(float)hh);
-  }
 }
 
 }  // namespace
@@ -88,22 +74,9 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
   const int r0 = sp * len, r1 = min(T, r0 + len);
   const int d = J.shift;
 
-  auto pow2 = [&](int64_t off, float& sc, float& iv) {
-    sc = 1.0f; iv = 1.0f;
-    if (off >= 0) {
-      const float m = ws[off];
-      if (m > 0.f && m < 3.0e38f) {
-        int e;
-        (void)frexpf(m, &e);
-        e = max(-100, min(100, e));
-        sc = ldexpf(1.0f, -e);
-        iv = ldexpf(1.0f, e);
-      }
-    }
-  };
-  float gsc, inv, gsc2 = 1.0f, inv2 = 1.0f;
-  pow2(J.gmax_off, gsc, inv);
-  if constexpr (G2) pow2(J.gmax2_off, gsc2, inv2);
+  float gsc = 1.0f, inv = 1.0f, gsc2 = 1.0f, inv2 = 1.0f;
+  if (J.gmax_off >= 0) pow2_scale(ws[J.gmax_off], gsc, inv);
+  if constexpr (G2) if (J.gmax2_off >= 0) pow2_scale(ws[J.gmax2_off], gsc2, inv2);
 
   // ---- this thread's pieces of a chunk: rows xr + XRP k of every x tap (4 channels at xc), rows gr + GRP k of g (4 at gc) ----
   const int xr = tid / XPR, xc = (tid % XPR) * 4;
@@ -131,16 +104,16 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
       const int t = t0 + xr + XRP * k;
       const int tc = min(t, T - 1);
       if (XSEG > 0) {
-        xs[0][k] = wt_ldg4(xbase + (int64_t)tc * LDX);
+        xs[0][k] = ldg4(xbase + (int64_t)tc * LDX);
       } else {
-        xs[0][k] = wt_ldg4(xbase + (int64_t)max(tc - d, 0) * LDX);
-        if constexpr (TAPS == 2) xs[1][k] = wt_ldg4(xbase + (int64_t)tc * LDX);
+        xs[0][k] = ldg4(xbase + (int64_t)max(tc - d, 0) * LDX);
+        if constexpr (TAPS == 2) xs[1][k] = ldg4(xbase + (int64_t)tc * LDX);
       }
     }
 #pragma unroll
     for (int k = 0; k < GP; ++k) {
       const int t = min(t0 + gr + GRP * k, T - 1);
-      gv[k] = wt_ldg4(gbase + (int64_t)t * LDG);
+      gv[k] = ldg4(gbase + (int64_t)t * LDG);
     }
   };
   auto store = [&](int stage, const Regs& q, int t0) {
@@ -154,24 +127,24 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
       const int t = t0 + xr + XRP * k;
 #pragma unroll
       for (int tp = 0; tp < TAPS; ++tp) {
-        wt_h4 hi, lo;
+        h4 hi, lo;
         // (the first plane is the SHIFTED tap x[t - d] unless the rows are segments of an unshifted tensor)
         const bool ok = interior || (t < r1 && (XSEG > 0 || (TAPS == 2 && tp == TAPS - 1) || t - d >= 0));
         const f32x4 xv = (ok && xvalid) ? xs[tp][k] : zero4;
-        wt_split4(xv, 1.0f, hi, lo);
-        *reinterpret_cast<wt_h4*>(row + (tp * KC + xc) * 2) = hi;
-        *reinterpret_cast<wt_h4*>(row + PLANE + (tp * KC + xc) * 2) = lo;
+        split4s(xv, 1.0f, hi, lo);
+        *reinterpret_cast<h4*>(row + (tp * KC + xc) * 2) = hi;
+        *reinterpret_cast<h4*>(row + PLANE + (tp * KC + xc) * 2) = lo;
       }
     }
 #pragma unroll
     for (int k = 0; k < GP; ++k) {
-      wt_h4 hi, lo;
+      h4 hi, lo;
       unsigned char* row = st + (gr + GRP * k) * PITCH;
       const f32x4 g4 = (interior || t0 + gr + GRP * k < r1) ? gv[k] : zero4;
-      wt_split4(g4, gs_t, hi, lo);
+      split4s(g4, gs_t, hi, lo);
       bsum[0] += g4.x; bsum[1] += g4.y; bsum[2] += g4.z; bsum[3] += g4.w;
-      *reinterpret_cast<wt_h4*>(row + (XC + gc) * 2) = hi;
-      *reinterpret_cast<wt_h4*>(row + PLANE + (XC + gc) * 2) = lo;
+      *reinterpret_cast<h4*>(row + (XC + gc) * 2) = hi;
+      *reinterpret_cast<h4*>(row + PLANE + (XC + gc) * 2) = lo;
     }
   };
 
@@ -192,7 +165,7 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
     wn_static_for<2>([&](auto kc) {
       constexpr int ks = decltype(kc)::value;
       constexpr int ro = ks * 16 * PITCH;
-      wt_h8 ah[TKW], al[TKW];
+      h8 ah[TKW], al[TKW];
 #pragma unroll
       for (int i = 0; i < TKW; ++i) {
         ah[i] = wt_frag<PITCH>(base, ro + 32 * (kt0 + i) * 2);
@@ -200,13 +173,11 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
       }
 #pragma unroll
       for (int j = 0; j < TNW; ++j) {
-        const wt_h8 bh = wt_frag<PITCH>(base, ro + (XC + 32 * (nt0 + j)) * 2);
-        const wt_h8 bl = wt_frag<PITCH>(base, ro + PLANE + (XC + 32 * (nt0 + j)) * 2);
+        const h8 bh = wt_frag<PITCH>(base, ro + (XC + 32 * (nt0 + j)) * 2);
+        const h8 bl = wt_frag<PITCH>(base, ro + PLANE + (XC + 32 * (nt0 + j)) * 2);
 #pragma unroll
         for (int i = 0; i < TKW; ++i) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);
+          mfma3(ah[i], al[i], bh, bl, acc[i][j]);
         }
       }
     });
