@@ -210,6 +210,26 @@ float wn_range_limit(void);
 int wn_generate(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                 int32_t length, int32_t deterministic, int32_t queued, uint64_t seed, float* out,
                 float* workspace, int64_t ws_floats, void* stream);
+/* ---- sampling controls of the stochastic draw (generation and sample_waveform) ----
+ * temperature T: finite and > 0 with a finite 1 / T (no denormal), else WN_E_INVALID.
+ *   categorical head: the draw is from p_T(j) ~ p(j)^(1/T), i.e. softmax(logits / T), evaluated max-normalised as
+ *   (p / p_max)^(1/T) -- the largest term is exactly 1, so no T underflows the total.
+ *   mixture heads, row [w | mu | s]: a draw at temperature T is a draw at temperature 1 from [w / T | mu | s + ln T]
+ *   (component pick sharpened, component scale times T, clip to [-1, 1] unchanged).
+ * top_k: 0 = off; < 0 is WN_E_INVALID; categorical head only (non-zero with a mixture head is WN_E_INVALID).
+ *   top_k >= classes is off (the unmodified path, bit for bit).  Otherwise the classes are ranked by (probability
+ *   descending, class index ascending), the first top_k kept and renormalised.  With that tie rule top_k = 1 is the
+ *   deterministic arg max ("first maximum wins").  The kept set does not depend on T.  Offered for up to 1024 classes
+ *   (WN_E_UNSUPPORTED beyond).
+ * seed: the Philox key of the draws.
+ * A deterministic draw ignores temperature and top_k (arg max and mode do not depend on them); they are still checked.
+ * {1.0f, 0, seed} is the draw of the entry points without controls, bit for bit.  The three fields are checked before
+ * any other argument is looked at and before anything touches the device. */
+typedef struct wn_sampling { float temperature; int32_t top_k; uint64_t seed; } wn_sampling;
+/* wn_generate with the sampling controls in place of the seed; wn_generate is its {1.0f, 0, seed} case */
+int wn_generate_sampled(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                        int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling, float* out,
+                        float* workspace, int64_t ws_floats, void* stream);
 int64_t wn_generate_workspace_floats(const wn_plan* p, int32_t B, int32_t queued);
 /* float offset, inside the caller's generation workspace, of the call's range-guard slot.  After wn_generate (stream
  * synchronised) the float is >= wn_range_limit() if and only if some split-precision kernel of the call was fed an
@@ -275,6 +295,10 @@ int wn_sum_squared_error(const float* a, const float* b, int64_t n, float scale,
 int wn_sample_waveform(int32_t head, const float* pred, int64_t rows, int32_t C,
                        int32_t num_mixtures, int32_t bits, int32_t deterministic, uint64_t seed,
                        uint64_t offset, float* out, void* stream);
+/* ... with the sampling controls in place of the seed (categorical: pred holds probabilities, C classes) */
+int wn_sample_waveform_sampled(int32_t head, const float* pred, int64_t rows, int32_t C,
+                               int32_t num_mixtures, int32_t bits, int32_t deterministic, const wn_sampling* sampling,
+                               uint64_t offset, float* out, void* stream);
 
 #ifdef __cplusplus
 }

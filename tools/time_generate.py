@@ -1,7 +1,14 @@
 """Generation speed (the reference prints 'Speed of generation was ... samples/s', train.py:253-261):
-naive sliding window vs queued ring buffers on BASELINE configs[1] weights, batch B."""
+naive sliding window vs queued ring buffers on BASELINE configs[1] weights, batch B.
+--temperature T / --top-k K anywhere on the command line: the sampling controls of the stochastic leg."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+controls = {}
+for flag, key, conv in (('--temperature', 'temperature', float), ('--top-k', 'top_k', int)):
+  if flag in sys.argv:
+    i = sys.argv.index(flag)
+    controls[key] = conv(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 import torch
 from wavenets_amd import WaveNet
 import bench
@@ -16,11 +23,15 @@ from wavenets_amd import _lib
 for k_, v_ in zip(sys.argv[3::2], sys.argv[4::2]):
   _lib.lib().wn_debug_set(int(k_), int(v_))
 w = (torch.rand(B, m.receptive_field, 1, generator=torch.Generator().manual_seed(0)) * 2 - 1).to(dev)
-for name, queued, n, det in (('naive', False, 20, True), ('queued', True, 400, True), ('queued, stochastic draws', True, 400, False)):
-  m.generate(3, sample=w, use_queues=queued, deterministic=det)
+legs = [('naive', False, 20, True), ('queued', True, 400, True), ('queued, stochastic draws', True, 400, False)]
+if controls:
+  legs = [(f'queued, stochastic draws, {controls}', True, 400, False)]
+for name, queued, n, det in legs:
+  kw_ = {} if det else controls
+  m.generate(3, sample=w, use_queues=queued, deterministic=det, **kw_)
   torch.cuda.synchronize()
   t0 = time.perf_counter()
-  out = m.generate(n, sample=w, use_queues=queued, deterministic=det)
+  out = m.generate(n, sample=w, use_queues=queued, deterministic=det, **kw_)
   torch.cuda.synchronize()
   dt = time.perf_counter() - t0
   print(f'{name}: B={B} {n} samples/utterance in {dt:.3f} s -> {n / dt:.1f} samples/s per utterance, '

@@ -32,6 +32,7 @@ config = {                       # defaults of the reference, train.py:22-50
     # additions of this driver
     'steps_per_epoch': 0, 'synthetic_utterances': 256, 'sample_rate': 16000, 'results_dir': './results',
     'preview_length': 0, 'condition_classes': 2, 'labels': None,
+    'preview_temperature': 1.0, 'preview_top_k': 0, 'preview_seed': None,   # WaveNet.generate's sampling controls
     'checkpoint_format': 'npz',    # 'h5': Keras .weights.h5 exchange files (weights only, as the reference writes them)
 }
 
@@ -168,7 +169,9 @@ def main():
     tic = time.time()
     nprev = min(config['batch_size'], 8)
     samples = model.generate(preview, batch_size=nprev, condition=cond[:nprev] if conditioned else None,
-                             use_queues=config['layers_per_block'] == 1)
+                             use_queues=config['layers_per_block'] == 1,
+                             temperature=float(config['preview_temperature']), top_k=int(config['preview_top_k']),
+                             seed=None if config['preview_seed'] is None else int(config['preview_seed']))
     torch.cuda.synchronize()
     tictoc = time.time() - tic
     print(f'Generation took {tictoc}s')

@@ -20,6 +20,7 @@ ACTIVATIONS = {None: 0, 'linear': 0, 'relu': 1, 'leaky_relu': 2, 'tanh': 3, 'sig
 HEADS = {'categorical': 0, 'logistic': 1, 'gaussian': 2}
 WN_MAX_FINAL = 8
 WN_MAX_MAPPING = 8
+WN_TOP_K_MAX_CLASSES = 1024   # top_k is offered for up to this many classes (WN_SAMPLE_FUSED_MAXC)
 
 
 class WnConfig(C.Structure):
@@ -34,6 +35,11 @@ class WnConfig(C.Structure):
       ('mapping_channels', C.c_int32 * WN_MAX_MAPPING), ('mapping_activation', C.c_int32),
       ('l2_reg_factor', C.c_float),
   ]
+
+
+class WnSampling(C.Structure):
+  """struct wn_sampling (include/wn_hip.h): temperature, top-k and Philox key of a stochastic draw."""
+  _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('seed', C.c_uint64)]
 
 
 class WnLayerDesc(C.Structure):
@@ -99,6 +105,8 @@ _SIGS = {
     'wn_range_limit': (C.c_float, []),
     'wn_generate': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _P,
                               _P, C.c_int64, _P]),
+    'wn_generate_sampled': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(WnSampling), _P,
+                                      _P, C.c_int64, _P]),
     'wn_generate_workspace_floats': (C.c_int64, [_P, C.c_int32, C.c_int32]),
     'wn_generate_guard_slot': (C.c_int64, [_P, C.c_int32, C.c_int32]),
     'wn_layer_saved_floats': (C.c_int64, [C.POINTER(WnLayerDesc), C.c_int32, C.c_int32]),
@@ -117,6 +125,8 @@ _SIGS = {
     'wn_sum_squared_error': (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P, _P]),
     'wn_sample_waveform': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_uint64, C.c_uint64, _P, _P]),
+    'wn_sample_waveform_sampled': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.POINTER(WnSampling), C.c_uint64, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -108,7 +108,7 @@ class SoundCallback:
   side by side (the reference's A/B hook for its queue TODO)."""
 
   def __init__(self, log_dir, sampling_frequency: int, samples: int, apply_mulaw: bool, epoch_frequency: int = 1,
-               condition=None, use_fast=False, initial_sample=None, model=None):
+               condition=None, use_fast=False, initial_sample=None, model=None, temperature=1.0, top_k=0, seed=None):
     if use_fast not in ['both', True, False]:
       raise ValueError('use_fast must be one of True, False, "both"')
     if epoch_frequency < 1:
@@ -122,6 +122,8 @@ class SoundCallback:
     self.initial_sample = initial_sample
     self.use_fast = use_fast
     self.model = model
+    # sampling controls of the generate calls (additions; WaveNet.generate)
+    self.temperature, self.top_k, self.seed = temperature, top_k, seed
 
   def set_model(self, model):
     self.model = model
@@ -134,8 +136,10 @@ class SoundCallback:
       return None
     modes = [('fast', True), ('standard', False)] if self.use_fast == 'both' else [('standard', self.use_fast)]
     generated = {}
+    controls = dict(temperature=self.temperature, top_k=self.top_k, seed=self.seed)
     for key, queued in modes:
-      generated[key] = self.model.generate(self.samples, batch_size=5, condition=self.condition, use_queues=queued)
+      generated[key] = self.model.generate(self.samples, batch_size=5, condition=self.condition, use_queues=queued,
+                                            **controls)
     if self.initial_sample is not None:
       if self.condition is not None:
         wave_, cond = self.initial_sample
@@ -145,7 +149,7 @@ class SoundCallback:
       for key, queued in modes:
         name = 'with_initial' + ('_fast' if (key == 'fast') else '')
         generated[name] = self.model.generate(self.samples, batch_size=5, condition=cond, sample=wave_,
-                                              use_queues=queued)
+                                              use_queues=queued, **controls)
     out_dir = os.path.join(self.log_dir, f'epoch_{epoch:04d}')
     os.makedirs(out_dir, exist_ok=True)
     for key, batch in generated.items():

@@ -39,9 +39,18 @@ extern "C" int wn_plan_arm_step_sample(wn_plan* p, float* sample_out, int32_t de
 extern "C" int wn_sample_waveform(int32_t head, const float* pred, int64_t rows, int32_t C, int32_t num_mixtures,
                                   int32_t bits, int32_t deterministic, uint64_t seed, uint64_t offset, float* out,
                                   void* stream) {
+  const wn_sampling sp = {1.0f, 0, seed};
+  return wn_sample_waveform_sampled(head, pred, rows, C, num_mixtures, bits, deterministic, &sp, offset, out, stream);
+}
+extern "C" int wn_sample_waveform_sampled(int32_t head, const float* pred, int64_t rows, int32_t C, int32_t num_mixtures,
+                                          int32_t bits, int32_t deterministic, const wn_sampling* sampling, uint64_t offset,
+                                          float* out, void* stream) {
+  WnSampleCtl ctl = WN_SAMPLE_CTL_OFF;
+  const int rc = wn_sampling_check("sample_waveform", sampling, head, C, &ctl);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int M = head == WN_HEAD_CATEGORICAL ? 0 : num_mixtures;
   if (deterministic) return wn_launch_sample_det(pred, rows, C, M, bits, out, s);
-  return wn_launch_sample_rand(pred, rows, C, M, bits, head, seed, offset, out, s);
+  return wn_launch_sample_rand(pred, rows, C, M, bits, head, sampling->seed, offset, out, s, ctl);
 }
 

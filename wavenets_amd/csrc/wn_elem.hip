@@ -636,6 +636,17 @@ __global__ __launch_bounds__(256) void wn_sample_rand_cat_kernel(const float* pr
   if (lane == 0) out[row] = (float)result * inv - 1.0f;
 }
 
+// ... under the sampling controls: the draw from the tempered / truncated view of the same row
+__global__ __launch_bounds__(256) void wn_sample_rand_cat_ctl_kernel(const float* pred, int64_t rows, int C,
+                                                                     float inv, uint64_t seed, uint64_t offset,
+                                                                     float* out, WnSampleCtl ctl) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int result = wn_draw_cat_row(wn_cat_ctl_view(pred + row * C, C, lane, ctl), C, lane, row, seed, offset);
+  if (lane == 0) out[row] = (float)result * inv - 1.0f;
+}
+
 // The same draw straight from the logits (training step with a compiled sample metric, src/model.py:338):
 // the probabilities are those of wn_softmax_kernel (same lane assignment, same reductions), kept in LDS
 // instead of a (rows, C) tensor in HBM, so the drawn class is the one sample_waveform(softmax(logits)) draws.
@@ -653,15 +664,33 @@ __global__ __launch_bounds__(256) void wn_sample_rand_cat_logits_kernel(const fl
     wn_emit_sample(em, row, v);
   }
 }
+__global__ __launch_bounds__(256) void wn_sample_rand_cat_logits_ctl_kernel(const float* logits, int64_t rows, int C,
+                                                                            float inv_lv, uint64_t seed, uint64_t offset,
+                                                                            float* out, WnEmit em, WnSampleCtl ctl) {
+  __shared__ float q[4][WN_SAMPLE_FUSED_MAXC];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + w;
+  if (row >= rows) return;
+  const float v = wn_cat_rand_row<true>(logits + row * C, C, lane, q[w], row, seed, offset, inv_lv, ctl);
+  if (lane == 0) {
+    out[row] = v;
+    wn_emit_sample(em, row, v);
+  }
+}
 int wn_sample_from_logits_supported(int C) { return C <= WN_SAMPLE_FUSED_MAXC ? 1 : 0; }
+int wn_sample_top_k_max_classes() { return WN_SAMPLE_FUSED_MAXC; }
 int wn_launch_sample_rand_cat_logits(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
                                      float* out, hipStream_t s) {
   return wn_launch_sample_rand_cat_logits_emit(logits, rows, C, bits, seed, offset, out, WnEmit{nullptr, 0, 0, nullptr}, s);
 }
 int wn_launch_sample_rand_cat_logits_emit(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
-                                          float* out, WnEmit em, hipStream_t s) {
+                                          float* out, WnEmit em, hipStream_t s, WnSampleCtl ctl) {
   if (rows <= 0) return WN_OK;
   if (C > WN_SAMPLE_FUSED_MAXC) { wn_set_error("sample from logits: %d classes > %d", C, WN_SAMPLE_FUSED_MAXC); return WN_E_UNSUPPORTED; }
+  if (ctl.on())
+    hipLaunchKernelGGL(wn_sample_rand_cat_logits_ctl_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, rows, C,
+                       1.0f / (float)(1 << (bits - 1)), seed, offset, out, em, ctl);
+  else
   hipLaunchKernelGGL(wn_sample_rand_cat_logits_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, rows, C,
                      1.0f / (float)(1 << (bits - 1)), seed, offset, out, em);
   WN_HIP_CHECK(hipGetLastError());
@@ -675,18 +704,37 @@ __global__ void wn_sample_rand_mix_kernel(const float* pred, int64_t rows, int M
   out[row] = vc;
   wn_emit_sample(em, row, vc);
 }
+__global__ void wn_sample_rand_mix_ctl_kernel(const float* pred, int64_t rows, int M, int kind, uint64_t seed,
+                                              uint64_t offset, float* out, WnEmit em, WnSampleCtl ctl) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  const float vc = wn_mix_rand_row<true>(pred + row * 3 * M, M, kind, row, seed, offset, ctl);
+  out[row] = vc;
+  wn_emit_sample(em, row, vc);
+}
 int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind,
-                          uint64_t seed, uint64_t offset, float* out, hipStream_t s) {
-  return wn_launch_sample_rand_emit(pred, rows, C, M, bits, kind, seed, offset, out, WnEmit{nullptr, 0, 0, nullptr}, s);
+                          uint64_t seed, uint64_t offset, float* out, hipStream_t s, WnSampleCtl ctl) {
+  return wn_launch_sample_rand_emit(pred, rows, C, M, bits, kind, seed, offset, out, WnEmit{nullptr, 0, 0, nullptr}, s, ctl);
 }
 // (categorical rows with an emit target go through wn_launch_sample_rand_cat_logits_emit)
 int wn_launch_sample_rand_emit(const float* pred, int64_t rows, int C, int M, int bits, int kind,
-                               uint64_t seed, uint64_t offset, float* out, WnEmit em, hipStream_t s) {
+                               uint64_t seed, uint64_t offset, float* out, WnEmit em, hipStream_t s, WnSampleCtl ctl) {
   if (rows <= 0) return WN_OK;
   if (M <= 0 && em.out) { wn_set_error("sample_rand_emit: categorical rows start from the logits"); return WN_E_INVALID; }
-  if (M <= 0) {
+  if (M > 0 && ctl.top_k > 0) { wn_set_error("sample_rand_emit: top_k applies to the categorical head only"); return WN_E_INVALID; }
+  if (M <= 0 && ctl.top_k > 0 && C > WN_SAMPLE_FUSED_MAXC) {
+    wn_set_error("sample_rand_emit: top_k over %d classes > %d", C, WN_SAMPLE_FUSED_MAXC);
+    return WN_E_UNSUPPORTED;
+  }
+  if (M <= 0 && ctl.on()) {
+    hipLaunchKernelGGL(wn_sample_rand_cat_ctl_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
+                       pred, rows, C, 1.0f / (float)(1 << (bits - 1)), seed, offset, out, ctl);
+  } else if (M <= 0) {
     hipLaunchKernelGGL(wn_sample_rand_cat_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
                        pred, rows, C, 1.0f / (float)(1 << (bits - 1)), seed, offset, out);
+  } else if (ctl.on()) {
+    hipLaunchKernelGGL(wn_sample_rand_mix_ctl_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
+                       s, pred, rows, M, kind, seed, offset, out, em, ctl);
   } else {
     hipLaunchKernelGGL(wn_sample_rand_mix_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
                        s, pred, rows, M, kind, seed, offset, out, em);

@@ -764,7 +764,9 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
       const int row = tile * 32 + (int)threadIdx.x;
       if (row < a.B) {
         const float* p = lg + threadIdx.x * 32;
-        const float v = a.tail == 3 ? wn_mix_det_row(p, a.mix_M) : wn_mix_rand_row(p, a.mix_M, a.mix_kind, row, a.seed, a.offset);
+        const float v = a.tail == 3 ? wn_mix_det_row(p, a.mix_M)
+                        : a.ctl.on() ? wn_mix_rand_row<true>(p, a.mix_M, a.mix_kind, row, a.seed, a.offset, a.ctl)
+                                     : wn_mix_rand_row(p, a.mix_M, a.mix_kind, row, a.seed, a.offset);
         if (a.samp) a.samp[row] = v;
         a.em.out[(int64_t)row * a.em.length + a.em.step] = v;
         if (a.em.xin_slot) a.em.xin_slot[row] = v;
@@ -783,8 +785,10 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
       const int row = tile * 32 + i;
       if (row >= a.B) break;                          // wave-uniform
       const float* l = a.ws + a.out_off + (int64_t)row * C;
+      // (a.ctl is a kernel argument: the branch on the sampling controls is uniform, and off takes the draw of before)
       const float v = a.tail == 1 ? wn_cat_det_row(l, C, lane, a.inv_lv)
-                                  : wn_cat_rand_row(l, C, lane, q, row, a.seed, a.offset, a.inv_lv);
+                      : a.ctl.on() ? wn_cat_rand_row<true>(l, C, lane, q, row, a.seed, a.offset, a.inv_lv, a.ctl)
+                                   : wn_cat_rand_row(l, C, lane, q, row, a.seed, a.offset, a.inv_lv);
       if (lane == 0) {
         if (a.samp) a.samp[row] = v;
         a.em.out[(int64_t)row * a.em.length + a.em.step] = v;
@@ -819,6 +823,7 @@ static int gn_head_check(const WnGenHeadArgs& a) {
       wn_set_error("gen_head: unsupported layer shape");
       return WN_E_UNSUPPORTED;
     }
+  if ((a.tail == 2 || a.tail == 4) && !(a.ctl.inv_T > 0.f)) { wn_set_error("gen_head: sampling controls not set"); return WN_E_INVALID; }
   return WN_OK;
 }
 int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, hipStream_t s) {
@@ -835,12 +840,8 @@ int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R
 }
 
 int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s) {
-  if (a.nlayers < 1 || a.nlayers > WN_GEN_HEAD_MAX) { wn_set_error("gen_head: bad layer count"); return WN_E_UNSUPPORTED; }
-  for (int i = 0; i < a.nlayers; ++i)
-    if (a.K[i] % 16 != 0 || a.K[i] > 256 || a.N[i] % 32 != 0 || a.N[i] > 256 || (i > 0 && a.K[i] != a.N[i - 1])) {
-      wn_set_error("gen_head: unsupported layer shape");
-      return WN_E_UNSUPPORTED;
-    }
+  const int rc = gn_head_check(a);
+  if (rc) return rc;
   if (a.f32_K > 0 && (a.f32_K != a.N[a.nlayers - 1] || a.f32_K % 64 != 0 || a.f32_N < 1 || a.f32_N > 32 ||
                       (a.tail >= 3 && 3 * a.mix_M != a.f32_N))) {
     wn_set_error("gen_head: unsupported fp32 last layer");

@@ -96,7 +96,7 @@ __global__ void wn_gen_emit_kernel(const float* samp, int B, float* out, int len
 
 // sample from the logits rows [B][Cout] (src/model.py:253-255 + sample_waveform)
 int sample_rows(wn_plan* p, const float* logits_rows, int B, bool deterministic, uint64_t seed, uint64_t step,
-                float* probs_tmp, float* samp, hipStream_t s) {
+                float* probs_tmp, float* samp, hipStream_t s, WnSampleCtl ctl) {
   const float* pred = logits_rows;
   int rc;
   if (p->c.head == WN_HEAD_CATEGORICAL) {
@@ -105,10 +105,34 @@ int sample_rows(wn_plan* p, const float* logits_rows, int B, bool deterministic,
     pred = probs_tmp;
   }
   if (deterministic) return wn_launch_sample_det(pred, B, p->Cout, p->c.num_mixtures, p->c.bits, samp, s);
-  return wn_launch_sample_rand(pred, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, step, samp, s);
+  return wn_launch_sample_rand(pred, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, step, samp, s, ctl);
 }
 
 }  // namespace
+
+// The sampling arguments of the *_sampled entry points, checked before anything touches the device or any other argument
+// is looked at (head: WN_HEAD_*, classes: the categorical row length).  On success *ctl holds the controls the kernels
+// take: top_k >= classes is off.
+int wn_sampling_check(const char* who, const wn_sampling* sp, int head, int classes, WnSampleCtl* ctl) {
+  if (!sp) { wn_set_error("%s: sampling is null", who); return WN_E_INVALID; }
+  const float T = sp->temperature;
+  if (!(T > 0.f) || !std::isfinite(T) || !std::isfinite(1.0f / T)) {
+    wn_set_error("%s: temperature must be finite and > 0 with a finite reciprocal (got %g)", who, (double)T);
+    return WN_E_INVALID;
+  }
+  if (sp->top_k < 0) { wn_set_error("%s: top_k must be >= 0 (got %d)", who, (int)sp->top_k); return WN_E_INVALID; }
+  if (sp->top_k > 0 && head != WN_HEAD_CATEGORICAL) {
+    wn_set_error("%s: top_k applies to the categorical head only (got top_k = %d with a mixture head)", who, (int)sp->top_k);
+    return WN_E_INVALID;
+  }
+  ctl->T = T; ctl->inv_T = 1.0f / T;
+  ctl->top_k = (sp->top_k >= classes) ? 0 : sp->top_k;
+  if (ctl->top_k > 0 && classes > wn_sample_top_k_max_classes()) {
+    wn_set_error("%s: top_k is offered for up to %d classes (got %d)", who, wn_sample_top_k_max_classes(), classes);
+    return WN_E_UNSUPPORTED;
+  }
+  return WN_OK;
+}
 
 extern "C" int64_t wn_generate_guard_slot(const wn_plan* p, int32_t B, int32_t queued) {
   if (!p || B < 1) return -1;
@@ -122,6 +146,19 @@ extern "C" int64_t wn_generate_workspace_floats(const wn_plan* p, int32_t B, int
 extern "C" int wn_generate(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                            int32_t length, int32_t deterministic, int32_t queued, uint64_t seed, float* out,
                            float* workspace, int64_t ws_floats, void* stream) {
+  const wn_sampling sp = {1.0f, 0, seed};
+  return wn_generate_sampled(p, params, window, cond, B, length, deterministic, queued, &sp, out, workspace, ws_floats, stream);
+}
+
+extern "C" int wn_generate_sampled(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                                   int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
+                                   float* out, float* workspace, int64_t ws_floats, void* stream) {
+  WnSampleCtl ctl = WN_SAMPLE_CTL_OFF;
+  {
+    const int rc = wn_sampling_check("generate", sampling, p ? p->c.head : WN_HEAD_CATEGORICAL, p ? p->Cout : 0x7fffffff, &ctl);
+    if (rc) return rc;
+  }
+  const uint64_t seed = sampling->seed;
   if (!p || !params || !window || !out || !workspace || B < 1 || length < 0) { wn_set_error("generate: bad arguments"); return WN_E_INVALID; }
   hipStream_t s = (hipStream_t)stream;
   const int RF = wn_plan_receptive_field(p);
@@ -151,7 +188,7 @@ extern "C" int wn_generate(wn_plan* p, const float* params, const float* window,
       rc = wn_launch_guard_accumulate(pws + L.fwd_absmax, gguard, s);
       if (rc) return rc;
       hipLaunchKernelGGL(wn_gather_last_kernel, dim3((B * p->Cout + 255) / 256), dim3(256), 0, s, pws + L.logits, B, RF, p->Cout, last);
-      rc = sample_rows(p, last, B, deterministic != 0, seed, (uint64_t)step, lastp, samp, s);
+      rc = sample_rows(p, last, B, deterministic != 0, seed, (uint64_t)step, lastp, samp, s, ctl);
       if (rc) return rc;
       hipLaunchKernelGGL(wn_gen_shift_kernel, dim3((B * RF + 255) / 256), dim3(256), 0, s, win[step & 1], samp, B, RF,
                          win[(step + 1) & 1], out, length, step);
@@ -177,7 +214,7 @@ extern "C" int wn_generate(wn_plan* p, const float* params, const float* window,
   rc = wn_launch_guard_accumulate(pws + L.fwd_absmax, gguard, s);
   if (rc) return rc;
   hipLaunchKernelGGL(wn_gather_last_kernel, dim3((B * p->Cout + 255) / 256), dim3(256), 0, s, pws + L.logits, B, RF, p->Cout, last);
-  rc = sample_rows(p, last, B, deterministic != 0, seed, 0, lastp, samp, s);
+  rc = sample_rows(p, last, B, deterministic != 0, seed, 0, lastp, samp, s, ctl);
   if (rc) return rc;
   // sample 0 is x[RF]; it becomes the network input at time tau = RF
   hipLaunchKernelGGL(wn_gen_emit_kernel, dim3((B + 255) / 256), dim3(256), 0, s, samp, B, out, length, 0,
@@ -396,7 +433,7 @@ extern "C" int wn_generate(wn_plan* p, const float* params, const float* window,
       if (head_tail) {
         ha.tail = deterministic ? 1 : 2;
         ha.inv_lv = 1.0f / (float)(1 << (p->c.bits - 1));
-        ha.seed = seed; ha.offset = (uint64_t)step;
+        ha.seed = seed; ha.offset = (uint64_t)step; ha.ctl = ctl;
         ha.samp = samp;
         ha.em = WnEmit{out, length, step, R.xin + (int64_t)((tau + 1) % p->KS) * B};
       }
@@ -424,7 +461,7 @@ extern "C" int wn_generate(wn_plan* p, const float* params, const float* window,
       ha.f32_w_off = G.prime + L.frag + cl.fragF; ha.f32_bias_off = p->tensors[cl.bias_t].off;
       ha.f32_K = cl.cin; ha.f32_N = cl.cout;
       ha.tail = deterministic ? 3 : 4; ha.mix_M = p->c.num_mixtures; ha.mix_kind = p->c.head;
-      ha.seed = seed; ha.offset = (uint64_t)step; ha.samp = samp;
+      ha.seed = seed; ha.offset = (uint64_t)step; ha.samp = samp; ha.ctl = ctl;
       ha.em = WnEmit{out, length, step, R.xin + (int64_t)((tau + 1) % p->KS) * B};
       rc = wn_launch_gen_head(ha, s);
       if (rc) return rc;
@@ -452,14 +489,14 @@ extern "C" int wn_generate(wn_plan* p, const float* params, const float* window,
       // wn_softmax_kernel in LDS, the class sample_waveform(softmax(logits)) draws)
       const WnEmit em{out, length, step, R.xin + (int64_t)((tau + 1) % p->KS) * B};
       if (p->c.head == WN_HEAD_CATEGORICAL && !deterministic && wn_sample_from_logits_supported(p->Cout)) {
-        rc = wn_launch_sample_rand_cat_logits_emit(last, B, p->Cout, p->c.bits, seed, (uint64_t)step, samp, em, s);
+        rc = wn_launch_sample_rand_cat_logits_emit(last, B, p->Cout, p->c.bits, seed, (uint64_t)step, samp, em, s, ctl);
         if (rc) return rc;
       } else if (p->c.head != WN_HEAD_CATEGORICAL) {
         if (deterministic) rc = wn_launch_sample_det_emit(last, B, p->Cout, p->c.num_mixtures, p->c.bits, samp, em, s);
-        else rc = wn_launch_sample_rand_emit(last, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, (uint64_t)step, samp, em, s);
+        else rc = wn_launch_sample_rand_emit(last, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, (uint64_t)step, samp, em, s, ctl);
         if (rc) return rc;
       } else {
-        rc = sample_rows(p, last, B, deterministic != 0, seed, (uint64_t)step, lastp, samp, s);
+        rc = sample_rows(p, last, B, deterministic != 0, seed, (uint64_t)step, lastp, samp, s, ctl);
         if (rc) return rc;
         hipLaunchKernelGGL(wn_gen_emit_kernel, dim3((B + 255) / 256), dim3(256), 0, s, samp, B, out, length, step,
                            R.xin + (int64_t)((tau + 1) % p->KS) * B);

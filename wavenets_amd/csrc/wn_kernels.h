@@ -287,6 +287,14 @@ int wn_launch_gen_relay128(const WnGen128Args& a, hipStream_t s);
 int64_t wn_gen_relay128_floats(int B, int nblocks);
 // queued generation: where a sampler also puts its sample (output rows [rows][length] at column step; network input slot)
 struct WnEmit { float* out; int length; int step; float* xin_slot; };
+// sampling controls of a stochastic draw (wn_sample.h; semantics: include/wn_hip.h, struct wn_sampling): temperature T with
+// inv_T = 1 / T finite, top_k = 0 off (callers pass 0 for top_k >= classes).  on() false = the draw without controls.
+struct WnSampleCtl {
+  float T, inv_T;
+  int32_t top_k;
+  __host__ __device__ bool on() const { return T != 1.0f || top_k > 0; }
+};
+#define WN_SAMPLE_CTL_OFF (WnSampleCtl{1.0f, 1.0f, 0})
 // the head of a generation step in one launch (wn_gen.hip)
 #define WN_GEN_HEAD_MAX 4
 struct WnGenHeadArgs {
@@ -310,6 +318,7 @@ struct WnGenHeadArgs {
   float* samp;                     // [B] samples (or null)
   WnEmit em;                       // output rows / network input slot
   float* guard;                    // range guard of the generate call (hidden activations are cast to fp16 hi | lo), or null
+  WnSampleCtl ctl;                 // tails 2 and 4: temperature / top-k (set it: all-zero bytes are not 'off')
 };
 int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s);
 int wn_gen_blocks_supported(int R, int D, int KS);
@@ -384,14 +393,16 @@ int wn_launch_sqdiff_sum(const float* a, const float* b, int64_t n, float scale,
 // deterministic samplers: categorical argmax -> left bin edge; mixtures -> clipped mean
 int wn_launch_sample_det_emit(const float* pred, int64_t rows, int C, int M, int bits, float* out, WnEmit em, hipStream_t s);
 int wn_launch_sample_rand_emit(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t seed, uint64_t offset,
-                               float* out, WnEmit em, hipStream_t s);
+                               float* out, WnEmit em, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF);
 int wn_launch_sample_rand_cat_logits_emit(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
-                                          float* out, WnEmit em, hipStream_t s);
+                                          float* out, WnEmit em, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF);
+// top-k is offered for up to this many classes (WN_SAMPLE_FUSED_MAXC, wn_elem.hip)
+int wn_sample_top_k_max_classes();
 int wn_launch_sample_det(const float* pred, int64_t rows, int C, int M, int bits, float* out,
                          hipStream_t s);
 // stochastic samplers (Philox4x32-10 keyed by seed, counter = row)
 int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind,
-                          uint64_t seed, uint64_t offset, float* out, hipStream_t s);
+                          uint64_t seed, uint64_t offset, float* out, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF);
 
 // ---------------------------------------------------------------- optimizer
 int wn_launch_sumsq(const float* g, const WnTensorDesc* d_table, int n, float* norms2, hipStream_t s);

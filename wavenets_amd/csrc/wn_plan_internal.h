@@ -374,3 +374,7 @@ int loss_stage(wn_plan* p, int B, int T, int global_batch, bool want_grad, float
                float* loss_out, float* absmax_out, hipStream_t s, bool fused_done = false);
 
 }  // namespace wnp
+
+// ---- wn_generate.hip ----
+// the sampling arguments of wn_generate_sampled / wn_sample_waveform_sampled -> the controls the kernels take
+int wn_sampling_check(const char* who, const wn_sampling* sp, int head, int classes, WnSampleCtl* ctl);

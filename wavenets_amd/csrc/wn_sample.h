@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include "wn_kernels.h"
 
 // ------------------------------------------------------------------------------------------
 // wave-per-row helpers
@@ -89,6 +90,94 @@ __device__ __forceinline__ int wn_draw_cat_row(P p, int C, int lane, int64_t row
 }
 
 
+// ------------------------------------------------------------------------------------------
+// Sampling controls: temperature T and top-k.  on() false = the draw without controls, which every
+// call site reaches by the code it ran before the controls existed (wave-uniform branch or a second instantiation).
+// (struct WnSampleCtl: wn_kernels.h)
+
+// The tempered / truncated law of a categorical row, as a view of the normalised probability row p[0..C) the wave holds
+// (global memory or LDS): element j reads as  keep(j) ? (p[j] / p_max)^(1/T) : 0.  The largest term is exactly 1, so no T
+// underflows the total.  wn_draw_cat_row takes the view in place of the row; the sliding window (stored softmax row), the
+// queued samplers (softmax row in LDS) and sample_waveform build it with wn_cat_ctl_view from the same values, so they
+// pick the same class for the same uniform number.
+// keep(j): rank by (probability descending, class index ascending), first top_k.  Probabilities are non-negative, so
+// their bit patterns order as unsigned integers: key > thr, or key == thr and j <= idx_cut.
+template <typename P>
+struct WnCatCtlView {
+  P p;
+  float pmax, inv_T;
+  uint32_t thr;
+  int idx_cut;
+  __device__ __forceinline__ static uint32_t key(float v) { return v > 0.f ? __builtin_bit_cast(uint32_t, v) : 0u; }
+  __device__ __forceinline__ float operator[](int j) const {
+    const float v = p[j];
+    const uint32_t k = key(v);
+    if (!(k > thr || (k == thr && j <= idx_cut))) return 0.f;
+    const float r = fmaxf(v, 0.f) / pmax;
+    return inv_T == 1.0f ? r : expf(inv_T * logf(r));      // r = 1 -> exactly 1; r = 0 -> 0
+  }
+};
+// Builds the view: one wave per row, all 64 lanes active, every lane gets the same view.  The k-th largest key by
+// bisection on the key (at most 31 rounds of count(key >= mid), a ballot + popcount per register slot for C <= 256, a
+// strided loop over the row beyond), then the ties at the threshold by class index with ballot prefix counts.
+template <typename P>
+__device__ __forceinline__ WnCatCtlView<P> wn_cat_ctl_view(P p, int C, int lane, WnSampleCtl ctl) {
+  using V = WnCatCtlView<P>;
+  V w{p, 1.0f, ctl.inv_T, 0u, 0x7fffffff};
+  const bool regs = C <= 256;
+  uint32_t kr[4] = {0u, 0u, 0u, 0u};
+  float m = 0.f;
+  if (regs) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      if (lane + 64 * s < C) { const float v = p[lane + 64 * s]; kr[s] = V::key(v); m = fmaxf(m, v); }
+  } else {
+    for (int j = lane; j < C; j += 64) m = fmaxf(m, p[j]);
+  }
+  m = wn_wave_max(m);
+  w.pmax = m > 0.f ? m : 1.0f;                       // an all-zero row stays all zero (the draw then returns class C - 1)
+  if (ctl.top_k <= 0 || ctl.top_k >= C) return w;
+  // count of classes whose key is >= t (t > 0 excludes the empty register slots, key 0) / == t, wave-uniform
+  auto count_ge = [&](uint32_t t) {
+    int c = 0;
+    if (regs) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) c += __popcll(__ballot(kr[s] >= t));
+    } else {
+      for (int j0 = 0; j0 < C; j0 += 64) c += __popcll(__ballot(j0 + lane < C && V::key(p[min(j0 + lane, C - 1)]) >= t));
+    }
+    return c;
+  };
+  // largest thr with count(key >= thr) >= top_k: lo always satisfies it (count(key >= 0) = C > top_k), hi never does
+  uint32_t lo = 0u, hi = V::key(m) + 1u;
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (count_ge(mid) >= ctl.top_k) lo = mid; else hi = mid;
+  }
+  w.thr = lo;
+  int need = ctl.top_k - count_ge(lo + 1u);               // of the ties at thr, the first `need` by class index
+  // slot s = classes 64 s .. 64 s + 63 in lane order; returns true once the need-th tie is found
+  auto take = [&](int s, bool tie) {
+    const unsigned long long mask = __ballot(tie);
+    const int cnt = __popcll(mask);
+    if (need > cnt) { need -= cnt; return false; }
+    const unsigned long long hit = __ballot(tie && __popcll(mask & ((2ull << lane) - 1ull)) == need);
+    w.idx_cut = 64 * s + __builtin_ctzll(hit);
+    return true;
+  };
+  if (regs) {
+    bool done = false;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      if (!done) done = take(s, lane + 64 * s < C && kr[s] == lo);
+  } else {
+    for (int s = 0; 64 * s < C; ++s)
+      if (take(s, 64 * s + lane < C && V::key(p[min(64 * s + lane, C - 1)]) == lo)) break;
+  }
+  return w;
+}
+
+
 // Categorical head, deterministic (src/model.py:393-421 with deterministic sampling): softmax -> arg max -> sample value.
 // The arithmetic is that of wn_softmax_kernel followed by wn_sample_det_cat_kernel (same lane assignment, same
 // reductions), so the result is the same sample.  Every lane returns it.
@@ -118,8 +207,10 @@ __device__ __forceinline__ float wn_cat_det_row(const float* l, int C, int lane,
 // Categorical head, stochastic draw straight from the logits: the probabilities are those of wn_softmax_kernel (same lane
 // assignment, same reductions), kept in the LDS row q[0..C) instead of a (rows, C) tensor in HBM, so the drawn class is
 // the one sample_waveform(softmax(logits)) draws.  Every lane returns the sample value.
+// CTL: the draw under the sampling controls, from the view of the same LDS row.
+template <bool CTL = false>
 __device__ __forceinline__ float wn_cat_rand_row(const float* l, int C, int lane, float* q, int64_t row, uint64_t seed,
-                                                 uint64_t offset, float inv_lv) {
+                                                 uint64_t offset, float inv_lv, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF) {
   if (C <= 256) {
     // one read of the row, one exp per class (element k of a lane = class lane + 64 k: the same per-lane
     // order of the max / sum as the loops below)
@@ -152,7 +243,9 @@ __device__ __forceinline__ float wn_cat_rand_row(const float* l, int C, int lane
   }
   __builtin_amdgcn_wave_barrier();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  const int result = wn_draw_cat_row((const float*)q, C, lane, row, seed, offset);
+  int result;
+  if constexpr (CTL) result = wn_draw_cat_row(wn_cat_ctl_view((const float*)q, C, lane, ctl), C, lane, row, seed, offset);
+  else result = wn_draw_cat_row((const float*)q, C, lane, row, seed, offset);
   return (float)result * inv_lv - 1.0f;
 }
 
@@ -163,18 +256,25 @@ __device__ __forceinline__ float wn_mix_det_row(const float* p, int M) {
   for (int k = 1; k < M; ++k) if (p[k] > best) { best = p[k]; bi = k; }
   return fminf(fmaxf(p[M + bi], -1.0f), 1.0f);
 }
-__device__ __forceinline__ float wn_mix_rand_row(const float* p, int M, int kind, int64_t row, uint64_t seed, uint64_t offset) {
+// CTL: at temperature T the row reads [w / T | mu | s + ln T] -- component pick sharpened, component scale times T; the
+// Philox words keep their use and the clip is unchanged.
+template <bool CTL = false>
+__device__ __forceinline__ float wn_mix_rand_row(const float* p, int M, int kind, int64_t row, uint64_t seed, uint64_t offset,
+                                                 WnSampleCtl ctl = WN_SAMPLE_CTL_OFF) {
   uint32_t r[4];
   wn_philox((uint64_t)row, offset, seed, r);
+  auto w = [&](int k) { if constexpr (CTL) return p[k] * ctl.inv_T; else return p[k]; };
   float wm = -INFINITY;
-  for (int k = 0; k < M; ++k) wm = fmaxf(wm, p[k]);
+  for (int k = 0; k < M; ++k) wm = fmaxf(wm, w(k));
   float wz = 0.f;
-  for (int k = 0; k < M; ++k) wz += expf(p[k] - wm);
+  for (int k = 0; k < M; ++k) wz += expf(w(k) - wm);
   const float target = wn_u01(r[0]) * wz;
   int sel = M - 1;
   float run = 0.f;
-  for (int k = 0; k < M; ++k) { run += expf(p[k] - wm); if (run > target) { sel = k; break; } }
-  const float mu = p[M + sel], sc = expf(p[2 * M + sel]);
+  for (int k = 0; k < M; ++k) { run += expf(w(k) - wm); if (run > target) { sel = k; break; } }
+  const float mu = p[M + sel];
+  float sc = expf(p[2 * M + sel]);
+  if constexpr (CTL) sc *= ctl.T;                  // e^(s + ln T)
   float v;
   if (kind == 1) {                       // logistic: mu + s (ln z - ln(1-z))     src/model.py:463-483
     const float zz = wn_u01(r[1]);

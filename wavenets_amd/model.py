@@ -656,18 +656,43 @@ class WaveNet(torch.nn.Module):
     _lib.check(_lib.lib().wn_quantize(_lib.ptr(x), _lib.ptr(idx), x.numel(), self.bits, _lib.stream_ptr()))
     return idx
 
-  def sample_waveform(self, inputs, deterministic=False):
+  def _sampling(self, temperature, top_k, seed, classes):
+    """The sampling controls of a stochastic draw as the C struct (semantics: include/wn_hip.h, struct wn_sampling),
+    checked as the library checks them, before any work is queued.  classes: row length of a categorical prediction."""
+    if isinstance(top_k, bool) or not isinstance(top_k, int):
+      raise ValueError(f'top_k must be an int (got {top_k!r})')
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+      raise ValueError(f'seed must be an int or None (got {seed!r})')
+    t = np.float32(temperature)
+    with np.errstate(all='ignore'):
+      if not (t > 0 and np.isfinite(t) and np.isfinite(np.float32(1.0) / t)):
+        raise ValueError(f'temperature must be finite and > 0 with a finite reciprocal (got {temperature!r})')
+    if not 0 <= top_k < 2**31:
+      raise ValueError(f'top_k must be >= 0 (got {top_k})')
+    if top_k > 0 and self.sampling_function != 'categorical':
+      raise ValueError(f'top_k applies to the categorical head only (got top_k = {top_k} with {self.sampling_function})')
+    if 0 < top_k < classes and classes > _lib.WN_TOP_K_MAX_CLASSES:
+      raise ValueError(f'top_k is offered for up to {_lib.WN_TOP_K_MAX_CLASSES} classes (got {classes})')
+    key = 0x0402 if seed is None else seed & 0xFFFFFFFFFFFFFFFF
+    return _lib.WnSampling(float(t), top_k, key)
+
+  def sample_waveform(self, inputs, deterministic=False, temperature=1.0, top_k=0, seed=None):
     """src/model.py:393-503: (B,T,C_out) -> (B,T,1).  Stochastic draws use Philox keyed by the
-    reference's seed (4,2) -> 0x0402 plus a per-call offset (TF's stream is not reproducible)."""
+    reference's seed (4,2) -> 0x0402 plus a per-call offset (TF's stream is not reproducible).
+    temperature / top_k / seed (additions): categorical rows are drawn from p^(1/T) over the
+    top_k most probable classes (ties: lower class index first; 0 or >= classes = all), mixture rows from
+    [w / T | mu | s + ln T]; seed replaces the key 0x0402.  The defaults are the draw without them, bit for bit."""
     pred = torch.as_tensor(inputs, dtype=torch.float32, device=self._device).contiguous()
     if pred.dim() != 3:
       raise ValueError('prediction must have shape (batch, samples, channels)')
     B, T, Cc = pred.shape
+    sampling = self._sampling(temperature, top_k, seed, Cc)
     out = torch.empty(B, T, 1, dtype=torch.float32, device=self._device)
     self._sample_calls += 1
-    _lib.check(_lib.lib().wn_sample_waveform(_lib.HEADS[self.sampling_function], _lib.ptr(pred), B * T, Cc,
-                                              self.num_mixtures or 0, self.bits, int(bool(deterministic)),
-                                              0x0402, self._sample_calls, _lib.ptr(out), _lib.stream_ptr()))
+    _lib.check(_lib.lib().wn_sample_waveform_sampled(_lib.HEADS[self.sampling_function], _lib.ptr(pred), B * T, Cc,
+                                                      self.num_mixtures or 0, self.bits, int(bool(deterministic)),
+                                                      C.byref(sampling), self._sample_calls, _lib.ptr(out),
+                                                      _lib.stream_ptr()))
     return out
 
   def loss_fn(self, target, pred):
@@ -687,9 +712,12 @@ class WaveNet(torch.nn.Module):
 
   # ------------------------------------------------------------------ generation
   def generate(self, length, batch_size: int = 1, condition=None, sample=None,
-               use_queues=False, deterministic=False):
+               use_queues=False, deterministic=False, temperature=1.0, top_k=0, seed=None):
     """src/model.py:258-307 (intended semantics; the reference's kwarg / rank bugs are not
-    reproduced).  Returns (B, length, 1)."""
+    reproduced).  Returns (B, length, 1).
+    temperature / top_k / seed (additions) as in sample_waveform; an int seed is the Philox key of
+    the draws and seeds the initial noise window when `sample` is None.  seed=None is seed=0x0402."""
+    sampling = self._sampling(temperature, top_k, seed, 2 ** self.bits)
     if self.conditioning is not None and condition is None:
       raise ValueError('Conditioning must be provided.')
     if condition is not None:
@@ -708,7 +736,7 @@ class WaveNet(torch.nn.Module):
       if deterministic:
         sample = torch.zeros(batch_size, rf, 1, device=self._device)
       else:
-        g = torch.Generator(device='cpu').manual_seed(0x0402)
+        g = torch.Generator(device='cpu').manual_seed(int(sampling.seed))
         sample = torch.randn(batch_size, rf, 1, generator=g).to(self._device)
     if sample.shape[1] != rf:
       if sample.shape[1] < rf:
@@ -720,9 +748,9 @@ class WaveNet(torch.nn.Module):
     ws = self._workspace('gen', L.wn_generate_workspace_floats(self._plan, batch_size, int(bool(use_queues))))
     out = torch.empty(batch_size, int(length), 1, dtype=torch.float32, device=self._device)
     def run():
-      _lib.check(L.wn_generate(self._plan, _lib.ptr(self.flat_params), _lib.ptr(sample), _lib.ptr(condition),
-                               batch_size, int(length), int(bool(deterministic)), int(bool(use_queues)), 0x0402,
-                               _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+      _lib.check(L.wn_generate_sampled(self._plan, _lib.ptr(self.flat_params), _lib.ptr(sample), _lib.ptr(condition),
+                                       batch_size, int(length), int(bool(deterministic)), int(bool(use_queues)),
+                                       C.byref(sampling), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
     run()
     # range guard (one host read; the caller reads the samples anyway): an activation beyond the fp16 range of the
     # split-precision kernels -> the whole call again on the exact-fp32 kernels (same seed: same draws)
