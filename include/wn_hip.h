@@ -190,6 +190,14 @@ int wn_adam_step_guarded(wn_plan* p, float* params, const float* grads, float* m
                          float lr, float beta1, float beta2, float eps, float clipnorm, float* scratch,
                          const float* skip_flag, void* stream);
 
+/* ---- per-replica clipnorm ahead of the data-parallel all-reduce (Adam(clip_before_reduce=True)) ----
+ * In place on the plan's flat gradient: every tensor t of wn_plan_tensor_info becomes
+ * g_t * clipnorm / max(||g_t||, clipnorm), the norm accumulated in double.  A tensor whose norm is <= clipnorm (0
+ * included) stays bit-identical.  Nothing past wn_plan_param_count(p) floats is read or written.  scratch: >= num_tensors
+ * floats, receives the squared norms.  clipnorm must be finite and > 0 (WN_E_INVALID otherwise, checked before the
+ * device is touched).  The following wn_adam_step then takes clipnorm 0. */
+int wn_clip_gradients(wn_plan* p, float* grads, float clipnorm, float* scratch, void* stream);
+
 /* ---- forward range guard of the split-precision mode ----
  * The default kernels evaluate fp32 products from fp16 hi|lo operand splits; an activation beyond the fp16 range
  * (65504) would turn into inf/NaN.  Every forward pass therefore keeps the running max-abs of the tensors that feed

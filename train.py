@@ -34,6 +34,9 @@ config = {                       # defaults of the reference, train.py:22-50
     'preview_length': 0, 'condition_classes': 2, 'labels': None,
     'preview_temperature': 1.0, 'preview_top_k': 0, 'preview_seed': None,   # WaveNet.generate's sampling controls
     'checkpoint_format': 'npz',    # 'h5': Keras .weights.h5 exchange files (weights only, as the reference writes them)
+    # data parallel: clip every replica's gradient to clipnorm BEFORE the all-reduce (the Keras 3 order) instead of the
+    # reduced gradient after it; configuration, not state: checkpoints do not carry it
+    'clip_before_reduce': False,
 }
 
 
@@ -105,7 +108,8 @@ def main():
                   device=dev)
   if conditioned:                                                  # Keras builds on the first call (train.py:232-235):
     model.build([(per_rank, L, 1), (per_rank, cond.shape[1])])    # the condition width fixes the mapping net's shapes
-  opt = Adam(learning_rate=config['lr'], clipnorm=1.0)           # train.py:225-226
+  opt = Adam(learning_rate=config['lr'], clipnorm=1.0,           # train.py:225-226
+             clip_before_reduce=config['clip_before_reduce'])
   model.compile(optimizer=opt, metrics=[MeanSquaredError()])          # train.py:225-228
   print('Receptive field') if rank == 0 else None
   if rank == 0:

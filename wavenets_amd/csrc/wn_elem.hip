@@ -774,6 +774,70 @@ int wn_launch_sumsq(const float* g, const WnTensorDesc* d_table, int n, float* n
   return WN_OK;
 }
 
+// Per-replica clipnorm ahead of the data-parallel all-reduce (Adam(clip_before_reduce=True)): in place, tensor t
+// becomes g_t * clipnorm / max(||g_t||, clipnorm).  One workgroup of 1024 threads owns one tensor: it reduces the
+// squared norm in double (as wn_sumsq_kernel does), then rescales the same <= 256 KiB, which it has just pulled into
+// L2 -- no sumsq launch, no norms round trip, no scale launch.  A tensor inside the bound (norm 0 included) has scale
+// exactly 1.0f and is not written at all.  The body moves float4; the scalar head and tail keep every access inside
+// [off, off + len), whatever the alignment of the tensor: the step's scalars sit right behind the last gradient.
+#define WN_CLIP_THREADS 1024
+__global__ void __launch_bounds__(WN_CLIP_THREADS)
+wn_clip_kernel(float* g, const WnTensorDesc* table, float clipnorm, float* norms2) {
+  __shared__ double sm[WN_CLIP_THREADS / 64];
+  __shared__ float sm_scale;
+  const WnTensorDesc d = table[blockIdx.x];
+  float* p = g + d.off;
+  const int tid = threadIdx.x;
+  int64_t head = (int64_t)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2;    // floats up to 16-byte alignment
+  if (head > d.len) head = d.len;
+  const int64_t nvec = (d.len - head) >> 2;
+  const int64_t tail = head + 4 * nvec;
+  float4* pv = reinterpret_cast<float4*>(p + head);
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  int64_t i = tid;
+  for (; i + WN_CLIP_THREADS < nvec; i += 2 * WN_CLIP_THREADS) {       // two loads in flight per thread
+    const float4 x = pv[i], y = pv[i + WN_CLIP_THREADS];
+    a0 += (double)x.x * (double)x.x; a1 += (double)x.y * (double)x.y;
+    a2 += (double)x.z * (double)x.z; a3 += (double)x.w * (double)x.w;
+    a0 += (double)y.x * (double)y.x; a1 += (double)y.y * (double)y.y;
+    a2 += (double)y.z * (double)y.z; a3 += (double)y.w * (double)y.w;
+  }
+  for (; i < nvec; i += WN_CLIP_THREADS) {
+    const float4 x = pv[i];
+    a0 += (double)x.x * (double)x.x; a1 += (double)x.y * (double)x.y;
+    a2 += (double)x.z * (double)x.z; a3 += (double)x.w * (double)x.w;
+  }
+  if (tid < head) a0 += (double)p[tid] * (double)p[tid];
+  if (tail + tid < d.len) a1 += (double)p[tail + tid] * (double)p[tail + tid];
+  double acc = (a0 + a1) + (a2 + a3);
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((tid & 63) == 0) sm[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double n2 = 0.0;
+    for (int w = 0; w < WN_CLIP_THREADS / 64; ++w) n2 += sm[w];
+    const float n2f = (float)n2;
+    norms2[blockIdx.x] = n2f;
+    sm_scale = clipnorm / fmaxf(sqrtf(n2f), clipnorm);     // tf.clip_by_norm, the expression of wn_adam_kernel
+  }
+  __syncthreads();
+  const float scale = sm_scale;
+  if (scale == 1.0f) return;       // uniform: inside the bound, the tensor stays bit-identical
+  for (i = tid; i < nvec; i += WN_CLIP_THREADS) {
+    float4 x = pv[i];
+    x.x *= scale; x.y *= scale; x.z *= scale; x.w *= scale;
+    pv[i] = x;
+  }
+  if (tid < head) p[tid] *= scale;
+  if (tail + tid < d.len) p[tail + tid] *= scale;
+}
+int wn_launch_clip(float* g, const WnTensorDesc* d_table, int n, float clipnorm, float* norms2, hipStream_t s) {
+  if (n <= 0) return WN_OK;
+  hipLaunchKernelGGL(wn_clip_kernel, dim3(n), dim3(WN_CLIP_THREADS), 0, s, g, d_table, clipnorm, norms2);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
 __global__ void wn_adam_kernel(float* p, const float* g, float* m, float* v, const WnTensorDesc* table,
                                const float* norms2, float clipnorm, float alpha, float beta1,
                                float beta2, float eps, const float* skip_flag) {

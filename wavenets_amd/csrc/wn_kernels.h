@@ -406,6 +406,8 @@ int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bit
 
 // ---------------------------------------------------------------- optimizer
 int wn_launch_sumsq(const float* g, const WnTensorDesc* d_table, int n, float* norms2, hipStream_t s);
+// in place: g_t *= clipnorm / max(||g_t||, clipnorm) per tensor of the table, norms2[t] = ||g_t||^2 (one launch)
+int wn_launch_clip(float* g, const WnTensorDesc* d_table, int n, float clipnorm, float* norms2, hipStream_t s);
 int wn_launch_axpy_table(float* y, const float* x, const WnTensorDesc* d_table, int n, float coef,
                          hipStream_t s);
 int wn_launch_adam(float* p, const float* g, float* m, float* v, const WnTensorDesc* d_table, int n,

@@ -772,6 +772,14 @@ extern "C" int wn_adam_step_guarded(wn_plan* p, float* params, const float* grad
   return wn_launch_adam(params, grads, m, v, p->d_tdesc, n, scratch, clipnorm, (float)alpha, beta1, beta2, eps, skip_flag, s);
 }
 
+extern "C" int wn_clip_gradients(wn_plan* p, float* grads, float clipnorm, float* scratch, void* stream) {
+  if (!p || !grads || !scratch) { wn_set_error("clip_gradients: bad arguments"); return WN_E_INVALID; }
+  if (!(clipnorm > 0.f) || !std::isfinite(clipnorm)) { wn_set_error("clip_gradients: clipnorm must be finite and > 0 (got %g)", (double)clipnorm); return WN_E_INVALID; }
+  int rc = ensure_device_tables(p);
+  if (rc) return rc;
+  return wn_launch_clip(grads, p->d_tdesc, (int)p->tdesc.size(), clipnorm, scratch, (hipStream_t)stream);
+}
+
 extern "C" int wn_adam_step(wn_plan* p, float* params, const float* grads, float* m, float* v, int64_t step,
                             float lr, float beta1, float beta2, float eps, float clipnorm, float* scratch,
                             void* stream) {

@@ -6,8 +6,12 @@ computes gradients of ``sum_local(loss) / B_global`` (tf.nn.compute_average_loss
 src/model.py:328-329) and the optimizer SUM-all-reduces them (src/model.py:336).  Here the
 same exchange is ONE all-reduce over the flat fp32 gradient bucket (gradient + {loss, reg_loss}; 5.0 MB for
 BASELINE configs[2]); utterances are sharded by rows, parameters and Adam state replicated.
-Clipnorm is applied AFTER the reduction on every rank (deterministic, identical replicas;
-SURVEY.md section 8c records the Keras-version ambiguity)."""
+By default clipnorm is applied AFTER the reduction on every rank, inside the Adam launch (deterministic, identical
+replicas; N ranks then equal one process on the global batch).  SURVEY.md section 8c records that the order depends on
+the Keras version: Keras 3 clips every replica's own gradient and sums the clipped ones.  ``Adam(clip_before_reduce=True)``
+is that order: ``WaveNet.train_step`` launches ``wn_clip_gradients`` on the local gradient right in front of the
+collective below (the bucket's tail of scalars is not touched) and the Adam launch clips nothing.  Replicas stay
+bit-identical either way; the two orders are different optimizers as soon as N > 1."""
 from __future__ import annotations
 
 import torch

@@ -593,11 +593,16 @@ class WaveNet(torch.nn.Module):
           dp.allreduce_bucket(vec)
         self._mirror(vec)
       loss, sample, y_true = self.loss_and_grads(data, want_sample=want_metric, _loss_in_bucket=True, _between=between)
+      self.optimizer.clip_local_gradients(self)         # clip_before_reduce only; in place, see the note below
       dp.allreduce_bucket(self._grad_bucket)            # gradients + tail; no-op without a process group
       self.optimizer.apply_gradients(self, skip_flag=tail[2:3])
     else:
       loss, sample, y_true = self.loss_and_grads(data, want_sample=want_metric, _loss_in_bucket=True)
       queue_metrics(sample, y_true)
+      # Adam(clip_before_reduce=True) clips THIS replica's gradient in place ahead of the SUM (one path, with or without a
+      # process group; the tail behind the gradient is not touched).  In place is safe under the range guard: a tripped
+      # step is skipped by the flag and repeated from scratch, gradients recomputed, so nothing is clipped twice.
+      self.optimizer.clip_local_gradients(self)
       dp.allreduce_bucket(self._grad_bucket)            # the step's ONE collective: gradients + {loss, reg_loss, flag, metrics}
       self._mirror(tail[:nt])
       self.optimizer.apply_gradients(self, skip_flag=tail[2:3])
