@@ -189,6 +189,15 @@ int wn_adam_step(wn_plan* p, float* params, const float* grads, float* m, float*
 int wn_adam_step_guarded(wn_plan* p, float* params, const float* grads, float* m, float* v, int64_t step,
                          float lr, float beta1, float beta2, float eps, float clipnorm, float* scratch,
                          const float* skip_flag, void* stream);
+/* Adam(use_ema=True): the guarded update plus the exponential moving average of the weights, in the same launch.
+ * After the parameter update of step t: t == 1: ema = p (a copy); t > 1: ema = ema + (p - ema) * (1 - ema_momentum),
+ * fp32 in that form; then, when ema_overwrite is 1, p = ema (the host decides: t % ema_overwrite_frequency == 0).
+ * A skipped step (*skip_flag != 0) leaves ema untouched together with p, m, v.  ema: wn_plan_param_count floats.
+ * ema_momentum must be finite and in [0, 1], ema_overwrite 0 or 1 (WN_E_INVALID otherwise, checked before the device is
+ * touched). */
+int wn_adam_step_ema(wn_plan* p, float* params, const float* grads, float* m, float* v, float* ema, int64_t step,
+                     float lr, float beta1, float beta2, float eps, float clipnorm, float ema_momentum,
+                     int32_t ema_overwrite, float* scratch, const float* skip_flag, void* stream);
 
 /* ---- per-replica clipnorm ahead of the data-parallel all-reduce (Adam(clip_before_reduce=True)) ----
  * In place on the plan's flat gradient: every tensor t of wn_plan_tensor_info becomes

@@ -37,7 +37,30 @@ config = {                       # defaults of the reference, train.py:22-50
     # data parallel: clip every replica's gradient to clipnorm BEFORE the all-reduce (the Keras 3 order) instead of the
     # reduced gradient after it; configuration, not state: checkpoints do not carry it
     'clip_before_reduce': False,
+    # Adam's exponential moving average of the weights (Keras keywords): previews and averaged.weights.h5 use the average
+    'use_ema': False, 'ema_momentum': 0.99, 'ema_overwrite_frequency': None,
+    # hold the last n utterances' frames out of training and report val_loss (test_step) after every epoch; the monitored
+    # quantity of checkpointing, plateau and early stop stays loss, as in the reference
+    'validation_utterances': 0,
 }
+
+
+def validate(model, frames, cond, per_rank, rank, world, scope):
+  """Mean test_step loss over the held-out frames (whole global batches; a smaller set is one batch of what is there),
+  on the averaged weights under use_ema.  Runs after the epoch's training results were read: the metrics are reset per
+  pass here and again when the next epoch starts."""
+  step = per_rank * world
+  if frames.shape[0] < step:
+    per_rank, step = max(frames.shape[0] // world, 1), max(frames.shape[0] // world, 1) * world
+  total, n = 0.0, 0
+  with scope():
+    for i in range(0, frames.shape[0] - step + 1, step):
+      for m in model.metrics:
+        m.reset_state()
+      sl = slice(i + rank * per_rank, i + (rank + 1) * per_rank)
+      total += float(model.test_step((frames[sl], cond[sl]) if cond is not None else frames[sl])['loss'])
+      n += 1
+  return total / max(n, 1)
 
 
 def main():
@@ -55,6 +78,7 @@ def main():
   if args.epochs is not None:
     config['epochs'] = args.epochs
 
+  import contextlib
   import torch.distributed as dist
   from wavenets_amd import WaveNet, Adam, MeanSquaredError, callbacks, data, io, ops
 
@@ -88,8 +112,20 @@ def main():
     parts = [data.preprocess_with_condition(w, int(l), ncls, L, config['apply_mulaw']) for w, l in zip(raw, labels)]
     frames = torch.cat([p[0] for p in parts], dim=0)
     cond = torch.cat([p[1] for p in parts], dim=0)
+    per_utterance = [p[0].shape[0] for p in parts]
   else:
-    frames = torch.cat([data.preprocess_waveform(w, L, config['apply_mulaw']) for w in raw], dim=0)
+    parts = [data.preprocess_waveform(w, L, config['apply_mulaw']) for w in raw]
+    frames = torch.cat(parts, dim=0)
+    per_utterance = [p.shape[0] for p in parts]
+  n_val = int(config['validation_utterances'])
+  val_frames = val_cond = None
+  if n_val > 0:                                                     # frames are in utterance order: the tail is held out
+    held = sum(per_utterance[-n_val:])
+    if n_val >= raw.shape[0] or held < world:
+      raise SystemExit('validation_utterances must hold a frame per GPU and leave utterances to train on')
+    val_frames, frames = frames[-held:], frames[:-held]
+    if conditioned:
+      val_cond, cond = cond[-held:], cond[:-held]
   per_rank = config['batch_size'] // world
   if per_rank < 1 or frames.shape[0] < config['batch_size']:
     raise SystemExit('not enough data for one global batch')
@@ -109,7 +145,9 @@ def main():
   if conditioned:                                                  # Keras builds on the first call (train.py:232-235):
     model.build([(per_rank, L, 1), (per_rank, cond.shape[1])])    # the condition width fixes the mapping net's shapes
   opt = Adam(learning_rate=config['lr'], clipnorm=1.0,           # train.py:225-226
-             clip_before_reduce=config['clip_before_reduce'])
+             clip_before_reduce=config['clip_before_reduce'], use_ema=config['use_ema'],
+             ema_momentum=config['ema_momentum'], ema_overwrite_frequency=config['ema_overwrite_frequency'])
+  averaged = model.averaged_weights if config['use_ema'] else contextlib.nullcontext
   model.compile(optimizer=opt, metrics=[MeanSquaredError()])          # train.py:225-228
   print('Receptive field') if rank == 0 else None
   if rank == 0:
@@ -150,6 +188,9 @@ def main():
         stop = True
         break
     loss = model.loss_tracker.result()
+    val_loss = None
+    if val_frames is not None and not stop:                         # every rank: test_step reduces over the replicas
+      val_loss = validate(model, val_frames, val_cond, per_rank, rank, world, averaged)
     if rank == 0:
       sps = n_batches * config['batch_size'] * L / max(time.time() - t0, 1e-9)
       extra = ''.join(f' - {k}: {v:.4f}' for k, v in logs.items() if k != 'loss')   # the compiled metrics, as Keras logs them
@@ -157,6 +198,7 @@ def main():
       # ~2.7x slower step): shown only when there were any
       trips = model.train_guard_trips - trips0
       extra += f' - exact-fp32 repeats: {trips}' if trips else ''
+      extra += f' - val_loss: {val_loss:.4f}' if val_loss is not None else ''
       print(f'Epoch {epoch + 1}/{config["epochs"]} - loss: {loss:.4f}{extra} - lr: {opt.learning_rate:g} - {sps:,.0f} samples/s')
       if loss < best:                                               # ModelCheckpoint(save_best_only, monitor='loss')
         best = loss
@@ -172,16 +214,21 @@ def main():
   if rank == 0:
     tic = time.time()
     nprev = min(config['batch_size'], 8)
-    samples = model.generate(preview, batch_size=nprev, condition=cond[:nprev] if conditioned else None,
-                             use_queues=config['layers_per_block'] == 1,
-                             temperature=float(config['preview_temperature']), top_k=int(config['preview_top_k']),
-                             seed=None if config['preview_seed'] is None else int(config['preview_seed']))
+    with averaged():
+      samples = model.generate(preview, batch_size=nprev, condition=cond[:nprev] if conditioned else None,
+                               use_queues=config['layers_per_block'] == 1,
+                               temperature=float(config['preview_temperature']), top_k=int(config['preview_top_k']),
+                               seed=None if config['preview_seed'] is None else int(config['preview_seed']))
     torch.cuda.synchronize()
     tictoc = time.time() - tic
     print(f'Generation took {tictoc}s')
     print(f'Speed of generation was {preview / tictoc} samples/s')
     if config['apply_mulaw']:
       samples = ops.inverse_mu_law(samples)
+    if config['use_ema']:                     # the averaged weights as a Keras exchange file; not a resume candidate
+      os.makedirs(run_dir, exist_ok=True)
+      with averaged():
+        io.save_weights(model, os.path.join(run_dir, 'averaged.weights.h5'))
     out_dir = os.path.join(run_dir, 'samples')
     os.makedirs(out_dir, exist_ok=True)
     arr = samples.cpu().numpy()

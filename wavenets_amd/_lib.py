@@ -101,6 +101,8 @@ _SIGS = {
                                C.c_float, _P, _P]),
     'wn_adam_step_guarded': (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_float, _P, _P, _P]),
+    'wn_adam_step_ema': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
+                                   C.c_float, C.c_float, C.c_int32, _P, _P, _P]),
     'wn_clip_gradients': (C.c_int, [_P, _P, C.c_float, _P, _P]),
     'wn_plan_range_slot': (C.c_int64, [_P, C.c_int32, C.c_int32, C.c_int32]),
     'wn_range_limit': (C.c_float, []),

@@ -105,7 +105,8 @@ def write_wav(path, waveform, sampling_frequency):
 class SoundCallback:
   """src/callbacks.py:4-118: generate at the end of every `epoch_frequency`-th epoch, from noise and (if
   given) from an initial sample; `use_fast='both'` produces the queued and the sliding-window result
-  side by side (the reference's A/B hook for its queue TODO)."""
+  side by side (the reference's A/B hook for its queue TODO).  Under Adam(use_ema=True) the dumps are generated from the
+  averaged weights (WaveNet.averaged_weights())."""
 
   def __init__(self, log_dir, sampling_frequency: int, samples: int, apply_mulaw: bool, epoch_frequency: int = 1,
                condition=None, use_fast=False, initial_sample=None, model=None, temperature=1.0, top_k=0, seed=None):
@@ -129,11 +130,18 @@ class SoundCallback:
     self.model = model
 
   def on_epoch_end(self, epoch, logs=None):
-    import os
-    import numpy as np
+    import contextlib
     del logs
     if epoch % self.log_freq != self.log_freq - 1:
       return None
+    opt = getattr(self.model, 'optimizer', None)
+    averaged = getattr(opt, 'use_ema', False) and getattr(self.model, '_averaged', None) is None
+    with self.model.averaged_weights() if averaged else contextlib.nullcontext():
+      return self._dump(epoch)
+
+  def _dump(self, epoch):
+    import os
+    import numpy as np
     modes = [('fast', True), ('standard', False)] if self.use_fast == 'both' else [('standard', self.use_fast)]
     generated = {}
     controls = dict(temperature=self.temperature, top_k=self.top_k, seed=self.seed)

@@ -869,6 +869,47 @@ int wn_launch_adam(float* p, const float* g, float* m, float* v, const WnTensorD
   return WN_OK;
 }
 
+// Adam(use_ema=True): the same update with the exponential moving average of the weights as one more stream of the same
+// launch -- a sibling of wn_adam_kernel picked by the host, so the default step runs the kernel above unchanged.  g, m, v
+// and p are evaluated with the expressions of wn_adam_kernel (the average observes, it never feeds back, unless
+// ``overwrite`` asks for p = a); a follows in the form m and v use: a + (p - a) * (1 - momentum), fp32.  ``first`` (step 1)
+// copies p instead: a multiply by zero would keep a NaN / inf of the initial average.  9 floats moved per parameter, 7
+// above; scalar accesses, since tensors start at arbitrary float offsets.
+__global__ void wn_adam_ema_kernel(float* p, const float* g, float* m, float* v, float* a, const WnTensorDesc* table,
+                                   const float* norms2, float clipnorm, float alpha, float beta1,
+                                   float beta2, float eps, float momentum, int first, int overwrite,
+                                   const float* skip_flag) {
+  if (skip_flag && *skip_flag != 0.f) return;     // range guard tripped: a stays put together with p, m, v (uniform)
+  const WnTensorDesc d = table[blockIdx.y];
+  float scale = 1.0f;
+  if (clipnorm > 0.f) {
+    const float nrm = sqrtf(norms2[blockIdx.y]);
+    scale = clipnorm / fmaxf(nrm, clipnorm);     // tf.clip_by_norm
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.len;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = d.off + i;
+    const float gi = g[k] * scale;
+    const float mi = m[k] + (gi - m[k]) * (1.0f - beta1);
+    const float vi = v[k] + (gi * gi - v[k]) * (1.0f - beta2);
+    m[k] = mi;
+    v[k] = vi;
+    const float pi = p[k] - alpha * mi / (sqrtf(vi) + eps);
+    const float ai = first ? pi : a[k] + (pi - a[k]) * (1.0f - momentum);
+    a[k] = ai;
+    p[k] = overwrite ? ai : pi;
+  }
+}
+int wn_launch_adam_ema(float* p, const float* g, float* m, float* v, float* a, const WnTensorDesc* d_table, int n,
+                       const float* norms2, float clipnorm, float alpha, float beta1, float beta2,
+                       float eps, float momentum, int first, int overwrite, const float* skip_flag, hipStream_t s) {
+  if (n <= 0) return WN_OK;
+  hipLaunchKernelGGL(wn_adam_ema_kernel, dim3(32, n), dim3(256), 0, s, p, g, m, v, a, d_table, norms2,
+                     clipnorm, alpha, beta1, beta2, eps, momentum, first, overwrite, skip_flag);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // gate of the composed (unfused) block path: u (rows, 2D) -> a = tanh(u[:, :D]), g = sigmoid(u[:, D:]),
 // z = a * g   (src/layers.py:208-210)

@@ -413,3 +413,7 @@ int wn_launch_axpy_table(float* y, const float* x, const WnTensorDesc* d_table, 
 int wn_launch_adam(float* p, const float* g, float* m, float* v, const WnTensorDesc* d_table, int n,
                    const float* norms2, float clipnorm, float alpha, float beta1, float beta2,
                    float eps, const float* skip_flag, hipStream_t s);
+// the same step with the weights' exponential moving average a as one more stream (Adam(use_ema=True)); first: a = p
+int wn_launch_adam_ema(float* p, const float* g, float* m, float* v, float* a, const WnTensorDesc* d_table, int n,
+                       const float* norms2, float clipnorm, float alpha, float beta1, float beta2,
+                       float eps, float momentum, int first, int overwrite, const float* skip_flag, hipStream_t s);

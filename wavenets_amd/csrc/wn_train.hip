@@ -772,6 +772,28 @@ extern "C" int wn_adam_step_guarded(wn_plan* p, float* params, const float* grad
   return wn_launch_adam(params, grads, m, v, p->d_tdesc, n, scratch, clipnorm, (float)alpha, beta1, beta2, eps, skip_flag, s);
 }
 
+extern "C" int wn_adam_step_ema(wn_plan* p, float* params, const float* grads, float* m, float* v, float* ema, int64_t step,
+                                float lr, float beta1, float beta2, float eps, float clipnorm, float ema_momentum,
+                                int32_t ema_overwrite, float* scratch, const float* skip_flag, void* stream) {
+  if (!p || !params || !grads || !m || !v || !ema || !scratch || step < 1) { wn_set_error("adam_step_ema: bad arguments"); return WN_E_INVALID; }
+  if (!std::isfinite(ema_momentum) || ema_momentum < 0.f || ema_momentum > 1.f) {
+    wn_set_error("adam_step_ema: ema_momentum must be finite and in [0, 1] (got %g)", (double)ema_momentum);
+    return WN_E_INVALID;
+  }
+  if (ema_overwrite != 0 && ema_overwrite != 1) { wn_set_error("adam_step_ema: ema_overwrite must be 0 or 1 (got %d)", (int)ema_overwrite); return WN_E_INVALID; }
+  hipStream_t s = (hipStream_t)stream;
+  int rc = ensure_device_tables(p);
+  if (rc) return rc;
+  const int n = (int)p->tdesc.size();
+  if (clipnorm > 0.f) {
+    rc = wn_launch_sumsq(grads, p->d_tdesc, n, scratch, s);
+    if (rc) return rc;
+  }
+  const double alpha = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
+  return wn_launch_adam_ema(params, grads, m, v, ema, p->d_tdesc, n, scratch, clipnorm, (float)alpha, beta1, beta2, eps,
+                            ema_momentum, step == 1 ? 1 : 0, (int)ema_overwrite, skip_flag, s);
+}
+
 extern "C" int wn_clip_gradients(wn_plan* p, float* grads, float clipnorm, float* scratch, void* stream) {
   if (!p || !grads || !scratch) { wn_set_error("clip_gradients: bad arguments"); return WN_E_INVALID; }
   if (!(clipnorm > 0.f) || !std::isfinite(clipnorm)) { wn_set_error("clip_gradients: clipnorm must be finite and > 0 (got %g)", (double)clipnorm); return WN_E_INVALID; }

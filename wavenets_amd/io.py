@@ -131,12 +131,16 @@ def save_weights(model, path: str, optimizer=None) -> None:
       if os.path.exists(tmp):
         os.remove(tmp)
     return
+  if optimizer is not None and getattr(model, '_averaged', None) is not None:
+    raise RuntimeError('save_weights(..., optimizer) inside averaged_weights(): a training checkpoint holds the raw weights')
   arrays = {f'w{i:03d}': w for i, w in enumerate(model.get_weights())}
   arrays['names'] = np.array(model.variable_names)
   if optimizer is not None and optimizer.m is not None:
     arrays['adam_m'] = optimizer.m.detach().cpu().numpy()
     arrays['adam_v'] = optimizer.v.detach().cpu().numpy()
     arrays['adam_iterations'] = np.int64(optimizer.iterations)
+    if getattr(optimizer, 'ema', None) is not None:          # Adam(use_ema=True): the weights' moving average
+      arrays['adam_ema'] = optimizer.ema.detach().cpu().numpy()
   if getattr(model, 'dropout', 0) > 0:
     arrays['drop_step'] = np.int64(getattr(model, '_drop_step', 0))
   # write beside the target and rename: a kill mid-write must not leave a truncated file that sorts last and
@@ -167,6 +171,12 @@ def load_weights(model, path: str, optimizer=None) -> None:
       optimizer.m.copy_(torch.from_numpy(d['adam_m']).to(optimizer.m.device))
       optimizer.v.copy_(torch.from_numpy(d['adam_v']).to(optimizer.v.device))
       optimizer.iterations = int(d['adam_iterations'])
+    if optimizer is not None and getattr(optimizer, 'use_ema', False):
+      optimizer.build(model)
+      if 'adam_ema' in d:
+        optimizer.ema.copy_(torch.from_numpy(d['adam_ema']).to(optimizer.ema.device))
+      else:                                    # a checkpoint without an average: it starts from the loaded weights
+        optimizer.ema.copy_(model.flat_params.data)
     if 'drop_step' in d and hasattr(model, 'set_drop_step'):
       model.set_drop_step(int(d['drop_step']))
 

@@ -141,6 +141,7 @@ class WaveNet(torch.nn.Module):
     self._ws = {}
     self.built = False
     self.optimizer = None
+    self._averaged = None                 # inside averaged_weights(): the raw weights' storage, swapped out of flat_params
     self._metrics_from_compilation = []
     self.loss_tracker = _Mean('loss')
     self.reg_loss = _Mean('reg_loss') if self.regularization else None
@@ -296,6 +297,7 @@ class WaveNet(torch.nn.Module):
     return [t.detach().cpu().numpy().copy() for t in self.trainable_variables]
 
   def set_weights(self, weights):
+    self._not_averaged('set_weights')
     if len(weights) != len(self._names):
       raise ValueError(f'expected {len(self._names)} arrays, got {len(weights)}')
     for t, w in zip(self.trainable_variables, weights):
@@ -303,6 +305,37 @@ class WaveNet(torch.nn.Module):
       if tuple(w.shape) != tuple(t.shape):
         raise ValueError(f'shape mismatch {tuple(w.shape)} vs {tuple(t.shape)}')
       t.copy_(w)
+
+  def _not_averaged(self, what):
+    if self._averaged is not None:
+      raise RuntimeError(f'{what} inside averaged_weights(): the scope runs on the averaged weights and is read-only')
+
+  def averaged_weights(self):
+    """Context manager (Adam(use_ema=True)): inside it every pass -- call, logits, test_step, generate, get_weights,
+    io.save_weights(model, '*.weights.h5') -- runs on the optimizer's exponential moving average of the weights.  The
+    storage behind ``flat_params`` is swapped for the average (every pass takes the parameters as a pointer and rebuilds
+    its weight images from it on each call): no copy, no second plan.  On exit, also through an exception, the raw
+    weights are back bit for bit.  Training, set_weights and training checkpoints raise RuntimeError inside it."""
+    import contextlib
+
+    @contextlib.contextmanager
+    def _cm():
+      opt = self.optimizer
+      if opt is None or not getattr(opt, 'use_ema', False):
+        raise RuntimeError('averaged_weights() needs compile(optimizer=Adam(use_ema=True))')
+      self._not_averaged('averaged_weights()')
+      if not self.built:
+        raise RuntimeError('averaged_weights(): the model is not built yet')
+      opt.build(self)
+      raw = self.flat_params.data
+      self._averaged = raw
+      self.flat_params.data = opt.ema
+      try:
+        yield self
+      finally:
+        self.flat_params.data = raw
+        self._averaged = None
+    return _cm()
 
   def gradients(self):
     """Gradient views matching trainable_variables (after train_step / loss_and_grads)."""
@@ -470,6 +503,7 @@ class WaveNet(torch.nn.Module):
     ``sample_waveform(pred)`` (src/model.py:338) from the logits inside the library -- same draw, no (B,T,C)
     probability tensor -- and returns it in place of pred; when the library cannot (deterministic / more than
     1024 classes) pred is returned and the caller samples from it."""
+    self._not_averaged('loss_and_grads')
     x, cond = self._split_inputs(data)
     B, T = x.shape[0], x.shape[1] - 1
     if T < 1:
@@ -530,6 +564,7 @@ class WaveNet(torch.nn.Module):
     counts those repeats (a tripped step costs a second, ~2.7x slower one)."""
     if self.optimizer is None:
       raise RuntimeError('compile(optimizer=...) first')
+    self._not_averaged('train_step')
     lv, pending, y_true, sample = self._train_step_once(data)
     if lv[2] > 0:                                    # tripped on some replica -> on all of them after the SUM
       self.train_guard_trips += 1
