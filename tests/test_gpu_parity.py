@@ -339,6 +339,30 @@ def test_loss_and_gradients_parity(name, math_mode):
     assert err < 1e-4 * scale + 1e-7, (n, err, scale)
 
 
+@pytest.mark.parametrize('bits', [5, 8])
+def test_categorical_loss_repeated_utterance_rows_bit_exact(bits, math_mode):
+  """One utterance stacked twice, B * T = 8230 rows: more than the 4 * 2048 rows the persistent waves of the <= 256-class
+  loss kernel take first, so rows 8192.. are a wave's SECOND row, worked on with a prefetch in flight, while their twins
+  4077.. of utterance 0 are first rows (exact fp32; in split mode the fused loss epilogue tiles the same rows).  The
+  network is causal and row-independent and gscale is one kernel argument: dL/dlogits of both utterances is the same
+  bits, no tolerance."""
+  from wavenets_amd import WaveNet
+  finals = [32]
+  kw = dict(blocks=3, channels=32, skip_channels=32, dilation_bound=4, final_layers_channels=finals, bits=bits)
+  model = WaveNet(**kw, device=dev())
+  model.set_weights([p.numpy() for p in O.init_params(O.OracleConfig(**kw), seed=6)])
+  one = O.synthetic_waveform(1, 4116, seed=12).to(dev())
+  B, T, C = 2, 4115, 1 << bits
+  assert B * T > 4 * 2048
+  loss2, _, _ = model.loss_and_grads(torch.cat([one, one], 0), global_batch=2, n_replicas=1)
+  g = model.training_intermediate(6, len(finals), B, T).reshape(B, T, C).clone()
+  assert g.abs().max().item() > 0
+  assert torch.equal(g[1], g[0])
+  loss1, _, _ = model.loss_and_grads(one, global_batch=2, n_replicas=2)
+  assert loss2[2].item() == 0 and loss1[2].item() == 0
+  assert abs(loss2[0].item() - 2 * loss1[0].item()) < 1e-5 * abs(2 * loss1[0].item())
+
+
 def test_l2_regulariser():
   kw = dict(MODEL_CASES['cat_small_fused'], l2_reg_factor=0.01)
   ocfg, params, model = make_pair(seed=4, **kw)

@@ -107,7 +107,7 @@ def test_queued_equals_sliding_window_mixture_head_in_one_launch(channels, sampl
 
 @pytest.mark.parametrize('T', MIX_T)
 def test_queued_equals_sliding_window_mixture_sampler_launch(T):
-  """'mol': the head's layers as separate launches, mixture sampler + emit in one (wn_sample_rand_mix_ctl_kernel)."""
+  """'mol': the head's layers as separate launches, mixture sampler + emit in one (wn_sample_rand_mix_kernel<true>)."""
   ocfg, params, model = make_pair(seed=11, bias_range=0.3, **dict(MODEL_CASES['mol']))
   naive, queued, plain = _both_forms(model, 14, 5, 12, temperature=T)
   assert torch.equal(naive, queued), (naive - queued).abs().max()

@@ -189,6 +189,14 @@ __device__ __forceinline__ void wn_guard_publish_over(float* slot, float wmax) {
   }
 }
 
+// grid of a grid-stride launch: one workgroup per `per` elements, at most `cap`
+static inline int wn_blocks(int64_t n, int per = 256, int cap = 4096) {
+  int64_t b = (n + per - 1) / per;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
 void wn_set_error(const char* fmt, ...);
 int wn_debug_get(int key);   // per-thread switches (wn_error.cpp): 1 = exact-fp32 kernels, 9 = no side stream, 24 / 29 = profiling hooks
 

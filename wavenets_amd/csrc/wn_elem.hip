@@ -1,18 +1,10 @@
-// Elementwise, loss, sampling and reduction kernels of the WaveNet hot path (gfx950).
-// References: quantiser src/model.py:151-153; mu-law src/utils.py:34-35; inverse
-// src/callbacks.py:126-131; losses src/model.py:505-551; samplers src/model.py:393-503.
+// Elementwise, optimizer and small dense kernels of the WaveNet hot path (gfx950); losses: wn_loss.hip, samplers:
+// wn_sample.hip.  References: quantiser src/model.py:151-153; mu-law src/utils.py:34-35; inverse
+// src/callbacks.py:126-131.
 #include <algorithm>
 
 #include "wn_kernels.h"
 #include "wn_sample.h"
-
-
-static inline int wn_blocks(int64_t n, int per = 256, int cap = 4096) {
-  int64_t b = (n + per - 1) / per;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
 
 // ------------------------------------------------------------------------------------------
 __global__ void wn_add_kernel(const float* a, const float* b, float* out, int64_t n) {
@@ -142,603 +134,6 @@ __global__ void wn_inv_mulaw_kernel(const float* y, float* x, int64_t n) {
 int wn_launch_inv_mulaw(const float* y, float* x, int64_t n, hipStream_t s) {
   if (n <= 0) return WN_OK;
   hipLaunchKernelGGL(wn_inv_mulaw_kernel, dim3(wn_blocks(n)), dim3(256), 0, s, y, x, n);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-__global__ __launch_bounds__(256) void wn_softmax_kernel(const float* logits, float* probs,
-                                                         int64_t rows, int C) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* l = logits + row * C;
-  float m = -INFINITY;
-  for (int j = lane; j < C; j += 64) m = fmaxf(m, l[j]);
-  m = wn_wave_max(m);
-  float z = 0.f;
-  for (int j = lane; j < C; j += 64) z += expf(l[j] - m);
-  z = wn_wave_sum(z);
-  const float inv = 1.0f / z;
-  for (int j = lane; j < C; j += 64) probs[row * C + j] = expf(l[j] - m) * inv;
-}
-int wn_launch_softmax(const float* logits, float* probs, int64_t rows, int C, hipStream_t s) {
-  if (rows <= 0) return WN_OK;
-  hipLaunchKernelGGL(wn_softmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits,
-                     probs, rows, C);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// Keras sparse_categorical_crossentropy(target, softmax(logits)), from_logits=False:
-//   q = softmax(logits); p = clip(q, eps, 1-eps); loss = -(log p_t - log sum_j p_j)
-// and its gradient w.r.t. the logits (clip passes gradient where eps <= q <= 1-eps).
-// sample_out (C <= 256 only): also draw sample_waveform(softmax(logits)) of the row (src/model.py:338,407-411)
-// from the probabilities already in registers -- the values wn_softmax_kernel would write, the draw
-// wn_sample_rand_cat_kernel would make from them.
-// C <= 256, the shape of every BASELINE categorical head: persistent waves, one row at a time per wave with the NEXT row's
-// logits and target already requested (the one-row-per-wave launch below spends most of a row waiting for its loads:
-// 172 us for 268 MB).  Per row the arithmetic is exactly that of wn_cat_loss_kernel's C <= 256 branch -- the target's
-// probability comes from the lane that holds it instead of a second, dependent load of the same logit -- and the max-abs
-// of the gradients is published once per wave.
-__global__ __launch_bounds__(256) void wn_cat_loss256_kernel(const float* logits, const int32_t* target,
-                                                             int64_t rows, int C, float gscale,
-                                                             float* loss_rows, float* g_logits, float* absmax_out,
-                                                             float* sample_out, float inv_lv, uint64_t seed, uint64_t offset) {
-  __shared__ float qs[4][256];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t stride = (int64_t)gridDim.x * 4;
-  int64_t row = (int64_t)blockIdx.x * 4 + w;
-  float vn[4];
-  int tn = 0;
-  auto fetch = [&](int64_t r) {
-    const float* l = logits + r * C;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) vn[k] = lane + 64 * k < C ? l[lane + 64 * k] : -INFINITY;
-    tn = target[r];
-  };
-  if (row < rows) fetch(row);
-  float gmax = 0.f;
-  for (; row < rows; row += stride) {
-    float v[4], e[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = vn[k];
-    int tgt = tn;
-    if (row + stride < rows) fetch(row + stride);     // in flight while this row is worked on
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) m = fmaxf(m, v[k]);
-    m = wn_wave_max(m);
-    float z = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      e[k] = lane + 64 * k < C ? expf(v[k] - m) : 0.f;
-      if (lane + 64 * k < C) z += e[k];
-    }
-    z = wn_wave_sum(z);
-    const float inv = 1.0f / z;
-    if (sample_out) {
-      float* qw = qs[w];
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (lane + 64 * k < C) qw[lane + 64 * k] = e[k] * inv;
-      __builtin_amdgcn_wave_barrier();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const int drawn = wn_draw_cat_row((const float*)qw, C, lane, row, seed, offset);
-      if (lane == 0) sample_out[row] = (float)drawn * inv_lv - 1.0f;
-      __builtin_amdgcn_wave_barrier();                // the next row rewrites qw
-    }
-    float S = 0.f, A = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (lane + 64 * k < C) {
-        const float q = e[k] * inv;
-        S += fminf(fmaxf(q, WN_KERAS_EPS), 1.0f - WN_KERAS_EPS);
-        if (q >= WN_KERAS_EPS && q <= 1.0f - WN_KERAS_EPS) A += q;
-      }
-    S = wn_wave_sum(S);
-    A = wn_wave_sum(A);
-    tgt = tgt < 0 ? 0 : (tgt >= C ? C - 1 : tgt);
-    const int tk = tgt >> 6;                          // wave-uniform: the lane tgt & 63 holds e[tk] = exp(l[tgt] - m)
-    const float et = __shfl(tk == 0 ? e[0] : tk == 1 ? e[1] : tk == 2 ? e[2] : e[3], tgt & 63);
-    const float qt = et * inv;
-    const float pt = fminf(fmaxf(qt, WN_KERAS_EPS), 1.0f - WN_KERAS_EPS);
-    const float ct = (qt >= WN_KERAS_EPS && qt <= 1.0f - WN_KERAS_EPS) ? 1.f : 0.f;
-    if (lane == 0) loss_rows[row] = -(logf(pt) - logf(S));
-    if (g_logits) {
-      const float invS = 1.0f / S;
-      const float dot = A * invS - ct * qt / pt;     // sum_j g_j q_j
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int j = lane + 64 * k;
-        if (j < C) {
-          const float q = e[k] * inv;
-          const float c = (q >= WN_KERAS_EPS && q <= 1.0f - WN_KERAS_EPS) ? 1.f : 0.f;
-          float g = c * invS;
-          if (j == tgt) g -= ct / pt;
-          const float gl = gscale * q * (g - dot);
-          g_logits[row * C + j] = gl;
-          gmax = fmaxf(gmax, fabsf(gl));
-        }
-      }
-    }
-  }
-  if (g_logits && absmax_out) {
-    gmax = wn_wave_max(gmax);
-    if (lane == 0) wn_absmax_publish(absmax_out, gmax);
-  }
-}
-
-__global__ __launch_bounds__(256) void wn_cat_loss_kernel(const float* logits, const int32_t* target,
-                                                          int64_t rows, int C, float gscale,
-                                                          float* loss_rows, float* g_logits, float* absmax_out,
-                                                          float* sample_out, float inv_lv, uint64_t seed, uint64_t offset) {
-  __shared__ float qs[4][256];
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* l = logits + row * C;
-  if (C <= 256) {
-    // the row lives in registers (element k of a lane = class lane + 64 k, the same assignment and the
-    // same per-lane summation order as the general path below): one read of the logits, one exp per class
-    float v[4], e[4];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int j = lane + 64 * k;
-      v[k] = j < C ? l[j] : -INFINITY;
-      m = fmaxf(m, v[k]);
-    }
-    m = wn_wave_max(m);
-    float z = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      e[k] = lane + 64 * k < C ? expf(v[k] - m) : 0.f;
-      if (lane + 64 * k < C) z += e[k];
-    }
-    z = wn_wave_sum(z);
-    const float inv = 1.0f / z;
-    if (sample_out) {
-      float* qw = qs[threadIdx.x >> 6];
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (lane + 64 * k < C) qw[lane + 64 * k] = e[k] * inv;
-      __builtin_amdgcn_wave_barrier();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const int drawn = wn_draw_cat_row((const float*)qw, C, lane, row, seed, offset);
-      if (lane == 0) sample_out[row] = (float)drawn * inv_lv - 1.0f;
-    }
-    float S = 0.f, A = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (lane + 64 * k < C) {
-        const float q = e[k] * inv;
-        S += fminf(fmaxf(q, WN_KERAS_EPS), 1.0f - WN_KERAS_EPS);
-        if (q >= WN_KERAS_EPS && q <= 1.0f - WN_KERAS_EPS) A += q;
-      }
-    S = wn_wave_sum(S);
-    A = wn_wave_sum(A);
-    int tgt = target[row];
-    tgt = tgt < 0 ? 0 : (tgt >= C ? C - 1 : tgt);
-    const float qt = expf(l[tgt] - m) * inv;
-    const float pt = fminf(fmaxf(qt, WN_KERAS_EPS), 1.0f - WN_KERAS_EPS);
-    const float ct = (qt >= WN_KERAS_EPS && qt <= 1.0f - WN_KERAS_EPS) ? 1.f : 0.f;
-    if (lane == 0) loss_rows[row] = -(logf(pt) - logf(S));
-    if (g_logits) {
-      float gmax = 0.f;
-      const float invS = 1.0f / S;
-      const float dot = A * invS - ct * qt / pt;     // sum_j g_j q_j
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int j = lane + 64 * k;
-        if (j < C) {
-          const float q = e[k] * inv;
-          const float c = (q >= WN_KERAS_EPS && q <= 1.0f - WN_KERAS_EPS) ? 1.f : 0.f;
-          float g = c * invS;
-          if (j == tgt) g -= ct / pt;
-          const float gl = gscale * q * (g - dot);
-          g_logits[row * C + j] = gl;
-          gmax = fmaxf(gmax, fabsf(gl));
-        }
-      }
-      if (absmax_out) {
-        gmax = wn_wave_max(gmax);
-        if (lane == 0) wn_absmax_publish(absmax_out, gmax);
-      }
-    }
-    return;
-  }
-  float m = -INFINITY;
-  for (int j = lane; j < C; j += 64) m = fmaxf(m, l[j]);
-  m = wn_wave_max(m);
-  float z = 0.f;
-  for (int j = lane; j < C; j += 64) z += expf(l[j] - m);
-  z = wn_wave_sum(z);
-  const float inv = 1.0f / z;
-  float S = 0.f, A = 0.f;
-  for (int j = lane; j < C; j += 64) {
-    const float q = expf(l[j] - m) * inv;
-    const float p = fminf(fmaxf(q, WN_KERAS_EPS), 1.0f - WN_KERAS_EPS);
-    S += p;
-    if (q >= WN_KERAS_EPS && q <= 1.0f - WN_KERAS_EPS) A += q;
-  }
-  S = wn_wave_sum(S);
-  A = wn_wave_sum(A);
-  int tgt = target[row];
-  tgt = tgt < 0 ? 0 : (tgt >= C ? C - 1 : tgt);
-  const float qt = expf(l[tgt] - m) * inv;
-  const float pt = fminf(fmaxf(qt, WN_KERAS_EPS), 1.0f - WN_KERAS_EPS);
-  const float ct = (qt >= WN_KERAS_EPS && qt <= 1.0f - WN_KERAS_EPS) ? 1.f : 0.f;
-  if (lane == 0) loss_rows[row] = -(logf(pt) - logf(S));
-  if (g_logits) {
-    float gmax = 0.f;
-    const float invS = 1.0f / S;
-    const float dot = A * invS - ct * qt / pt;     // sum_j g_j q_j
-    for (int j = lane; j < C; j += 64) {
-      const float q = expf(l[j] - m) * inv;
-      const float c = (q >= WN_KERAS_EPS && q <= 1.0f - WN_KERAS_EPS) ? 1.f : 0.f;
-      float g = c * invS;
-      if (j == tgt) g -= ct / pt;
-      const float gl = gscale * q * (g - dot);
-      g_logits[row * C + j] = gl;
-      gmax = fmaxf(gmax, fabsf(gl));
-    }
-    if (absmax_out) {
-      gmax = wn_wave_max(gmax);
-      if (lane == 0) wn_absmax_publish(absmax_out, gmax);
-    }
-  }
-}
-int wn_launch_cat_loss(const float* logits, const int32_t* target, int64_t rows, int C,
-                       float gscale, float* loss_rows, float* g_logits, float* absmax_out, hipStream_t s,
-                       float* sample_out, int bits, uint64_t seed, uint64_t offset) {
-  if (rows <= 0) return WN_OK;
-  if (sample_out && C > 256) { wn_set_error("cat_loss: the in-kernel sample draw needs <= 256 classes"); return WN_E_UNSUPPORTED; }
-  const float inv_lv = sample_out ? 1.0f / (float)(1 << (bits - 1)) : 0.f;
-  if (C <= 256) {
-    const int64_t wgs = std::min<int64_t>((rows + 3) / 4, 256 * 8);
-    hipLaunchKernelGGL(wn_cat_loss256_kernel, dim3((unsigned)wgs), dim3(256), 0, s, logits, target, rows, C, gscale,
-                       loss_rows, g_logits, absmax_out, sample_out, inv_lv, seed, offset);
-  } else {
-    hipLaunchKernelGGL(wn_cat_loss_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits,
-                       target, rows, C, gscale, loss_rows, g_logits, absmax_out, sample_out, inv_lv, seed, offset);
-  }
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-__global__ __launch_bounds__(256) void wn_cat_loss_probs_kernel(const float* probs,
-                                                                const int32_t* target, int64_t rows,
-                                                                int C, float* loss_rows) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* q = probs + row * C;
-  float S = 0.f;
-  for (int j = lane; j < C; j += 64) S += fminf(fmaxf(q[j], WN_KERAS_EPS), 1.0f - WN_KERAS_EPS);
-  S = wn_wave_sum(S);
-  int tgt = target[row];
-  tgt = tgt < 0 ? 0 : (tgt >= C ? C - 1 : tgt);
-  const float pt = fminf(fmaxf(q[tgt], WN_KERAS_EPS), 1.0f - WN_KERAS_EPS);
-  if (lane == 0) loss_rows[row] = -(logf(pt) - logf(S));
-}
-int wn_launch_cat_loss_probs(const float* probs, const int32_t* target, int64_t rows, int C,
-                             float* loss_rows, hipStream_t s) {
-  if (rows <= 0) return WN_OK;
-  hipLaunchKernelGGL(wn_cat_loss_probs_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
-                     probs, target, rows, C, loss_rows);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// mixture losses, one thread per (b,t) row; M <= 32.  Evaluated in double: with bits = 16 the
-// half-bin (src/model.py:538) is 7.6e-6, so sigmoid(a) - sigmoid(b) cancels ~5 digits and an
-// fp32 evaluation (the reference's own included) carries 1e-3..1e-2 relative noise per term.
-#define WN_MAXMIX 32
-__device__ __forceinline__ double wn_sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
-__global__ void wn_mix_loss_kernel(const float* pred, const float* y, int64_t rows, int M, int bits,
-                                   int kind, float gscale, float* loss_rows, float* g_pred, float* absmax_out) {
-  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= rows) return;
-  const float* p = pred + row * 3 * M;
-  const double yy = (double)y[row];
-  double w[WN_MAXMIX], comp[WN_MAXMIX];
-  double wm = -INFINITY;
-  for (int k = 0; k < M; ++k) wm = fmax(wm, (double)p[k]);
-  double wz = 0.0;
-  for (int k = 0; k < M; ++k) { w[k] = exp((double)p[k] - wm); wz += w[k]; }
-  const double winv = 1.0 / wz;
-  const double halfbit = 0.5 / (double)(1 << bits);                      // src/model.py:538
-  const double sqrt2pi = sqrt(2.0 * 3.14159265359);                      // src/model.py:9
-  double lik = 0.0;
-  for (int k = 0; k < M; ++k) {
-    w[k] *= winv;
-    const double mu = (double)p[M + k];
-    const double ls = fmax((double)p[2 * M + k], -7.0);
-    if (kind == 1) {
-      const double inv = exp(-ls);
-      comp[k] = wn_sigmoid_d((yy - mu + halfbit) * inv) - wn_sigmoid_d((yy - mu - halfbit) * inv);
-    } else {
-      const double sc = exp(ls);
-      const double xx = fmin((yy - mu) / sc, 1e8);
-      comp[k] = exp(-0.5 * xx * xx) / (sc * sqrt2pi);
-    }
-    lik += w[k] * comp[k];
-  }
-  loss_rows[row] = (float)(-log(lik));
-  if (!g_pred) return;
-  float* g = g_pred + row * 3 * M;
-  const double dl = -(double)gscale / lik;                               // dL/dlik
-  for (int k = 0; k < M; ++k) {
-    const double mu = (double)p[M + k];
-    const double lsr = (double)p[2 * M + k];
-    const double ls = fmax(lsr, -7.0);
-    const double lsmask = lsr >= -7.0 ? 1.0 : 0.0;
-    g[k] = (float)(dl * (w[k] * comp[k] - w[k] * lik));
-    if (kind == 1) {
-      const double inv = exp(-ls);
-      const double a = (yy - mu + halfbit) * inv, b = (yy - mu - halfbit) * inv;
-      const double sa = wn_sigmoid_d(a), sb = wn_sigmoid_d(b);
-      const double da = sa * (1.0 - sa), db = sb * (1.0 - sb);
-      g[M + k] = (float)(dl * (-w[k] * inv * (da - db)));
-      g[2 * M + k] = (float)(dl * lsmask * (-w[k] * (a * da - b * db)));
-    } else {
-      const double sc = exp(ls);
-      const double xr = (yy - mu) / sc;
-      const double xx = fmin(xr, 1e8);
-      const double xmask = xr <= 1e8 ? 1.0 : 0.0;
-      const double pdf = comp[k];
-      // d pdf/d mu = pdf * xx / sc ; d pdf/d ls = pdf * (xx^2 - 1)
-      g[M + k] = (float)(dl * w[k] * pdf * xx / sc * xmask);
-      g[2 * M + k] = (float)(dl * lsmask * w[k] * pdf * (xx * xx * xmask - 1.0));
-    }
-  }
-  if (absmax_out) {
-    float gmax = 0.f;
-    for (int k = 0; k < 3 * M; ++k) gmax = fmaxf(gmax, fabsf(g[k]));
-    wn_absmax_publish(absmax_out, gmax);
-  }
-}
-int wn_launch_mix_loss(const float* pred, const float* y, int64_t rows, int M, int bits, int kind,
-                       float gscale, float* loss_rows, float* g_pred, float* absmax_out, hipStream_t s) {
-  if (rows <= 0) return WN_OK;
-  if (M < 1 || M > WN_MAXMIX) { wn_set_error("mix_loss: num_mixtures %d unsupported (max %d)", M, WN_MAXMIX); return WN_E_UNSUPPORTED; }
-  hipLaunchKernelGGL(wn_mix_loss_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, pred,
-                     y, rows, M, bits, kind, gscale, loss_rows, g_pred, absmax_out);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// deterministic two-stage sum (double accumulation), out[0] = scale * sum(v)
-__global__ void wn_sum_stage1(const float* v, int64_t n, double* scratch) {
-  __shared__ double sm[256];
-  double acc = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    acc += (double)v[i];
-  sm[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) scratch[blockIdx.x] = sm[0];
-}
-__global__ void wn_sum_stage2(const double* scratch, int nb, float scale, float* out) {
-  __shared__ double sm[256];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nb; i += blockDim.x) acc += scratch[i];
-  sm[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)(sm[0] * (double)scale);
-}
-// scratch: >= 1024 doubles (8 KiB)
-int wn_launch_sum(const float* v, int64_t n, float scale, float* out, float* scratch, hipStream_t s) {
-  int nb = wn_blocks(n, 256, 1024);
-  hipLaunchKernelGGL(wn_sum_stage1, dim3(nb), dim3(256), 0, s, v, n, reinterpret_cast<double*>(scratch));
-  hipLaunchKernelGGL(wn_sum_stage2, dim3(1), dim3(256), 0, s, reinterpret_cast<const double*>(scratch), nb, scale, out);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// out[0] = scale * sum((a - b)^2): tf.keras.metrics.MeanSquaredError(y_true, sample) of a step (src/model.py:346,
-// train.py:227) with scale = 1 / (n * replicas); same two-stage double accumulation as wn_launch_sum
-__global__ void wn_sqdiff_stage1(const float* a, const float* b, int64_t n, double* scratch) {
-  __shared__ double sm[256];
-  double acc = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float d = a[i] - b[i];
-    acc += (double)(d * d);
-  }
-  sm[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) scratch[blockIdx.x] = sm[0];
-}
-int wn_launch_sqdiff_sum(const float* a, const float* b, int64_t n, float scale, float* out, float* scratch, hipStream_t s) {
-  int nb = wn_blocks(n, 256, 1024);
-  hipLaunchKernelGGL(wn_sqdiff_stage1, dim3(nb), dim3(256), 0, s, a, b, n, reinterpret_cast<double*>(scratch));
-  hipLaunchKernelGGL(wn_sum_stage2, dim3(1), dim3(256), 0, s, reinterpret_cast<const double*>(scratch), nb, scale, out);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// samplers
-// (queued generation: the sample also goes to its place in the output rows and into the network's input ring -- the
-// emit step of a generation step rides in the sampler's launch)
-__device__ __forceinline__ void wn_emit_sample(const WnEmit& e, int64_t row, float v) {
-  if (!e.out) return;
-  e.out[row * e.length + e.step] = v;
-  if (e.xin_slot) e.xin_slot[row] = v;
-}
-__global__ __launch_bounds__(256) void wn_sample_det_cat_kernel(const float* pred, int64_t rows, int C,
-                                                                float inv, float* out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* p = pred + row * C;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int j = lane; j < C; j += 64) {
-    const float v = p[j];
-    if (v > best) { best = v; bi = j; }          // strictly greater keeps the first maximum
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o);
-    const int oi = __shfl_xor(bi, o);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if (lane == 0) out[row] = (float)bi * inv - 1.0f;
-}
-__global__ void wn_sample_det_mix_kernel(const float* pred, int64_t rows, int M, float* out, WnEmit em) {
-  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= rows) return;
-  const float v = wn_mix_det_row(pred + row * 3 * M, M);
-  out[row] = v;
-  wn_emit_sample(em, row, v);
-}
-int wn_launch_sample_det(const float* pred, int64_t rows, int C, int M, int bits, float* out,
-                         hipStream_t s) {
-  return wn_launch_sample_det_emit(pred, rows, C, M, bits, out, WnEmit{nullptr, 0, 0, nullptr}, s);
-}
-// (categorical rows with an emit target go through wn_launch_gen_tail_cat_det, which starts from the logits)
-int wn_launch_sample_det_emit(const float* pred, int64_t rows, int C, int M, int bits, float* out, WnEmit em, hipStream_t s) {
-  if (rows <= 0) return WN_OK;
-  if (M <= 0 && em.out) { wn_set_error("sample_det_emit: categorical rows use the fused tail"); return WN_E_INVALID; }
-  if (M <= 0) {
-    hipLaunchKernelGGL(wn_sample_det_cat_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
-                       pred, rows, C, 1.0f / (float)(1 << (bits - 1)), out);
-  } else {
-    hipLaunchKernelGGL(wn_sample_det_mix_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
-                       s, pred, rows, M, out, em);
-  }
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-__global__ __launch_bounds__(256) void wn_sample_rand_cat_kernel(const float* pred, int64_t rows, int C,
-                                                                 float inv, uint64_t seed, uint64_t offset,
-                                                                 float* out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int result = wn_draw_cat_row(pred + row * C, C, lane, row, seed, offset);
-  if (lane == 0) out[row] = (float)result * inv - 1.0f;
-}
-
-// ... under the sampling controls: the draw from the tempered / truncated view of the same row
-__global__ __launch_bounds__(256) void wn_sample_rand_cat_ctl_kernel(const float* pred, int64_t rows, int C,
-                                                                     float inv, uint64_t seed, uint64_t offset,
-                                                                     float* out, WnSampleCtl ctl) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int result = wn_draw_cat_row(wn_cat_ctl_view(pred + row * C, C, lane, ctl), C, lane, row, seed, offset);
-  if (lane == 0) out[row] = (float)result * inv - 1.0f;
-}
-
-// The same draw straight from the logits (training step with a compiled sample metric, src/model.py:338):
-// the probabilities are those of wn_softmax_kernel (same lane assignment, same reductions), kept in LDS
-// instead of a (rows, C) tensor in HBM, so the drawn class is the one sample_waveform(softmax(logits)) draws.
-#define WN_SAMPLE_FUSED_MAXC 1024
-__global__ __launch_bounds__(256) void wn_sample_rand_cat_logits_kernel(const float* logits, int64_t rows, int C,
-                                                                        float inv_lv, uint64_t seed, uint64_t offset,
-                                                                        float* out, WnEmit em) {
-  __shared__ float q[4][WN_SAMPLE_FUSED_MAXC];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t row = (int64_t)blockIdx.x * 4 + w;
-  if (row >= rows) return;
-  const float v = wn_cat_rand_row(logits + row * C, C, lane, q[w], row, seed, offset, inv_lv);
-  if (lane == 0) {
-    out[row] = v;
-    wn_emit_sample(em, row, v);
-  }
-}
-__global__ __launch_bounds__(256) void wn_sample_rand_cat_logits_ctl_kernel(const float* logits, int64_t rows, int C,
-                                                                            float inv_lv, uint64_t seed, uint64_t offset,
-                                                                            float* out, WnEmit em, WnSampleCtl ctl) {
-  __shared__ float q[4][WN_SAMPLE_FUSED_MAXC];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t row = (int64_t)blockIdx.x * 4 + w;
-  if (row >= rows) return;
-  const float v = wn_cat_rand_row<true>(logits + row * C, C, lane, q[w], row, seed, offset, inv_lv, ctl);
-  if (lane == 0) {
-    out[row] = v;
-    wn_emit_sample(em, row, v);
-  }
-}
-int wn_sample_from_logits_supported(int C) { return C <= WN_SAMPLE_FUSED_MAXC ? 1 : 0; }
-int wn_sample_top_k_max_classes() { return WN_SAMPLE_FUSED_MAXC; }
-int wn_launch_sample_rand_cat_logits(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
-                                     float* out, hipStream_t s) {
-  return wn_launch_sample_rand_cat_logits_emit(logits, rows, C, bits, seed, offset, out, WnEmit{nullptr, 0, 0, nullptr}, s);
-}
-int wn_launch_sample_rand_cat_logits_emit(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
-                                          float* out, WnEmit em, hipStream_t s, WnSampleCtl ctl) {
-  if (rows <= 0) return WN_OK;
-  if (C > WN_SAMPLE_FUSED_MAXC) { wn_set_error("sample from logits: %d classes > %d", C, WN_SAMPLE_FUSED_MAXC); return WN_E_UNSUPPORTED; }
-  if (ctl.on())
-    hipLaunchKernelGGL(wn_sample_rand_cat_logits_ctl_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, rows, C,
-                       1.0f / (float)(1 << (bits - 1)), seed, offset, out, em, ctl);
-  else
-  hipLaunchKernelGGL(wn_sample_rand_cat_logits_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, rows, C,
-                     1.0f / (float)(1 << (bits - 1)), seed, offset, out, em);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-__global__ void wn_sample_rand_mix_kernel(const float* pred, int64_t rows, int M, int kind, uint64_t seed,
-                                          uint64_t offset, float* out, WnEmit em) {
-  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= rows) return;
-  const float vc = wn_mix_rand_row(pred + row * 3 * M, M, kind, row, seed, offset);
-  out[row] = vc;
-  wn_emit_sample(em, row, vc);
-}
-__global__ void wn_sample_rand_mix_ctl_kernel(const float* pred, int64_t rows, int M, int kind, uint64_t seed,
-                                              uint64_t offset, float* out, WnEmit em, WnSampleCtl ctl) {
-  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= rows) return;
-  const float vc = wn_mix_rand_row<true>(pred + row * 3 * M, M, kind, row, seed, offset, ctl);
-  out[row] = vc;
-  wn_emit_sample(em, row, vc);
-}
-int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind,
-                          uint64_t seed, uint64_t offset, float* out, hipStream_t s, WnSampleCtl ctl) {
-  return wn_launch_sample_rand_emit(pred, rows, C, M, bits, kind, seed, offset, out, WnEmit{nullptr, 0, 0, nullptr}, s, ctl);
-}
-// (categorical rows with an emit target go through wn_launch_sample_rand_cat_logits_emit)
-int wn_launch_sample_rand_emit(const float* pred, int64_t rows, int C, int M, int bits, int kind,
-                               uint64_t seed, uint64_t offset, float* out, WnEmit em, hipStream_t s, WnSampleCtl ctl) {
-  if (rows <= 0) return WN_OK;
-  if (M <= 0 && em.out) { wn_set_error("sample_rand_emit: categorical rows start from the logits"); return WN_E_INVALID; }
-  if (M > 0 && ctl.top_k > 0) { wn_set_error("sample_rand_emit: top_k applies to the categorical head only"); return WN_E_INVALID; }
-  if (M <= 0 && ctl.top_k > 0 && C > WN_SAMPLE_FUSED_MAXC) {
-    wn_set_error("sample_rand_emit: top_k over %d classes > %d", C, WN_SAMPLE_FUSED_MAXC);
-    return WN_E_UNSUPPORTED;
-  }
-  if (M <= 0 && ctl.on()) {
-    hipLaunchKernelGGL(wn_sample_rand_cat_ctl_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
-                       pred, rows, C, 1.0f / (float)(1 << (bits - 1)), seed, offset, out, ctl);
-  } else if (M <= 0) {
-    hipLaunchKernelGGL(wn_sample_rand_cat_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
-                       pred, rows, C, 1.0f / (float)(1 << (bits - 1)), seed, offset, out);
-  } else if (ctl.on()) {
-    hipLaunchKernelGGL(wn_sample_rand_mix_ctl_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
-                       s, pred, rows, M, kind, seed, offset, out, em, ctl);
-  } else {
-    hipLaunchKernelGGL(wn_sample_rand_mix_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
-                       s, pred, rows, M, kind, seed, offset, out, em);
-  }
   WN_HIP_CHECK(hipGetLastError());
   return WN_OK;
 }
@@ -1368,29 +763,6 @@ int wn_launch_inconv_wgrad(const float* x, const float* g, int B, int T, int R, 
   const dim3 grid((unsigned)(B * splits_per_b));
   if (KS == 2) hipLaunchKernelGGL(wn_inconv_wgrad_kernel<2>, grid, dim3(256), 0, s, x, g, T, R, splits_per_b, slab, P, w_off, b_off);
   else hipLaunchKernelGGL(wn_inconv_wgrad_kernel<3>, grid, dim3(256), 0, s, x, g, T, R, splits_per_b, slab, P, w_off, b_off);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// Queued generation, categorical head, deterministic: softmax -> arg max -> sample value -> output row and
-// next network input, in ONE launch.  The arithmetic per row is that of wn_softmax_kernel followed by
-// wn_sample_det_cat_kernel (same lane assignment, same reductions), so the result is the same sample.
-__global__ __launch_bounds__(256) void wn_gen_tail_cat_det_kernel(const float* logits, int rows, int C, float inv_lv,
-                                                                  float* out, int length, int step, float* xin_slot) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float sv = wn_cat_det_row(logits + (int64_t)row * C, C, lane, inv_lv);
-  if (lane == 0) {
-    out[(int64_t)row * length + step] = sv;
-    if (xin_slot) xin_slot[row] = sv;
-  }
-}
-int wn_launch_gen_tail_cat_det(const float* logits, int rows, int C, int bits, float* out, int length, int step,
-                               float* xin_slot, hipStream_t s) {
-  if (rows <= 0) return WN_OK;
-  hipLaunchKernelGGL(wn_gen_tail_cat_det_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, rows, C,
-                     1.0f / (float)(1 << (bits - 1)), out, length, step, xin_slot);
   WN_HIP_CHECK(hipGetLastError());
   return WN_OK;
 }

@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
       const bool rok = xok[0];
       const int64_t row = row0 + tl;
       int tgt = rok ? a.target[row] : 0;
-      tgt = tgt < 0 ? 0 : (tgt > 255 ? 255 : tgt);
+      tgt = wn_ce_target(tgt, 256);
       auto xch = [](float v) { return __shfl_xor(v, 32); };       // the partner lane holds the row's other 128 classes
       // logits = acc + bias; row maximum
       float m = -INFINITY;
@@ -295,28 +295,22 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
         for (int r = 0; r < 16; ++r) {
           const float q = acc[0][j][r] * inv;
           acc[0][j][r] = q;
-          S += fminf(fmaxf(q, WN_KERAS_EPS), 1.0f - WN_KERAS_EPS);
-          if (q >= WN_KERAS_EPS && q <= 1.0f - WN_KERAS_EPS) A += q;
+          S += wn_ce_clip(q);
+          if (wn_ce_inside(q)) A += q;
           if (32 * j + 8 * (r >> 2) + 4 * h + (r & 3) == tgt) qt = q;
         }
       S += xch(S);
       A += xch(A);
       qt += xch(qt);                                      // (the other half contributes 0)
-      const float pt = fminf(fmaxf(qt, WN_KERAS_EPS), 1.0f - WN_KERAS_EPS);
-      const float ct = (qt >= WN_KERAS_EPS && qt <= 1.0f - WN_KERAS_EPS) ? 1.f : 0.f;
-      if (rok && h == 0) a.loss_rows[row] = -(logf(pt) - logf(S));
+      const WnCeRow ce(S, A, qt);
+      if (rok && h == 0) a.loss_rows[row] = wn_ce_loss(ce.pt, S);
       // ---- gradient w.r.t. the logits, in place ----
-      const float invS = 1.0f / S;
-      const float dot = A * invS - ct * qt / pt;          // sum_j g_j q_j
 #pragma unroll
       for (int j = 0; j < JT; ++j) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float q = acc[0][j][r];
-          const float c = (q >= WN_KERAS_EPS && q <= 1.0f - WN_KERAS_EPS) ? 1.f : 0.f;
-          float g = c * invS;
-          if (32 * j + 8 * (r >> 2) + 4 * h + (r & 3) == tgt) g -= ct / pt;
-          const float gl = a.gscale * q * (g - dot);
+          const float gl = ce.grad(q, 32 * j + 8 * (r >> 2) + 4 * h + (r & 3) == tgt, a.gscale);
           acc[0][j][r] = gl;
           if (rok) wmax = fmaxf(wmax, fabsf(gl));
         }

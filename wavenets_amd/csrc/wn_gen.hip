@@ -768,14 +768,13 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
                         : a.ctl.on() ? wn_mix_rand_row<true>(p, a.mix_M, a.mix_kind, row, a.seed, a.offset, a.ctl)
                                      : wn_mix_rand_row(p, a.mix_M, a.mix_kind, row, a.seed, a.offset);
         if (a.samp) a.samp[row] = v;
-        a.em.out[(int64_t)row * a.em.length + a.em.step] = v;
-        if (a.em.xin_slot) a.em.xin_slot[row] = v;
+        wn_emit_sample(a.em, row, v);
       }
     }
     return;
   }
   // ---- categorical sampling tail (softmax -> arg max, or softmax -> inverse-CDF draw) and emit, one wave per row: the
-  // rows of wn_gen_tail_cat_det_kernel / wn_sample_rand_cat_logits_kernel, so the samples are theirs.  The logits were
+  // rows of wn_sample_det_cat_logits_kernel / wn_sample_rand_cat_logits_kernel, so the samples are theirs.  The logits were
   // stored by other waves of this workgroup: the barrier above has drained those stores, and nothing has read these
   // lines into this CU's L1 before ----
   if (a.tail == 1 || a.tail == 2) {
@@ -791,8 +790,7 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
                                    : wn_cat_rand_row(l, C, lane, q, row, a.seed, a.offset, a.inv_lv);
       if (lane == 0) {
         if (a.samp) a.samp[row] = v;
-        a.em.out[(int64_t)row * a.em.length + a.em.step] = v;
-        if (a.em.xin_slot) a.em.xin_slot[row] = v;
+        wn_emit_sample(a.em, row, v);
       }
     }
   }

@@ -480,20 +480,16 @@ extern "C" int wn_generate_sampled(wn_plan* p, const float* params, const float*
     }
     if (head_tail || head_mix) {
       // sampled and emitted by the head launch
-    } else if (p->c.head == WN_HEAD_CATEGORICAL && deterministic) {
-      // softmax + arg max + emit in one launch
-      rc = wn_launch_gen_tail_cat_det(last, B, p->Cout, p->c.bits, out, length, step, R.xin + (int64_t)((tau + 1) % p->KS) * B, s);
-      if (rc) return rc;
     } else {
-      // sampler and emit in one launch (categorical draws straight from the logits: the softmax of
-      // wn_softmax_kernel in LDS, the class sample_waveform(softmax(logits)) draws)
+      // sampler and emit in one launch (categorical: straight from the logits -- softmax + arg max, or the softmax of
+      // wn_softmax_kernel in LDS and the class sample_waveform(softmax(logits)) draws)
       const WnEmit em{out, length, step, R.xin + (int64_t)((tau + 1) % p->KS) * B};
-      if (p->c.head == WN_HEAD_CATEGORICAL && !deterministic && wn_sample_from_logits_supported(p->Cout)) {
-        rc = wn_launch_sample_rand_cat_logits_emit(last, B, p->Cout, p->c.bits, seed, (uint64_t)step, samp, em, s, ctl);
+      const bool cat = p->c.head == WN_HEAD_CATEGORICAL;
+      if (deterministic) {
+        rc = wn_launch_sample_det(last, B, p->Cout, p->c.num_mixtures, p->c.bits, cat ? nullptr : samp, s, em);
         if (rc) return rc;
-      } else if (p->c.head != WN_HEAD_CATEGORICAL) {
-        if (deterministic) rc = wn_launch_sample_det_emit(last, B, p->Cout, p->c.num_mixtures, p->c.bits, samp, em, s);
-        else rc = wn_launch_sample_rand_emit(last, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, (uint64_t)step, samp, em, s, ctl);
+      } else if (!cat || wn_sample_from_logits_supported(p->Cout)) {
+        rc = wn_launch_sample_rand(last, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, (uint64_t)step, samp, s, ctl, em);
         if (rc) return rc;
       } else {
         rc = sample_rows(p, last, B, deterministic != 0, seed, (uint64_t)step, lastp, samp, s, ctl);

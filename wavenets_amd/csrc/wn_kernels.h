@@ -287,6 +287,7 @@ int wn_launch_gen_relay128(const WnGen128Args& a, hipStream_t s);
 int64_t wn_gen_relay128_floats(int B, int nblocks);
 // queued generation: where a sampler also puts its sample (output rows [rows][length] at column step; network input slot)
 struct WnEmit { float* out; int length; int step; float* xin_slot; };
+#define WN_EMIT_NONE (WnEmit{nullptr, 0, 0, nullptr})
 // sampling controls of a stochastic draw (wn_sample.h; semantics: include/wn_hip.h, struct wn_sampling): temperature T with
 // inv_T = 1 / T finite, top_k = 0 off (callers pass 0 for top_k >= classes).  on() false = the draw without controls.
 struct WnSampleCtl {
@@ -328,7 +329,7 @@ int wn_gen_skip_fusable(int S);
 int wn_launch_gen_blocks(const WnGenStepArgs& a, int R, int KS, int what, hipStream_t s);
 int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, hipStream_t s);
 
-// ---------------------------------------------------------------- elementwise / loss / sampling
+// ---------------------------------------------------------------- elementwise (wn_elem.hip)
 int wn_launch_add(const float* a, const float* b, float* out, int64_t n, hipStream_t s);
 int wn_launch_fill(float* p, float v, int64_t n, hipStream_t s);
 int wn_launch_dact_mul(const float* g, const float* y, float* out, int64_t n, int act, hipStream_t s);
@@ -365,8 +366,6 @@ int wn_launch_inconv_fwd(const float* x, const float* w, const float* bias, int 
 int wn_launch_guard_flag(const float* absmax, float limit, int enabled, float* out, hipStream_t s);
 // dst[0] = max(dst[0], src[0]) on the bit patterns (non-negative floats; inf / NaN stay on top)
 int wn_launch_guard_accumulate(const float* src, float* dst, hipStream_t s);
-int wn_launch_gen_tail_cat_det(const float* logits, int rows, int C, int bits, float* out, int length, int step,
-                               float* xin_slot, hipStream_t s);
 int wn_launch_batch_reduce(const float* slab, int B, int splits, int N, float* out, hipStream_t s);
 int64_t wn_colsum_scratch_floats(int B, int C);
 int wn_launch_colsum_per_batch(const float* g, int B, int T, int C, float* out, float* scratch, hipStream_t s);
@@ -374,10 +373,9 @@ int wn_launch_quantize(const float* x, int32_t* idx, int64_t n, int bits, hipStr
 int wn_launch_dequantize(const int32_t* idx, float* x, int64_t n, int bits, hipStream_t s);
 int wn_launch_mulaw(const float* x, float* y, int64_t n, hipStream_t s);
 int wn_launch_inv_mulaw(const float* y, float* x, int64_t n, hipStream_t s);
+
+// ---------------------------------------------------------------- softmax / loss / reductions (wn_loss.hip)
 int wn_launch_softmax(const float* logits, float* probs, int64_t rows, int C, hipStream_t s);
-int wn_sample_from_logits_supported(int C);
-int wn_launch_sample_rand_cat_logits(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
-                                     float* out, hipStream_t s);
 // categorical: Keras sparse CE on clipped probabilities; g_logits may be null (loss only)
 int wn_launch_cat_loss(const float* logits, const int32_t* target, int64_t rows, int C,
                        float gscale, float* loss_rows, float* g_logits, float* absmax_out, hipStream_t s,
@@ -390,19 +388,23 @@ int wn_launch_mix_loss(const float* pred, const float* y, int64_t rows, int M, i
                        float gscale, float* loss_rows, float* g_pred, float* absmax_out, hipStream_t s);
 int wn_launch_sum(const float* v, int64_t n, float scale, float* out, float* scratch, hipStream_t s);
 int wn_launch_sqdiff_sum(const float* a, const float* b, int64_t n, float scale, float* out, float* scratch, hipStream_t s);
+
+// ---------------------------------------------------------------- samplers (wn_sample.hip)
+// em: queued generation, the sample also goes to the output rows and the network's input slot in the same launch.
+// Categorical rows with an emit target are LOGITS rows (softmax, sampler and emit in one launch; out may be null for the
+// deterministic one); without one, pred holds probabilities.
 // deterministic samplers: categorical argmax -> left bin edge; mixtures -> clipped mean
-int wn_launch_sample_det_emit(const float* pred, int64_t rows, int C, int M, int bits, float* out, WnEmit em, hipStream_t s);
-int wn_launch_sample_rand_emit(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t seed, uint64_t offset,
-                               float* out, WnEmit em, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF);
-int wn_launch_sample_rand_cat_logits_emit(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
-                                          float* out, WnEmit em, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF);
-// top-k is offered for up to this many classes (WN_SAMPLE_FUSED_MAXC, wn_elem.hip)
-int wn_sample_top_k_max_classes();
-int wn_launch_sample_det(const float* pred, int64_t rows, int C, int M, int bits, float* out,
-                         hipStream_t s);
+int wn_launch_sample_det(const float* pred, int64_t rows, int C, int M, int bits, float* out, hipStream_t s,
+                         WnEmit em = WN_EMIT_NONE);
 // stochastic samplers (Philox4x32-10 keyed by seed, counter = row)
-int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind,
-                          uint64_t seed, uint64_t offset, float* out, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF);
+int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t seed, uint64_t offset,
+                          float* out, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF, WnEmit em = WN_EMIT_NONE);
+// the categorical draw straight from the logits, for up to WN_SAMPLE_FUSED_MAXC classes
+int wn_sample_from_logits_supported(int C);
+int wn_launch_sample_rand_cat_logits(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
+                                     float* out, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF, WnEmit em = WN_EMIT_NONE);
+// top-k is offered for up to this many classes (WN_SAMPLE_FUSED_MAXC, wn_sample.hip)
+int wn_sample_top_k_max_classes();
 
 // ---------------------------------------------------------------- optimizer
 int wn_launch_sumsq(const float* g, const WnTensorDesc* d_table, int n, float* norms2, hipStream_t s);

@@ -1,0 +1,264 @@
+// Softmax, loss and reduction kernels of the WaveNet hot path (gfx950).  The categorical row arithmetic is that of
+// wn_catrow.h; losses src/model.py:505-551.
+#include <algorithm>
+
+#include "wn_kernels.h"
+#include "wn_sample.h"
+
+__global__ __launch_bounds__(256) void wn_softmax_kernel(const float* logits, float* probs,
+                                                         int64_t rows, int C) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  WnSoftmaxLoop(logits + row * C, C, lane).each([&](int j, float q) { probs[row * C + j] = q; });
+}
+int wn_launch_softmax(const float* logits, float* probs, int64_t rows, int C, hipStream_t s) {
+  if (rows <= 0) return WN_OK;
+  hipLaunchKernelGGL(wn_softmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits,
+                     probs, rows, C);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
+// Keras sparse_categorical_crossentropy(target, softmax(logits)), from_logits=False, and its gradient w.r.t. the logits:
+// wn_cat_ce_row (wn_catrow.h) on the softmax row of the logits.
+// sample_out (C <= 256 only): also draw sample_waveform(softmax(logits)) of the row (src/model.py:338,407-411)
+// from the probabilities already in registers -- the values wn_softmax_kernel would write, the draw
+// wn_sample_rand_cat_kernel would make from them.
+// C <= 256, the shape of every BASELINE categorical head: persistent waves, one row at a time per wave with the NEXT row's
+// logits and target already requested (a one-row-per-wave launch spends most of a row waiting for its loads: 172 us for
+// 268 MB); the row lives in registers, and the max-abs of the gradients is published once per wave.
+__global__ __launch_bounds__(256) void wn_cat_loss256_kernel(const float* logits, const int32_t* target,
+                                                             int64_t rows, int C, float gscale,
+                                                             float* loss_rows, float* g_logits, float* absmax_out,
+                                                             float* sample_out, float inv_lv, uint64_t seed, uint64_t offset) {
+  __shared__ float qs[4][256];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  int64_t row = (int64_t)blockIdx.x * 4 + w;
+  float vn[4];
+  int tn = 0;
+  auto fetch = [&](int64_t r) {
+    wn_cat_load4(logits + r * C, C, lane, vn);
+    tn = target[r];
+  };
+  if (row < rows) fetch(row);
+  float gmax = 0.f;
+  for (; row < rows; row += stride) {
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = vn[k];
+    const int tgt = tn;
+    if (row + stride < rows) fetch(row + stride);     // in flight while this row is worked on
+    const WnSoftmaxRegs r(v, C, lane);
+    if (sample_out) {
+      float* qw = qs[w];
+      r.each([&](int j, float q) { qw[j] = q; });
+      __builtin_amdgcn_wave_barrier();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      const int drawn = wn_draw_cat_row((const float*)qw, C, lane, row, seed, offset);
+      if (lane == 0) sample_out[row] = (float)drawn * inv_lv - 1.0f;
+      __builtin_amdgcn_wave_barrier();                // the next row rewrites qw
+    }
+    wn_cat_ce_row(r, tgt, gscale, loss_rows + row, g_logits, row * C, gmax);
+  }
+  if (g_logits && absmax_out) {
+    gmax = wn_wave_max(gmax);
+    if (lane == 0) wn_absmax_publish(absmax_out, gmax);
+  }
+}
+
+// more than 256 classes: one row per wave, the row re-read from memory on every pass
+__global__ __launch_bounds__(256) void wn_cat_loss_kernel(const float* logits, const int32_t* target,
+                                                          int64_t rows, int C, float gscale,
+                                                          float* loss_rows, float* g_logits, float* absmax_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  float gmax = 0.f;
+  wn_cat_ce_row(WnSoftmaxLoop(logits + row * C, C, lane), target[row], gscale, loss_rows + row, g_logits, row * C, gmax);
+  if (g_logits && absmax_out) {
+    gmax = wn_wave_max(gmax);
+    if (lane == 0) wn_absmax_publish(absmax_out, gmax);
+  }
+}
+int wn_launch_cat_loss(const float* logits, const int32_t* target, int64_t rows, int C,
+                       float gscale, float* loss_rows, float* g_logits, float* absmax_out, hipStream_t s,
+                       float* sample_out, int bits, uint64_t seed, uint64_t offset) {
+  if (rows <= 0) return WN_OK;
+  if (sample_out && C > 256) { wn_set_error("cat_loss: the in-kernel sample draw needs <= 256 classes"); return WN_E_UNSUPPORTED; }
+  const float inv_lv = sample_out ? 1.0f / (float)(1 << (bits - 1)) : 0.f;
+  if (C <= 256) {
+    const int64_t wgs = std::min<int64_t>((rows + 3) / 4, 256 * 8);
+    hipLaunchKernelGGL(wn_cat_loss256_kernel, dim3((unsigned)wgs), dim3(256), 0, s, logits, target, rows, C, gscale,
+                       loss_rows, g_logits, absmax_out, sample_out, inv_lv, seed, offset);
+  } else {
+    hipLaunchKernelGGL(wn_cat_loss_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits,
+                       target, rows, C, gscale, loss_rows, g_logits, absmax_out);
+  }
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
+__global__ __launch_bounds__(256) void wn_cat_loss_probs_kernel(const float* probs,
+                                                                const int32_t* target, int64_t rows,
+                                                                int C, float* loss_rows) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* q = probs + row * C;
+  float S = 0.f;
+  for (int j = lane; j < C; j += 64) S += wn_ce_clip(q[j]);
+  S = wn_wave_sum(S);
+  const float pt = wn_ce_clip(q[wn_ce_target(target[row], C)]);
+  if (lane == 0) loss_rows[row] = wn_ce_loss(pt, S);
+}
+int wn_launch_cat_loss_probs(const float* probs, const int32_t* target, int64_t rows, int C,
+                             float* loss_rows, hipStream_t s) {
+  if (rows <= 0) return WN_OK;
+  hipLaunchKernelGGL(wn_cat_loss_probs_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
+                     probs, target, rows, C, loss_rows);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
+// mixture losses, one thread per (b,t) row; M <= 32.  Evaluated in double: with bits = 16 the
+// half-bin (src/model.py:538) is 7.6e-6, so sigmoid(a) - sigmoid(b) cancels ~5 digits and an
+// fp32 evaluation (the reference's own included) carries 1e-3..1e-2 relative noise per term.
+#define WN_MAXMIX 32
+__device__ __forceinline__ double wn_sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
+__global__ void wn_mix_loss_kernel(const float* pred, const float* y, int64_t rows, int M, int bits,
+                                   int kind, float gscale, float* loss_rows, float* g_pred, float* absmax_out) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  const float* p = pred + row * 3 * M;
+  const double yy = (double)y[row];
+  double w[WN_MAXMIX], comp[WN_MAXMIX];
+  double wm = -INFINITY;
+  for (int k = 0; k < M; ++k) wm = fmax(wm, (double)p[k]);
+  double wz = 0.0;
+  for (int k = 0; k < M; ++k) { w[k] = exp((double)p[k] - wm); wz += w[k]; }
+  const double winv = 1.0 / wz;
+  const double halfbit = 0.5 / (double)(1 << bits);                      // src/model.py:538
+  const double sqrt2pi = sqrt(2.0 * 3.14159265359);                      // src/model.py:9
+  double lik = 0.0;
+  for (int k = 0; k < M; ++k) {
+    w[k] *= winv;
+    const double mu = (double)p[M + k];
+    const double ls = fmax((double)p[2 * M + k], -7.0);
+    if (kind == 1) {
+      const double inv = exp(-ls);
+      comp[k] = wn_sigmoid_d((yy - mu + halfbit) * inv) - wn_sigmoid_d((yy - mu - halfbit) * inv);
+    } else {
+      const double sc = exp(ls);
+      const double xx = fmin((yy - mu) / sc, 1e8);
+      comp[k] = exp(-0.5 * xx * xx) / (sc * sqrt2pi);
+    }
+    lik += w[k] * comp[k];
+  }
+  loss_rows[row] = (float)(-log(lik));
+  if (!g_pred) return;
+  float* g = g_pred + row * 3 * M;
+  const double dl = -(double)gscale / lik;                               // dL/dlik
+  for (int k = 0; k < M; ++k) {
+    const double mu = (double)p[M + k];
+    const double lsr = (double)p[2 * M + k];
+    const double ls = fmax(lsr, -7.0);
+    const double lsmask = lsr >= -7.0 ? 1.0 : 0.0;
+    g[k] = (float)(dl * (w[k] * comp[k] - w[k] * lik));
+    if (kind == 1) {
+      const double inv = exp(-ls);
+      const double a = (yy - mu + halfbit) * inv, b = (yy - mu - halfbit) * inv;
+      const double sa = wn_sigmoid_d(a), sb = wn_sigmoid_d(b);
+      const double da = sa * (1.0 - sa), db = sb * (1.0 - sb);
+      g[M + k] = (float)(dl * (-w[k] * inv * (da - db)));
+      g[2 * M + k] = (float)(dl * lsmask * (-w[k] * (a * da - b * db)));
+    } else {
+      const double sc = exp(ls);
+      const double xr = (yy - mu) / sc;
+      const double xx = fmin(xr, 1e8);
+      const double xmask = xr <= 1e8 ? 1.0 : 0.0;
+      const double pdf = comp[k];
+      // d pdf/d mu = pdf * xx / sc ; d pdf/d ls = pdf * (xx^2 - 1)
+      g[M + k] = (float)(dl * w[k] * pdf * xx / sc * xmask);
+      g[2 * M + k] = (float)(dl * lsmask * w[k] * pdf * (xx * xx * xmask - 1.0));
+    }
+  }
+  if (absmax_out) {
+    float gmax = 0.f;
+    for (int k = 0; k < 3 * M; ++k) gmax = fmaxf(gmax, fabsf(g[k]));
+    wn_absmax_publish(absmax_out, gmax);
+  }
+}
+int wn_launch_mix_loss(const float* pred, const float* y, int64_t rows, int M, int bits, int kind,
+                       float gscale, float* loss_rows, float* g_pred, float* absmax_out, hipStream_t s) {
+  if (rows <= 0) return WN_OK;
+  if (M < 1 || M > WN_MAXMIX) { wn_set_error("mix_loss: num_mixtures %d unsupported (max %d)", M, WN_MAXMIX); return WN_E_UNSUPPORTED; }
+  hipLaunchKernelGGL(wn_mix_loss_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, pred,
+                     y, rows, M, bits, kind, gscale, loss_rows, g_pred, absmax_out);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// deterministic two-stage sum (double accumulation), out[0] = scale * sum(v)
+__global__ void wn_sum_stage1(const float* v, int64_t n, double* scratch) {
+  __shared__ double sm[256];
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    acc += (double)v[i];
+  sm[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) scratch[blockIdx.x] = sm[0];
+}
+__global__ void wn_sum_stage2(const double* scratch, int nb, float scale, float* out) {
+  __shared__ double sm[256];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) acc += scratch[i];
+  sm[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)(sm[0] * (double)scale);
+}
+// scratch: >= 1024 doubles (8 KiB)
+int wn_launch_sum(const float* v, int64_t n, float scale, float* out, float* scratch, hipStream_t s) {
+  int nb = wn_blocks(n, 256, 1024);
+  hipLaunchKernelGGL(wn_sum_stage1, dim3(nb), dim3(256), 0, s, v, n, reinterpret_cast<double*>(scratch));
+  hipLaunchKernelGGL(wn_sum_stage2, dim3(1), dim3(256), 0, s, reinterpret_cast<const double*>(scratch), nb, scale, out);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
+// out[0] = scale * sum((a - b)^2): tf.keras.metrics.MeanSquaredError(y_true, sample) of a step (src/model.py:346,
+// train.py:227) with scale = 1 / (n * replicas); same two-stage double accumulation as wn_launch_sum
+__global__ void wn_sqdiff_stage1(const float* a, const float* b, int64_t n, double* scratch) {
+  __shared__ double sm[256];
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float d = a[i] - b[i];
+    acc += (double)(d * d);
+  }
+  sm[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) scratch[blockIdx.x] = sm[0];
+}
+int wn_launch_sqdiff_sum(const float* a, const float* b, int64_t n, float scale, float* out, float* scratch, hipStream_t s) {
+  int nb = wn_blocks(n, 256, 1024);
+  hipLaunchKernelGGL(wn_sqdiff_stage1, dim3(nb), dim3(256), 0, s, a, b, n, reinterpret_cast<double*>(scratch));
+  hipLaunchKernelGGL(wn_sum_stage2, dim3(1), dim3(256), 0, s, reinterpret_cast<const double*>(scratch), nb, scale, out);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}

@@ -1,37 +1,13 @@
-// Row samplers shared by the sampling kernels (wn_elem.hip) and the generation head kernel (wn_gen.hip): one wave per row.
+// Row samplers shared by the sampling kernels (wn_sample.hip) and the generation head kernel (wn_gen.hip): one wave per row.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 #include "wn_kernels.h"
+#include "wn_catrow.h"
 
 // ------------------------------------------------------------------------------------------
-// wave-per-row helpers
-// Reductions over the 64 lanes on the DPP cross-lane operands of the VALU (no LDS round trips: __shfl_xor is a ds_bpermute
-// with its own address and wait, six in a row per reduction): quad butterflies, then the two mirror permutations leave
-// every lane with the sum / max of its row of 16; the four row results are read as scalars.  Every lane returns the result.
-// (All 64 lanes must be active, as with the shuffles.)
-#define WN_DPP_F(v, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, false))
-__device__ __forceinline__ float wn_wave_max(float v) {
-  v = fmaxf(v, WN_DPP_F(v, 0xB1));                  // quad_perm [1, 0, 3, 2]
-  v = fmaxf(v, WN_DPP_F(v, 0x4E));                  // quad_perm [2, 3, 0, 1]
-  v = fmaxf(v, WN_DPP_F(v, 0x141));                 // row_half_mirror
-  v = fmaxf(v, WN_DPP_F(v, 0x140));                 // row_mirror
-  const int b = __builtin_bit_cast(int, v);
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-  return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-}
-__device__ __forceinline__ float wn_wave_sum(float v) {
-  v += WN_DPP_F(v, 0xB1);
-  v += WN_DPP_F(v, 0x4E);
-  v += WN_DPP_F(v, 0x141);
-  v += WN_DPP_F(v, 0x140);
-  const int b = __builtin_bit_cast(int, v);
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-  return (r0 + r1) + (r2 + r3);
-}
+// wave-per-row helpers (wn_wave_max / wn_wave_sum: wn_catrow.h)
 // inclusive prefix sum over the lanes: shifts by 1, 2, 4, 8 inside the rows of 16 (lanes without a source add zero), then
 // the last lane of rows 0 / 2 into rows 1 / 3 and lane 31 into the upper half
 #define WN_DPP_Z(v, ctrl, rmask) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, rmask, 0xf, false))
@@ -179,67 +155,32 @@ __device__ __forceinline__ WnCatCtlView<P> wn_cat_ctl_view(P p, int C, int lane,
 
 
 // Categorical head, deterministic (src/model.py:393-421 with deterministic sampling): softmax -> arg max -> sample value.
-// The arithmetic is that of wn_softmax_kernel followed by wn_sample_det_cat_kernel (same lane assignment, same
-// reductions), so the result is the same sample.  Every lane returns it.
+// The probabilities are those wn_softmax_kernel stores and the arg max is that of wn_sample_det_cat_kernel (the same row
+// and the same butterfly of wn_catrow.h), so the result is the same sample.  Every lane returns it.
 __device__ __forceinline__ float wn_cat_det_row(const float* l, int C, int lane, float inv_lv) {
-  float m = -INFINITY;
-  for (int j = lane; j < C; j += 64) m = fmaxf(m, l[j]);
-  m = wn_wave_max(m);
-  float z = 0.f;
-  for (int j = lane; j < C; j += 64) z += expf(l[j] - m);
-  z = wn_wave_sum(z);
-  const float inv = 1.0f / z;
   float best = -INFINITY;
   int bi = 0x7fffffff;
-  for (int j = lane; j < C; j += 64) {
-    const float v = expf(l[j] - m) * inv;        // the probability wn_softmax_kernel would have stored
-    if (v > best) { best = v; bi = j; }          // strictly greater keeps the first maximum
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o);
-    const int oi = __shfl_xor(bi, o);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
+  WnSoftmaxLoop(l, C, lane).each([&](int j, float v) {
+    if (v > best) { best = v; bi = j; }            // strictly greater keeps the first maximum
+  });
+  wn_wave_argmax_first(best, bi);
   return (float)bi * inv_lv - 1.0f;
 }
 
-// Categorical head, stochastic draw straight from the logits: the probabilities are those of wn_softmax_kernel (same lane
-// assignment, same reductions), kept in the LDS row q[0..C) instead of a (rows, C) tensor in HBM, so the drawn class is
-// the one sample_waveform(softmax(logits)) draws.  Every lane returns the sample value.
+// Categorical head, stochastic draw straight from the logits: the probabilities are those wn_softmax_kernel stores, kept
+// in the LDS row q[0..C) instead of a (rows, C) tensor in HBM, so the drawn class is the one
+// sample_waveform(softmax(logits)) draws.  Every lane returns the sample value.
 // CTL: the draw under the sampling controls, from the view of the same LDS row.
 template <bool CTL = false>
 __device__ __forceinline__ float wn_cat_rand_row(const float* l, int C, int lane, float* q, int64_t row, uint64_t seed,
                                                  uint64_t offset, float inv_lv, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF) {
-  if (C <= 256) {
-    // one read of the row, one exp per class (element k of a lane = class lane + 64 k: the same per-lane
-    // order of the max / sum as the loops below)
-    float v[4], e[4];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      v[k] = lane + 64 * k < C ? l[lane + 64 * k] : -INFINITY;
-      m = fmaxf(m, v[k]);
-    }
-    m = wn_wave_max(m);
-    float z = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (lane + 64 * k < C) { e[k] = expf(v[k] - m); z += e[k]; }
-    z = wn_wave_sum(z);
-    const float inv = 1.0f / z;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (lane + 64 * k < C) q[lane + 64 * k] = e[k] * inv;
+  auto keep = [&](int j, float v) { q[j] = v; };
+  if (C <= 256) {                                    // one read of the row, one exp per class
+    float v[4];
+    wn_cat_load4(l, C, lane, v);
+    WnSoftmaxRegs(v, C, lane).each(keep);
   } else {
-    float m = -INFINITY;
-    for (int j = lane; j < C; j += 64) m = fmaxf(m, l[j]);
-    m = wn_wave_max(m);
-    float z = 0.f;
-    for (int j = lane; j < C; j += 64) z += expf(l[j] - m);
-    z = wn_wave_sum(z);
-    const float inv = 1.0f / z;
-    for (int j = lane; j < C; j += 64) q[j] = expf(l[j] - m) * inv;
+    WnSoftmaxLoop(l, C, lane).each(keep);
   }
   __builtin_amdgcn_wave_barrier();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
