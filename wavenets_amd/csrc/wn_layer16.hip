@@ -32,10 +32,15 @@ struct WnL16 {
   static constexpr int LDS_BYTES = WD_BYTES + WR_BYTES + WAVES * STAGE_BYTES + BIAS_BYTES;
 };
 
-// tile (32 rows x C floats) held as D-layout registers -> LDS stage -> coalesced rows in HBM
+// tile (32 rows x C floats) held as D-layout registers -> LDS stage -> coalesced rows in HBM.
+// The rows leave as buffer stores on a descriptor that ends behind the tile's last valid row (dst and rows_valid are
+// wave-uniform): the hardware drops the rows of a ragged tile, and no store sits in a branch.  As `if (row < rows_valid)`
+// around a global store every store had an exec-skip branch of its own, and hipcc's wait counts behind them are those of
+// the path that stored nothing: requests made before a tile's stores could not be told from the stores (vmcnt(15) where
+// 38 were allowed).
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 template <int C32, int PITCH>
-__device__ __forceinline__ void wn_store_tile(const f32x16 (&v)[C32], float* stage, float* dst, int64_t ld,
-                                              int rows_valid, int lane) {
+__device__ __forceinline__ void wn_store_tile(const f32x16 (&v)[C32], float* stage, float* dst, int ld, int rows_valid, int lane) {
   const int tl = lane & 31, h = lane >> 5;
 #pragma unroll
   for (int j = 0; j < C32; ++j)
@@ -50,12 +55,13 @@ __device__ __forceinline__ void wn_store_tile(const f32x16 (&v)[C32], float* sta
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   constexpr int LPR = C32 * 8;                 // lanes (16-byte pieces) per row
   constexpr int RPI = 64 / LPR;                // rows per store instruction
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, rows_valid * ld * 4, 0x00020000);
 #pragma unroll
   for (int i = 0; i < 32 / RPI; ++i) {
     const int row = i * RPI + lane / LPR;
     const int col = (lane % LPR) * 4;
     const f32x4 o = *reinterpret_cast<const f32x4*>(stage + row * PITCH + col);
-    if (row < rows_valid) *reinterpret_cast<f32x4*>(dst + (int64_t)row * ld + col) = o;
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs, (row * ld + col) * 4, 0, 0);
   }
   asm volatile("" ::: "memory");
 }
@@ -77,7 +83,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
   constexpr int QR = R / 8;
   __shared__ __attribute__((aligned(16))) unsigned char smem[G::LDS_BYTES];
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform: what follows from the tile index stays in scalar registers
   const int tl = lane & 31, h = lane >> 5;
 
   // ---- weights: global (fp16 hi|lo images) -> LDS, once per workgroup ----
@@ -102,30 +108,74 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
   const int64_t ntiles = (int64_t)a.B * tiles_per_b;
   float wmax = 0.f;                                      // forward range guard: max |x_out| of this wave's tiles
   const WnTileWalk walk = wn_tile_walk(ntiles, G::WAVES, wave);
-  for (int64_t tile = walk.first; tile < walk.end; tile += walk.stride) {
-    const int b = (int)(tile / tiles_per_b);
+
+  // Where a tile's rows and taps are.  The activation loads are unconditional, on a clamped row; what is carried is
+  // whether a lane's row counts.
+  struct Tile {
+    int b, rows_valid;
+    bool tin, xvalid[KS];
+    int64_t row0;
+    const float* xrow[KS];
+  };
+  auto tile_at = [&](int64_t tile) {
+    Tile s;
+    s.b = (int)(tile / tiles_per_b);
     const int t0 = (int)(tile % tiles_per_b) * 32;
     const int t = t0 + tl;
-    const bool tin = t < a.T;
-    const int rows_valid = min(32, a.T - t0);
-    const int64_t row0 = (int64_t)b * a.T + t0;
-
-    // ---- activation loads of all taps, issued up front (unconditional, clamped row) ----
-    f32x4 xq[KS][QR];
-    bool xvalid[KS];
+    s.tin = t < a.T;
+    s.rows_valid = min(32, a.T - t0);
+    s.row0 = (int64_t)s.b * a.T + t0;
 #pragma unroll
     for (int tap = 0; tap < KS; ++tap) {
       const int ts = a.xt[tap] ? t : t - (KS - 1 - tap) * a.dilation;
-      xvalid[tap] = tin && ts >= 0;
-      const float* xrow = (a.xt[tap] ? a.xt[tap] : a.x) + ((int64_t)b * a.T + (xvalid[tap] ? ts : 0)) * R + 4 * h;
-#pragma unroll
-      for (int q = 0; q < QR; ++q) xq[tap][q] = *reinterpret_cast<const f32x4*>(xrow + 8 * q);
+      s.xvalid[tap] = s.tin && ts >= 0;
+      s.xrow[tap] = (a.xt[tap] ? a.xt[tap] : a.x) + ((int64_t)s.b * a.T + (s.xvalid[tap] ? ts : 0)) * R + 4 * h;
     }
-    // the per-utterance conditioning bias: ONE coalesced request per lane (2 D floats a row) in the same round trip as the
-    // activations, spread to the accumulator layout through the wave's (still idle) output stage.  (As 16 D-layout loads
-    // behind the pin it cost a second, exposed round trip per tile: 38.8 against 34.5 us a launch with global conditioning.)
-    f32x4 cbv = {0.f, 0.f, 0.f, 0.f};
-    if (a.cb && 4 * lane < 2 * D) cbv = *reinterpret_cast<const f32x4*>(a.cb + (int64_t)b * 2 * D + 4 * lane);
+    return s;
+  };
+  f32x4 xq[KS][QR];
+  f32x4 cbv = {0.f, 0.f, 0.f, 0.f};
+  auto request_tap = [&](const Tile& s, auto tapc) {
+    constexpr int tap = decltype(tapc)::value;
+#pragma unroll
+    for (int q = 0; q < QR; ++q) xq[tap][q] = *reinterpret_cast<const f32x4*>(s.xrow[tap] + 8 * q);
+  };
+  // the per-utterance conditioning bias: ONE coalesced request per lane (2 D floats a row) in the same round trip as the
+  // activations, spread to the accumulator layout through the wave's (still idle) output stage.  (As 16 D-layout loads
+  // behind the pin it cost a second, exposed round trip per tile: 38.8 against 34.5 us a launch with global conditioning.)
+  auto request_cb = [&](const Tile& s) {
+    if (a.cb && 4 * lane < 2 * D) cbv = *reinterpret_cast<const f32x4*>(a.cb + (int64_t)s.b * 2 * D + 4 * lane);
+  };
+
+  // The training forms (FAST >= 2) rotate the tap registers through the tile loop: a tap's quads die at its last k-step
+  // of the conv (the newest tap's at the residual add), and the NEXT tile's tap is requested into them right there, so
+  // that the requests travel under the rest of this tile's products and stores instead of in front of the next tile's.
+  // Only a wave's first tile requests its own taps, at its top.  A wave without a next tile requests nothing.
+  //
+  // Whether a tile has a successor is a COMPILE-TIME property of the body (`nextc`), and the body is instantiated once per
+  // position in the walk (see the walk below).  As one loop with a run-time guard around the requests hipcc's wait counts
+  // are those of the worst path through every join: the newest tap's k-steps waited for the requests issued in the middle
+  // of the conv (vmcnt(7) .. vmcnt(0) behind 8 new loads), and the first product of a tile for the requests made in
+  // front of the previous tile's last stores (the loop header merges the prologue's 16 loads with the rotated state).
+  constexpr bool ROT = FAST >= 2;
+  Tile cur, nxt;
+  auto do_tile = [&](int64_t tile, auto nextc, auto firstc) __attribute__((always_inline)) {
+    constexpr bool has_next = ROT && decltype(nextc)::value;
+    constexpr bool first = !ROT || decltype(firstc)::value;   // this tile's own taps are still to be requested
+    // The copies start alike.  A marker that differs from copy to copy, in front of the first tile's requests, keeps
+    // hipcc from hoisting their common head in front of the branch that chooses between them (it took every operand
+    // split of the conv there: 56 registers, and all but one wait in front of the first product).
+    asm volatile("; tile body %0" ::"n"(2 * (int)has_next + (int)first) : "memory");
+    if constexpr (first) {
+      // ---- activation loads of all taps, issued up front (unconditional, clamped row) ----
+      cur = tile_at(tile);
+      wn_static_for<KS>([&](auto tapc) { request_tap(cur, tapc); });
+      request_cb(cur);
+    }
+    if constexpr (has_next) nxt = tile_at(tile + walk.stride);
+    const bool tin = cur.tin;
+    const int rows_valid = cur.rows_valid;               // 1 .. 32: every tile of the walk starts inside its utterance
+    const int64_t row0 = cur.row0;
     // Pin the requests HERE.  Without it hipcc's scheduler sinks most of them into the conv below, each right in front of its
     // first use with s_waitcnt vmcnt(0) behind it (to shorten the live ranges of the 2 * R / 8 quads): the conv then walks
     // six exposed global round trips per tile (found with s_memtime stamps: 8.1 k clocks for 96 MFMAs).
@@ -142,6 +192,9 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
     if (a.cb) {   // wave-uniform
       f32x4* cbl = reinterpret_cast<f32x4*>(stage);
       if (4 * lane < 2 * D) cbl[lane] = cbv;
+      if constexpr (ROT) {
+        if constexpr (has_next) request_cb(nxt);                   // the bias of the tile that will use it: its utterance may differ
+      }
 #pragma unroll
       for (int j = 0; j < JU; ++j)
 #pragma unroll
@@ -168,7 +221,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
         if constexpr (j == 0) {
           constexpr int tap = ks / (R / 16), kk = ks % (R / 16);
           f32x4 q0 = xq[tap][2 * kk], q1 = xq[tap][2 * kk + 1];
-          if (!xvalid[tap]) { q0 = f32x4{0.f, 0.f, 0.f, 0.f}; q1 = q0; }
+          if (!cur.xvalid[tap]) { q0 = f32x4{0.f, 0.f, 0.f, 0.f}; q1 = q0; }
           split8(q0, q1, bh, bl);
         }
         if constexpr (blk + 2 < NB) {
@@ -177,6 +230,11 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
         }
         mfma3(fr[blk % 3][0], fr[blk % 3][1], bh, bl, u[j]);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (has_next && j == 0 && (ks + 1) % (R / 16) == 0 && ks / (R / 16) < KS - 1) {
+          // this k-step was the last of an older tap: its quads now take the next tile's
+          request_tap(nxt, std::integral_constant<int, ks / (R / 16)>{});
+          __builtin_amdgcn_sched_barrier(0);
+        }
       });
     }
 
@@ -192,7 +250,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
           u[j + D32][r] = wn_sigmoid_fast(u[j + D32][r]);
           u[j][r] = wn_tanh_fast(u[j][r]) * u[j + D32][r];
         }
-      if (rows_valid > 0) {
+      {
         f32x16 gv[D32];
 #pragma unroll
         for (int j = 0; j < D32; ++j) gv[j] = u[j + D32];
@@ -204,7 +262,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
 #pragma unroll
         for (int r = 0; r < 16; ++r) u[j][r] = wn_tanh_fast(u[j][r]) * wn_sigmoid_fast(u[j + D32][r]);
     }
-    if (a.z_out && rows_valid > 0) {
+    if (a.z_out) {
       f32x16 zv[D32];
 #pragma unroll
       for (int j = 0; j < D32; ++j) zv[j] = u[j];
@@ -245,28 +303,51 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
       });
     }
 
-    if (rows_valid > 0) {
-      if (a.o_out) wn_store_tile<R32, PITCH>(o, stage, a.o_out + row0 * R, R, rows_valid, lane);
-      if (a.residual) {
+    if (a.o_out) wn_store_tile<R32, PITCH>(o, stage, a.o_out + row0 * R, R, rows_valid, lane);
+    if (a.residual) {
 #pragma unroll
-        for (int j = 0; j < R32; ++j)
+      for (int j = 0; j < R32; ++j)
 #pragma unroll
-          for (int rq = 0; rq < 4; ++rq) {
-            f32x4 xr;
-            if (a.res) xr = tin ? *reinterpret_cast<const f32x4*>(a.res + (row0 + tl) * R + 32 * j + 8 * rq + 4 * h)
-                                : f32x4{0.f, 0.f, 0.f, 0.f};
-            else xr = xq[KS - 1][j * 4 + rq];
-            o[j][4 * rq + 0] += xr.x; o[j][4 * rq + 1] += xr.y; o[j][4 * rq + 2] += xr.z; o[j][4 * rq + 3] += xr.w;
-          }
-      }
-      if (tin) {
-#pragma unroll
-        for (int j = 0; j < R32; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) wmax = fmaxf(wmax, fabsf(o[j][r]));
-      }
-      wn_store_tile<R32, PITCH>(o, stage, a.x_out + row0 * R, R, rows_valid, lane);
+        for (int rq = 0; rq < 4; ++rq) {
+          f32x4 xr;
+          if (a.res) xr = tin ? *reinterpret_cast<const f32x4*>(a.res + (row0 + tl) * R + 32 * j + 8 * rq + 4 * h)
+                              : f32x4{0.f, 0.f, 0.f, 0.f};
+          else xr = xq[KS - 1][j * 4 + rq];
+          o[j][4 * rq + 0] += xr.x; o[j][4 * rq + 1] += xr.y; o[j][4 * rq + 2] += xr.z; o[j][4 * rq + 3] += xr.w;
+        }
     }
+    if constexpr (has_next) {
+      // the newest tap was the residual: the next tile's goes out in front of this tile's x_out stores
+      __builtin_amdgcn_sched_barrier(0);
+      request_tap(nxt, std::integral_constant<int, KS - 1>{});
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (tin) {
+#pragma unroll
+      for (int j = 0; j < R32; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) wmax = fmaxf(wmax, fabsf(o[j][r]));
+    }
+    wn_store_tile<R32, PITCH>(o, stage, a.x_out + row0 * R, R, rows_valid, lane);
+    if constexpr (has_next) cur = nxt;
+  };
+  using Next = std::true_type;
+  using Last = std::false_type;
+  using First = std::true_type;
+  using Later = std::false_type;                          // enters with the rotated requests and the last stores in flight
+  if constexpr (ROT) {
+    if (walk.first < walk.end) {
+      int64_t tile = walk.first;
+      if (tile + walk.stride < walk.end) {
+        do_tile(tile, Next{}, First{});
+        for (tile += walk.stride; tile + walk.stride < walk.end; tile += walk.stride) do_tile(tile, Next{}, Later{});
+        do_tile(tile, Last{}, Later{});
+      } else {
+        do_tile(tile, Last{}, First{});                   // the wave's only tile (every launch of up to 2048 tiles)
+      }
+    }
+  } else {
+    for (int64_t tile = walk.first; tile < walk.end; tile += walk.stride) do_tile(tile, Last{}, First{});
   }
   if (a.absmax_out) {
     if (!(wmax < 3.0e38f)) wmax = 3.0e38f;               // inf / NaN: beyond any limit
