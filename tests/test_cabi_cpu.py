@@ -168,3 +168,40 @@ def test_plan_describe_names_the_kernel_family_of_every_phase():
     assert 'exact fp32' in describe(_cfg(channels=64, **base))
   finally:
     lib.wn_debug_set(1, 0)
+
+
+def _describe_cases():
+  """The configurations whose training paths the GPU suite covers: every model of the parity tests, the 7 x 128-channel
+  mixture net of test_wide_blocks_gradients_ragged and the 30-block 64- / 128-channel baseline nets."""
+  from test_gpu_parity import MODEL_CASES
+  from test_gpu_baseline_nets import NETS
+  cases = dict(MODEL_CASES)
+  cases['wide7_mol_r128'] = dict(blocks=7, channels=128, skip_channels=256, dilation_bound=128, final_layers_channels=[128, 256],
+                                 activation='leaky_relu', num_mixtures=10, sampling_function='logistic', bits=16)
+  cases['configs1_cat_r64'] = NETS['configs1_cat_r64']
+  cases['configs3_mol10_r128'] = NETS['configs3_mol10_r128']
+  return cases
+
+
+def test_plan_describe_text_is_the_recorded_one(lib):
+  """wn_plan_describe reads the same path decision as the training step (wnp::train_paths).  Its full text, in split and
+  exact mode, equals tests/golden/plan_describe.json, recorded from the library before the decision had one home."""
+  import json
+  golden = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'plan_describe.json')))
+  cases = _describe_cases()
+  assert set(golden) == set(cases)
+  try:
+    for name, kw in cases.items():
+      kw = dict(kw)
+      cond_inputs = kw.pop('cond_inputs', 0)
+      for mode, knob in (('split', 0), ('fp32', 1)):
+        lib.wn_debug_set(1, knob)
+        p = C.c_void_p(_plan(lib, _cfg(**kw), cond_inputs))
+        assert p.value, lib.wn_last_error_string()
+        buf = C.create_string_buffer(4096)
+        assert lib.wn_plan_describe(p, buf, 4096) == 0
+        lib.wn_plan_destroy(p)
+        assert buf.value.decode() == golden[name][mode], (name, mode)
+  finally:
+    lib.wn_debug_set(1, 0)
+

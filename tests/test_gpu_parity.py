@@ -1124,6 +1124,32 @@ def test_plan_caches_survive_shape_changes():
   assert all(math.isfinite(v) for v in losses)
 
 
+@pytest.mark.parametrize('name', ['cat_r64', 'cat_r128', 'cat_lpb2_r64'])
+def test_weight_gradient_schedule_follows_every_key_change(name):
+  """The cached weight-gradient schedule is keyed by (B, T, time splits, kernel paths): one model through
+  split -> exact fp32 -> split -> another (B, T) -> back.  Every revisit of a state gives the gradients of its first
+  visit bit for bit, and those of a fresh model built directly in that state (layer kernel + kind-7 M jobs; transposed-read
+  pairs; deep16 + the INNER form).  Correctness against the oracle is the parity tests' job."""
+  import contextlib
+  kw = dict(MODEL_CASES[name])
+  xs = {bt: O.synthetic_waveform(bt[0], bt[1] + 1, seed=21 + bt[0]).to(dev()) for bt in ((2, 97), (3, 40))}
+
+  def grads_of(model, exact, bt):
+    with (model.exact_fp32() if exact else contextlib.nullcontext()):
+      loss, _, _ = model.loss_and_grads(xs[bt])
+    return [loss.clone()] + [g.clone() for g in model.gradients()]
+  _, _, model = make_pair(seed=6, **kw)
+  first = {}
+  for state in ((False, (2, 97)), (True, (2, 97)), (False, (2, 97)), (False, (3, 40)), (False, (2, 97))):
+    got = grads_of(model, *state)
+    if state not in first:
+      first[state] = got
+      fresh = grads_of(make_pair(seed=6, **kw)[2], *state)
+      assert all(torch.equal(a, b) for a, b in zip(got, fresh)), ('fresh', state)
+    assert all(torch.equal(a, b) for a, b in zip(got, first[state])), ('revisit', state)
+  assert any(not torch.equal(a, b) for a, b in zip(first[(False, (2, 97))], first[(True, (2, 97))]))   # two math modes really ran
+
+
 @pytest.mark.parametrize('B,T', [(1, 20), (3, 97)])
 def test_wide_blocks_gradients_ragged(B, T, math_mode):
   """128-channel blocks (BASELINE configs[3] width): the forward is two split-precision contractions with the

@@ -141,10 +141,13 @@ struct WnWgPair {
   int64_t x_off, g_off;            // workspace offsets of X [rows][K] and G [rows][N]
   int64_t w_off, b_off;            // dW[k][n] -> slab row + w_off + k * N + n; db -> slab row + b_off (or < 0)
   int64_t gmax_off;                // running max-abs of G, or < 0
-  int32_t shift, pad_;             // X row = t - shift
+  int32_t shift;                   // X row = t - shift
+  union { int32_t pad_; int32_t nseg; };   // segmented X (kinds 7 / 8): segments of X this job reads
   // transposed-read kernel, two-source form (kind 6): the upper half of G's columns comes from a second tensor and its
   // product goes to a second slab -- dW_r = z^T g_o and M = z^T dL/da (folded skip path) from ONE read of z
-  int64_t g2_off, w2_off, b2_off, gmax2_off;
+  // (segmented X: seg_stride = floats between two segments of X, in g2_off's place)
+  union { int64_t g2_off; int64_t seg_stride; };
+  int64_t w2_off, b2_off, gmax2_off;
 };
 int wn_wgrad_pair_kind(int K, int N);
 int wn_launch_wgrad_pairs(int kind, const WnWgPair* d_jobs, int njobs, float* ws, float* slab, int64_t P, int B, int T,

@@ -140,11 +140,7 @@ void exec_release(wn_exec* e) {
   for (hipEvent_t ev : e->stack_ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->foldprep_ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->phase_ev) if (ev) (void)hipEventDestroy(ev);
-  if (e->d_jobs) (void)hipFree(e->d_jobs);
-  if (e->d_cov) (void)hipFree(e->d_cov);
-  if (e->d_wgl) (void)hipFree(e->d_wgl);
-  if (e->d_wgli) (void)hipFree(e->d_wgli);
-  if (e->d_pairs) (void)hipFree(e->d_pairs);
+  e->wg.release();
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
   if (e->ev_ffork) (void)hipEventDestroy(e->ev_ffork);
@@ -215,6 +211,48 @@ bool head_pairs_ok(const wn_plan* p) {
   return false;
 }
 
+// Which kernel families the gradient half of a training step takes for this plan under knob 1 (the one decision: the
+// schedule builder, the launch phases and wn_plan_describe read it)
+TrainPaths train_paths(const wn_plan* p) {
+  TrainPaths t;
+  const bool split = wn_debug_get(1) != 1;
+  t.fold = fold_ok(p);
+  t.deep16 = deep16(p);
+  t.head_pairs = head_pairs_ok(p);
+  // the dedicated skip weight-gradient kernel applies to the split-precision path with uniform blocks
+  t.skipk = p->c.use_skip && p->S > 0 && p->Dp == p->D && p->N >= 1 && split && wn_wgrad_skip_supported(p->D, p->S, p->N * p->D);
+  // 32 / 64-channel blocks: one workgroup per (block, utterance, time range) (wn_wgrad_layer.hip; stacks deeper than 1 in
+  // split-precision training: the last conv + the 1x1 as for depth 1, every inner conv through the kernel's INNER form)
+  const bool layerk = (p->LPB == 1 || t.deep16) && wn_wgrad_layer_supported(p->R, p->D, p->KS) && p->Dp == p->R && split;
+  // 128-channel blocks: two transposed-LDS-read jobs per block (wn_wgrad_tr.hip): both taps of the gated conv against ONE
+  // read of du; dW_r
+  const bool pairk = !layerk && p->LPB == 1 && p->KS == 2 && p->R == p->D && p->Dp == p->D && split &&
+                     wn_wgrad_pair_kind(p->R, 2 * p->D) == 1 && wn_wgrad_pair_kind(p->D, p->R) == 2;
+  // other shapes stay on the generic job table (deeper stacks without split-precision images: in exact fp32)
+  t.wg = layerk ? (p->LPB > 1 ? WG_LAYER_INNER : WG_LAYER) : pairk ? WG_TR_PAIRS : (p->LPB > 1 && !t.deep16) ? WG_GENERIC_FP32 : WG_GENERIC;
+  // the folded skip path's M = Z^T dL/da: in the dW_r jobs of 128-channel blocks (one read of z); 64- / 32-channel
+  // blocks: transposed-read jobs over the z of four / eight blocks at a time against one read of dL/da (wn_wgrad_tr
+  // kinds 7 / 8); other widths: wn_wgrad_skip_kernel
+  const bool m128 = t.fold && p->fold_F0 == 128 && p->Dp == p->D && p->S > 0;
+  t.mfused = pairk && p->D == 128 && m128;
+  t.mtr = (layerk && m128) ? (p->D == 64 ? 7 : (p->D == 32 ? 8 : 0)) : 0;
+  // backward chain, two products per launch (wn_bwd_pair.hip / wn_bwd16s.hip)
+  if (t.fold && p->N >= 2 && p->c.use_residual && (p->c.cond_inputs == 0 || p->frag_condB >= 0) && p->Dp == p->D &&
+      (wn_bwd_pair_supported(p->R, p->D, p->KS, p->fold_F0) || wn_bwd_s128_supported(p->R, p->D, p->KS, p->fold_F0)))
+    t.bwd = p->R == 128 ? BWD_S128 : BWD_PAIR;
+  return t;
+}
+
+TrainPaths train_paths(const wn_plan* p, const wn_exec& e, const WsLayout& L, int64_t rows) {
+  TrainPaths t = train_paths(p);
+  t.drop = e.drop_rate > 0.f;
+  t.head_split = L.hsplits > 0;
+  t.in_split = L.isplits > 0;
+  // (the streamed R = 128 pair kernel indexes with 32-bit byte offsets: the two-launch chain takes over beyond)
+  t.rows32 = rows * 2 * p->D * 4 < ((int64_t)1 << 32);
+  return t;
+}
+
 WsLayout make_layout(const wn_plan* p, int B, int T, bool training) {
   WsLayout L;
   Carver cv;
@@ -253,7 +291,7 @@ WsLayout make_layout(const wn_plan* p, int B, int T, bool training) {
   L.loss_rows = cv.take(rows);
   L.yt = cv.take(rows);
   L.sum_scratch = cv.take(2048 + 64);
-  L.n_absmax = (int)p->finals.size() + 1 + p->N + (p->N + 1) + p->N * (p->LPB - 1);   // ... | GP[b][i] (deep stacks)
+  L.n_absmax = AbsmaxSlots{(int)p->finals.size(), p->N, p->LPB}.count();
   L.absmax = cv.take(L.n_absmax);
   L.fwd_absmax = cv.take(1);
   // conditioning
@@ -787,29 +825,30 @@ extern "C" int wn_plan_describe(const wn_plan* p, char* buf, int32_t len) {
     fwd = "two split-precision contractions per block (gated conv + gate, 1x1 + residual)";
   else if (p->fused_ok) fwd = "fused exact-fp32 block kernel (wn_layer_fwd_kernel)";
   else fwd = "composed: rows GEMM -> gate kernel -> rows GEMM";
-  const bool fold = fold_ok(p);
+  const TrainPaths tp = train_paths(p);
+  const bool fold = tp.fold;
   const char* bwd;
   if (p->LPB > 1) bwd = "per-block composed backward, one rows contraction per conv of the stack (layers_per_block > 1)";
-  else if (fold && p->N >= 2 && wn_bwd_pair_supported(p->R, p->D, p->KS, p->fold_F0) && p->Dp == p->D)
-    bwd = "two products per launch (wn_bwd_pair_kernel: g_x(b+1) and g_u(b))";
-  else if (fold && p->N >= 2 && wn_bwd_s128_supported(p->R, p->D, p->KS, p->fold_F0) && p->Dp == p->D)
+  else if (tp.bwd == BWD_PAIR) bwd = "two products per launch (wn_bwd_pair_kernel: g_x(b+1) and g_u(b))";
+  else if (tp.bwd == BWD_S128)
     bwd = "two products per launch, weights streamed through an LDS ring (wn_bwd_s128_kernel: g_x(b+1) and g_u(b))";
   else if (!exact) bwd = "two split-precision rows contractions per block (g_u with the gate derivative, g_x)";
   else bwd = "two exact-fp32 rows contractions per block";
-  const char* wg;
-  if (p->LPB > 1 && deep16(p) && wn_wgrad_layer_supported(p->R, p->D, p->KS) && p->Dp == p->R)
-    wg = "one workgroup per (conv, utterance, time range): the last conv + 1x1 of a block as for depth 1, inner convs through the kernel's INNER form (wn_wgrad_layer_kernel)";
-  else if (p->LPB > 1 && deep16(p)) wg = "generic batched job table, split precision, every conv of every stack in one launch (wn_wgrad_batched_kernel)";
-  else if (p->LPB > 1) wg = "generic batched job table in exact fp32, every conv of every stack in one launch (wn_wgrad_batched_kernel)";
-  else if (!exact && wn_wgrad_layer_supported(p->R, p->D, p->KS) && p->Dp == p->R)
-    wg = "one workgroup per (block, utterance, time range) for dW_d, db_d, dW_r, db_r (wn_wgrad_layer_kernel)";
-  else if (!exact && p->KS == 2 && p->R == p->D && p->Dp == p->D &&
-           wn_wgrad_pair_kind(p->R, 2 * p->D) == 1 && wn_wgrad_pair_kind(p->D, p->R) == 2)
-    wg = (fold && p->fold_F0 == 128 && p->D == 128)
-             ? "two jobs per block on transposed LDS reads: both taps of dW_d from one read of du; dW_r together with the "
-               "folded skip path's M = Z^T dL/da from one read of z (wn_wgrad_tr_kernel)"
-             : "two jobs per block on transposed LDS reads: both taps of dW_d from one read of du; dW_r (wn_wgrad_tr_kernel)";
-  else wg = "generic batched job table (wn_wgrad_batched_kernel)";
+  const char* wg = "";
+  switch (tp.wg) {
+    case WG_LAYER_INNER: wg = "one workgroup per (conv, utterance, time range): the last conv + 1x1 of a block as for depth 1, inner convs through the kernel's INNER form (wn_wgrad_layer_kernel)"; break;
+    case WG_LAYER: wg = "one workgroup per (block, utterance, time range) for dW_d, db_d, dW_r, db_r (wn_wgrad_layer_kernel)"; break;
+    case WG_TR_PAIRS:
+      wg = tp.mfused ? "two jobs per block on transposed LDS reads: both taps of dW_d from one read of du; dW_r together with the "
+                       "folded skip path's M = Z^T dL/da from one read of z (wn_wgrad_tr_kernel)"
+                     : "two jobs per block on transposed LDS reads: both taps of dW_d from one read of du; dW_r (wn_wgrad_tr_kernel)";
+      break;
+    case WG_GENERIC_FP32: wg = "generic batched job table in exact fp32, every conv of every stack in one launch (wn_wgrad_batched_kernel)"; break;
+    case WG_GENERIC:
+      wg = p->LPB > 1 ? "generic batched job table, split precision, every conv of every stack in one launch (wn_wgrad_batched_kernel)"
+                      : "generic batched job table (wn_wgrad_batched_kernel)";
+      break;
+  }
   snprintf(buf, (size_t)len,
            "math: %s | block forward: %s | skip path: %s | backward data: %s | block weight gradients: %s",
            exact ? "exact fp32 MFMA" : "fp16 hi|lo split, 3 products, fp32 accumulate", fwd,

@@ -52,6 +52,86 @@ struct BlockInfo {
   BlockInfo() { for (int i = 0; i < 16; ++i) d16F[i] = d16B[i] = -1; }
 };
 
+// The running max-abs scalars of the gradient tensors (operand scaling of the split-precision products), as indices from
+// WsLayout::absmax: GF[i] | g_skipsum | GU[b] | GH[b] (N + 1 of them) | GP[b][i] (inner convs of deeper stacks)
+struct AbsmaxSlots {
+  int nf, N, LPB;
+  int gf(int i) const { return i; }
+  int gskip() const { return nf; }
+  int gu(int b) const { return nf + 1 + b; }
+  int gh(int b) const { return nf + 1 + N + b; }
+  int gp(int b, int i) const { return nf + 1 + N + (N + 1) + b * (LPB - 1) + i; }
+  int count() const { return gp(N, 0); }
+};
+
+// Which kernel family each part of the gradient half of a training step takes: decided once (train_paths, wn_plan.hip),
+// read by the schedule builder, the launch phases and wn_plan_describe.
+// block weight gradients: wn_wgrad_layer_kernel | ... with its INNER form for the inner convs of deeper stacks | two
+// wn_wgrad_tr_kernel jobs per block | generic job table | ... forced to exact fp32 (deeper stacks without split images)
+enum WgFamily { WG_LAYER, WG_LAYER_INNER, WG_TR_PAIRS, WG_GENERIC, WG_GENERIC_FP32 };
+enum BwdFamily { BWD_BLOCKS, BWD_PAIR, BWD_S128 };   // per-block backward | wn_bwd_pair_kernel | wn_bwd_s128_kernel
+struct TrainPaths {
+  // from the plan and knob 1
+  WgFamily wg = WG_GENERIC;
+  BwdFamily bwd = BWD_BLOCKS;
+  int mtr = 0;             // M = Z^T dL/da of the folded skip path as wn_wgrad_tr jobs over several blocks' z (kind 7 / 8), or 0
+  bool mfused = false;     // ... or riding in the dW_r jobs of WG_TR_PAIRS
+  // the skip convs' own weight-gradient kernel | skip path folded into the head's first conv | deeper stacks train in split
+  // precision (inner gradients carry max-abs slots) | some head layer has a staged pair kind
+  bool skipk = false, fold = false, deep16 = false, head_pairs = false;
+  // from the call: dropout on, the head / the input conv on a time split of their own, the pair chain's 32-bit row limit
+  bool drop = false, head_split = false, in_split = false, rows32 = true;
+  bool layerk() const { return wg == WG_LAYER || wg == WG_LAYER_INNER; }
+  bool pairk() const { return wg == WG_TR_PAIRS; }
+  bool headpairs() const { return head_pairs && head_split; }
+  bool bwd_pairs() const { return bwd != BWD_BLOCKS && !drop && (bwd != BWD_S128 || rows32); }
+  bool operator==(const TrainPaths& o) const {
+    return wg == o.wg && bwd == o.bwd && mtr == o.mtr && mfused == o.mfused && skipk == o.skipk && fold == o.fold &&
+           deep16 == o.deep16 && head_pairs == o.head_pairs && drop == o.drop && head_split == o.head_split &&
+           in_split == o.in_split && rows32 == o.rows32;
+  }
+};
+
+// owning device copy of a host table
+template <class T> struct DevTable {
+  T* d = nullptr;
+  void release() { if (d) (void)hipFree(d); d = nullptr; }
+  int upload(const std::vector<T>& v, size_t min_count = 0) {
+    release();
+    const size_t n = std::max(v.size(), min_count);
+    if (n == 0) return WN_OK;
+    WN_HIP_CHECK(hipMalloc((void**)&d, n * sizeof(T)));
+    if (!v.empty()) WN_HIP_CHECK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return WN_OK;
+  }
+};
+
+// one launch of the weight-gradient phase, everything about it resolved when the schedule is built
+struct WgSpan {
+  enum Op : uint8_t { INCONV, JOBS, PAIRS, TR, LAYERS, SKIP } op;
+  enum Slab : uint8_t { BATCH, HEAD, MFOLD } slab;   // batched slab | the head's compact slab and time split | the slab of M
+  int kind;            // PAIRS / TR: the kernel's kind; JOBS: 1 = exact fp32; LAYERS: 1 = the inner table, INNER form
+  int first, count;    // entries of the op's table
+};
+
+// The weight-gradient schedule of one workspace layout: device tables and the launches over them.  Valid for its key
+// (B, T, bsplits, paths) only; `valid` is false from before the first upload of a rebuild until the last one succeeds.
+struct WgSchedule {
+  bool valid = false;
+  int B = 0, T = 0, bsplits = 0;
+  TrainPaths paths;
+  DevTable<WnWgJob> jobs;
+  DevTable<WnWgLayer> layers, inner;
+  DevTable<WnWgPair> pairs;
+  DevTable<WnTensorDesc> cov;
+  std::vector<WnTensorDesc> h_cov;   // host copy of the coverage table (the flattened reduce sizes its grid from it)
+  std::vector<WgSpan> spans;         // in issue order: the first n_side on the side stream when the step forks
+  int n_side = 0;
+  bool overlap = false;              // the side-stream spans may run beside the others
+  int cov_head = 0;                  // coverage table: from here on the entries are reduced from the head's own slab
+  void release() { valid = false; jobs.release(); layers.release(); inner.release(); pairs.release(); cov.release(); }
+};
+
 }  // namespace wnp
 
 // The mutable side of a plan: per-caller state of the orchestration ("a wn_plan is immutable and shareable
@@ -62,38 +142,15 @@ struct BlockInfo {
 // plan's own.
 struct wn_exec {
   const struct wn_plan* plan = nullptr;
-  std::vector<WnTensorDesc> h_cov;      // host copy of the coverage table of the cached jobs (the flattened reduce sizes its grid from it)
   float drop_rate = 0.f;        // Dropout rate applied to every block input in training (src/layers.py:108-111)
   uint64_t drop_seed = 0, drop_step = 0;
   // armed by wn_plan_arm_step_sample: the next training step also draws sample_waveform(pred)
   float* step_sample = nullptr; int step_sample_det = 0; uint64_t step_sample_seed = 0, step_sample_off = 0;
-  // batched weight-gradient job table (device), valid for one (B, T) workspace layout
-  WnWgJob* d_jobs = nullptr;
-  WnTensorDesc* d_cov = nullptr;
-  int njobs = 0, ncov = 0, jobs_B = 0, jobs_T = 0, jobs_splits = 0;
-  bool jobs_drop = false;
-  bool jobs_skipk = false;
-  bool jobs_layerk = false;   // per-block dW_d / dW_r come from the layer weight-gradient kernel
-  WnWgLayer* d_wgl = nullptr;
-  WnWgLayer* d_wgli = nullptr;  // inner convs of deeper stacks (wn_wgrad_layer_kernel<.., INNER>)
-  int n_wgli = 0;
-  // per-block weight gradients as staged pair jobs (widths the per-block kernel does not cover), by kind
-  WnWgPair* d_pairs = nullptr;
-  int pair_first[3] = {0, 0, 0}, pair_count[3] = {0, 0, 0};
-  bool jobs_pairk = false;
-  bool jobs_mfused = false;             // M = Z^T dL/da of the folded skip path rides in the dW_r jobs
-  bool jobs_deep16 = false;             // inner gradients of deeper stacks carry max-abs slots (split-precision job kernel)
-  int jobs_mtr = 0;                     // ... or is its own transposed-read launch over several blocks' z (kind 7 / 8; pairs index 0)
-  // the head layers' weight gradients as staged pair jobs (kinds 1..4) on the head's own time split
-  int hpair_first[6] = {0, 0, 0, 0, 0, 0}, hpair_count[6] = {0, 0, 0, 0, 0, 0};
-  bool jobs_headpairs = false;
-  bool jobs_inconvk = false;    // input conv's dW / db from the dedicated reduction kernel, not from jobs
-  bool jobs_fold = false;       // tables built for the folded skip path (no conv_skip / first-head-conv entries)
+  wnp::WgSchedule wg;           // the cached weight-gradient schedule of the last (B, T) layout it trained
   // side stream: the low-occupancy generic weight-gradient jobs overlap the per-block / skip kernels
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   hipEvent_t ev_ffork = nullptr, ev_fjoin = nullptr;   // forward pass: the fold's weight preparation beside the block chain
-  int head_first = 0, cov_head_first = 0;   // job / coverage tables: the head's entries come last
   WnGenBlock* d_gen = nullptr;  // fused generation step: per-block offsets for one batch size
   WnGenBlock gen_blk0[3]{};
   int64_t gen_bias_stride = 0;
@@ -195,7 +252,7 @@ struct WsLayout {
   int64_t vfold, bfold, wsall, mslab, mtot, ytmp;
   std::vector<int64_t> XD;              // dropout: dropped copy of every block input (training)
   int64_t gxd;                          // dropout: scratch for d loss / d (dropped input)
-  int64_t absmax; int n_absmax;         // running max-abs scalars: GF[i] | g_skipsum | GU[b] | GH[b] | GP[b][i]
+  int64_t absmax; int n_absmax;         // running max-abs scalars of the gradient tensors (AbsmaxSlots)
   int64_t fwd_absmax;                   // forward range guard: running max-abs of H[b], skip sum, head activations
   int64_t sum_scratch;
   std::vector<int64_t> M;               // mapping activations [B][w]
@@ -347,6 +404,8 @@ bool deep16(const wn_plan* p);
 bool cond_small(const wn_plan* p);
 bool fold_ok(const wn_plan* p);
 bool head_pairs_ok(const wn_plan* p);
+TrainPaths train_paths(const wn_plan* p);   // the plan-level part; the per-call part as of a call without dropout or splits
+TrainPaths train_paths(const wn_plan* p, const wn_exec& e, const WsLayout& L, int64_t rows);
 int64_t slab_need(int B, int T, int K, int N);
 // ---- wn_block.hip ----
 int wgrad(const float* x, int ldx, int K, int shift, const float* g, int ldg, int N, int B, int T,

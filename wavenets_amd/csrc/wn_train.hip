@@ -20,49 +20,24 @@ void add_jobs(std::vector<WnWgJob>& jobs, int64_t x_off, int ldx, int K, int shi
     }
 }
 
-// the dedicated skip weight-gradient kernel applies to the split-precision path with uniform blocks
-bool skip_kernel_ok(const wn_plan* p) {
-  return p->c.use_skip && p->S > 0 && p->Dp == p->D && p->N >= 1 && wn_debug_get(1) != 1 &&
-         wn_wgrad_skip_supported(p->D, p->S, p->N * p->D);
-}
-
-int ensure_jobs(wn_plan* p, const WsLayout& L, int B, int T) {
-  const bool skipk = skip_kernel_ok(p);
-  // 32 / 64-channel blocks: one workgroup per (block, utterance, time range) (wn_wgrad_layer.hip; stacks deeper than 1 in
-  // split-precision training, deep16: the last conv + the 1x1 as for depth 1, every inner conv through the kernel's INNER
-  // form); other shapes stay on the generic job table
-  const bool layerk = (p->LPB == 1 || deep16(p)) && wn_wgrad_layer_supported(p->R, p->D, p->KS) && p->Dp == p->R && wn_debug_get(1) != 1;
-  // 128-channel blocks: two transposed-LDS-read jobs per block (wn_wgrad_tr.hip): both taps of the gated conv against ONE
-  // read of du; dW_r
-  const bool pairk = !layerk && p->LPB == 1 && p->KS == 2 && p->R == p->D && p->Dp == p->D && wn_wgrad_pair_kind(p->R, 2 * p->D) == 1 &&
-                     wn_wgrad_pair_kind(p->D, p->R) == 2 && wn_debug_get(1) != 1;
-  // ... whose dW_r jobs also compute the folded skip path's M = Z^T dL/da (one read of z)
-  const bool mfused = pairk && p->D == 128 && fold_ok(p) && p->fold_F0 == 128 && p->Dp == p->D && p->S > 0;
-  // 64- / 32-channel blocks: M as transposed-read jobs over the z of four / eight blocks at a time against one read of
-  // dL/da (wn_wgrad_tr kinds 7 / 8); other widths: wn_wgrad_skip_kernel
-  const int mtr = (layerk && fold_ok(p) && p->fold_F0 == 128 && p->Dp == p->D && p->S > 0)
-                      ? (p->D == 64 ? 7 : (p->D == 32 ? 8 : 0)) : 0;
-  const bool fold = fold_ok(p);
-  const bool headpairs = head_pairs_ok(p) && L.hsplits > 0;
-  const bool inconvk = L.isplits > 0;
-  const bool d16 = deep16(p);
-  if (wnp::ex(p).d_jobs && wnp::ex(p).jobs_B == B && wnp::ex(p).jobs_T == T && wnp::ex(p).jobs_splits == L.bsplits &&
-      wnp::ex(p).jobs_drop == (wnp::ex(p).drop_rate > 0.f) && wnp::ex(p).jobs_skipk == skipk && wnp::ex(p).jobs_layerk == layerk &&
-      wnp::ex(p).jobs_pairk == pairk && wnp::ex(p).jobs_mfused == mfused && wnp::ex(p).jobs_mtr == mtr && wnp::ex(p).jobs_deep16 == d16 && wnp::ex(p).jobs_headpairs == headpairs && wnp::ex(p).jobs_inconvk == inconvk && wnp::ex(p).jobs_fold == fold) return WN_OK;
+// the cached schedule of e: rebuilt when (B, T, bsplits, paths) is not the key it was built for
+int ensure_schedule(const wn_plan* p, wn_exec& e, const WsLayout& L, int B, int T, const TrainPaths& tp) {
+  WgSchedule& g = e.wg;
+  if (g.valid && g.B == B && g.T == T && g.bsplits == L.bsplits && g.paths == tp) return WN_OK;
+  const bool layerk = tp.layerk(), pairk = tp.pairk(), fold = tp.fold;
   std::vector<WnWgLayer> wgl, wgli;
   std::vector<WnWgPair> pairs[3];
   std::vector<WnWgPair> hpairs[6];
   std::vector<WnWgJob> jobs;
   std::vector<WnTensorDesc> cov;
   auto cover = [&](int t) { WnTensorDesc d; d.off = p->tensors[t].off; d.len = p->tensors[t].len; cov.push_back(d); };
-  // running max-abs slots (same numbering as in wn_train_fwd_bwd): GF[i] | g_skipsum | GU[b] | GH[b]
-  const int nfin = (int)p->finals.size();
-  const int64_t am_skip = L.absmax + nfin;
-  auto am_GU = [&](int b) { return L.absmax + nfin + 1 + b; };
-  auto am_GH = [&](int b) { return L.absmax + nfin + 1 + p->N + b; };
-  auto am_GP = [&](int b, int i) { return d16 ? L.absmax + nfin + 1 + p->N + (p->N + 1) + (int64_t)b * (p->LPB - 1) + i : (int64_t)-1; };
+  const AbsmaxSlots slot{(int)p->finals.size(), p->N, p->LPB};
+  const int64_t am_skip = L.absmax + slot.gskip();
+  auto am_GU = [&](int b) { return L.absmax + slot.gu(b); };
+  auto am_GH = [&](int b) { return L.absmax + slot.gh(b); };
+  auto am_GP = [&](int b, int i) { return tp.deep16 ? L.absmax + slot.gp(b, i) : (int64_t)-1; };
   // input causal conv: x = inputs (B,T,1), g = d loss / d H[0]
-  if (!inconvk)
+  if (!tp.in_split)
     for (int t = 0; t < p->KS; ++t)
       add_jobs(jobs, L.probs, 1, 1, p->KS - 1 - t, L.GH[0], p->R, p->R,
                p->tensors[p->causal.kernel_t].off + (int64_t)t * p->R,
@@ -73,7 +48,7 @@ int ensure_jobs(wn_plan* p, const WsLayout& L, int B, int T) {
     const ConvInfo& c = bi.dil.back();
     const int64_t zoff = L.Z + (int64_t)b * B * T * p->Dp;      // block-major Z
     if (layerk) {
-      const int64_t xin0 = wnp::ex(p).drop_rate > 0.f ? L.XD[b] : L.H[b];
+      const int64_t xin0 = tp.drop ? L.XD[b] : L.H[b];
       for (int i = 0; i + 1 < p->LPB; ++i) {                     // inner convs of a deeper stack
         const ConvInfo& ci = bi.dil[i];
         WnWgLayer w;
@@ -97,7 +72,7 @@ int ensure_jobs(wn_plan* p, const WsLayout& L, int B, int T) {
       w.dilation = c.dil;
       wgl.push_back(w);
     } else if (pairk) {
-      const int64_t xoff = wnp::ex(p).drop_rate > 0.f ? L.XD[b] : L.H[b];
+      const int64_t xoff = tp.drop ? L.XD[b] : L.H[b];
       {
         // both taps in one job: x[t - d] | x[t] against ONE read of du
         WnWgPair w;
@@ -114,11 +89,11 @@ int ensure_jobs(wn_plan* p, const WsLayout& L, int B, int T) {
       w.w_off = p->tensors[bi.conv1.kernel_t].off; w.b_off = p->tensors[bi.conv1.bias_t].off;
       w.gmax_off = p->S == 0 ? am_skip : am_GH(b + 1);
       w.g2_off = w.w2_off = w.b2_off = w.gmax2_off = -1;
-      if (mfused) {
+      if (tp.mfused) {
         // the folded skip path's M(b) = z_b^T dL/da rides in the same job (one read of z_b): second slab = mslab
         w.g2_off = L.GF[0]; w.w2_off = (int64_t)b * p->D * p->fold_F0;
         w.b2_off = b == 0 ? (int64_t)p->N * p->D * p->fold_F0 : -1;       // colsum(dL/da) once
-        w.gmax2_off = L.absmax + 0;                                        // am_GF(0)
+        w.gmax2_off = L.absmax + slot.gf(0);
       }
       pairs[2].push_back(w);
     } else {
@@ -128,7 +103,7 @@ int ensure_jobs(wn_plan* p, const WsLayout& L, int B, int T) {
     for (int i = 0; i < p->LPB; ++i) {
       const ConvInfo& ci = bi.dil[i];
       const bool lastc = i == p->LPB - 1;
-      const int64_t xo = i == 0 ? (wnp::ex(p).drop_rate > 0.f ? L.XD[b] : L.H[b]) : L.P[b][i - 1];
+      const int64_t xo = i == 0 ? (tp.drop ? L.XD[b] : L.H[b]) : L.P[b][i - 1];
       const int kc = i == 0 ? p->R : p->D, nc = lastc ? 2 * p->D : p->D;
       for (int t = 0; t < p->KS; ++t)
         add_jobs(jobs, xo, kc, kc, (p->KS - 1 - t) * ci.dil, lastc ? L.GU[b] : L.GP[b][i], nc, nc,
@@ -143,39 +118,38 @@ int ensure_jobs(wn_plan* p, const WsLayout& L, int B, int T) {
     cover(bi.dil.back().kernel_t); cover(bi.dil.back().bias_t);
     cover(bi.conv1.kernel_t); cover(bi.conv1.bias_t);
     if (bi.has_skip && p->c.use_skip && !fold) {     // (folded: dW_s, db_s come out of M, see the weight-gradient phase)
-      if (!skipk)
+      if (!tp.skipk)
         add_jobs(jobs, zoff, p->Dp, p->D, 0, L.g_skipsum, p->S, p->S,
                  p->tensors[bi.conv_skip.kernel_t].off, p->tensors[bi.conv_skip.bias_t].off, am_skip);
       cover(bi.conv_skip.kernel_t); cover(bi.conv_skip.bias_t);
     }
   }
-  if (mtr != 0) {
+  if (tp.mtr != 0) {
     const int per = 256 / p->D;                               // blocks per job
     for (int b0 = 0; b0 < p->N; b0 += per) {
       WnWgPair w;
       memset(&w, 0, sizeof(w));
       w.x_off = L.Z + (int64_t)b0 * B * T * p->Dp;            // block-major Z: segment stride = one block's plane
-      w.g2_off = (int64_t)B * T * p->Dp;
-      w.pad_ = std::min(per, p->N - b0);
+      w.seg_stride = (int64_t)B * T * p->Dp;
+      w.nseg = std::min(per, p->N - b0);
       w.g_off = L.GF[0]; w.shift = 0;
       w.w_off = (int64_t)b0 * p->D * p->fold_F0;
       w.b_off = b0 == 0 ? (int64_t)p->N * p->D * p->fold_F0 : -1;       // colsum(dL/da) once
-      w.gmax_off = L.absmax + 0;                              // am_GF(0)
+      w.gmax_off = L.absmax + slot.gf(0);
       w.w2_off = w.b2_off = w.gmax2_off = -1;
       pairs[0].push_back(w);
     }
   }
-  wnp::ex(p).head_first = (int)jobs.size();
-  wnp::ex(p).cov_head_first = (int)cov.size();
+  const int head_first = (int)jobs.size(), cov_head = (int)cov.size();
   for (size_t i = fold ? 1 : 0; i < p->finals.size(); ++i) {      // (folded: the first conv's gradients come from M too)
     const ConvInfo& c = p->finals[i];
     const int64_t xin = (i == 0) ? (p->c.use_skip ? L.skipsum : L.H[p->N]) : L.HA[i - 1];
-    if (headpairs && wn_wgrad_pair_kind(c.cin, c.cout) != 0) {
+    if (tp.headpairs() && wn_wgrad_pair_kind(c.cin, c.cout) != 0) {
       WnWgPair w;
       memset(&w, 0, sizeof(w));
       w.x_off = xin; w.g_off = L.GF[i]; w.shift = 0;
       w.w_off = p->tensors[c.kernel_t].off; w.b_off = p->tensors[c.bias_t].off;
-      w.gmax_off = L.absmax + (int64_t)i;
+      w.gmax_off = L.absmax + slot.gf((int)i);
       const int kind = wn_wgrad_pair_kind(c.cin, c.cout);
       hpairs[kind].push_back(w);
       if (kind == 5) {                     // second 128-column half
@@ -184,51 +158,53 @@ int ensure_jobs(wn_plan* p, const WsLayout& L, int B, int T) {
       }
     } else {
       add_jobs(jobs, xin, c.cin, c.cin, 0, L.GF[i], c.cout, c.cout, p->tensors[c.kernel_t].off,
-               p->tensors[c.bias_t].off, L.absmax + (int64_t)i);
+               p->tensors[c.bias_t].off, L.absmax + slot.gf((int)i));
     }
     cover(c.kernel_t); cover(c.bias_t);
   }
-  if (wnp::ex(p).d_jobs) { (void)hipFree(wnp::ex(p).d_jobs); wnp::ex(p).d_jobs = nullptr; }
-  if (wnp::ex(p).d_cov) { (void)hipFree(wnp::ex(p).d_cov); wnp::ex(p).d_cov = nullptr; }
-  WN_HIP_CHECK(hipMalloc((void**)&wnp::ex(p).d_jobs, std::max<size_t>(jobs.size(), 1) * sizeof(WnWgJob)));
-  if (!jobs.empty()) WN_HIP_CHECK(hipMemcpy(wnp::ex(p).d_jobs, jobs.data(), jobs.size() * sizeof(WnWgJob), hipMemcpyHostToDevice));
-  WN_HIP_CHECK(hipMalloc((void**)&wnp::ex(p).d_cov, cov.size() * sizeof(WnTensorDesc)));
-  WN_HIP_CHECK(hipMemcpy(wnp::ex(p).d_cov, cov.data(), cov.size() * sizeof(WnTensorDesc), hipMemcpyHostToDevice));
-  wnp::ex(p).h_cov = cov;
-  if (wnp::ex(p).d_wgl) { (void)hipFree(wnp::ex(p).d_wgl); wnp::ex(p).d_wgl = nullptr; }
-  if (!wgl.empty()) {
-    WN_HIP_CHECK(hipMalloc((void**)&wnp::ex(p).d_wgl, wgl.size() * sizeof(WnWgLayer)));
-    WN_HIP_CHECK(hipMemcpy(wnp::ex(p).d_wgl, wgl.data(), wgl.size() * sizeof(WnWgLayer), hipMemcpyHostToDevice));
+  // ---- the launches over these tables, in issue order: first the low-occupancy leftovers (input conv, generic jobs, the
+  // head) that may run beside the rest on a side stream, then the per-block kernels and the skip path ----
+  std::vector<WnWgPair> all;     // one pair table: the blocks' jobs by kind, then the head's
+  int pfirst[3], hfirst[6] = {0, 0, 0, 0, 0, 0};
+  for (int kd = 0; kd <= 2; ++kd) { pfirst[kd] = (int)all.size(); all.insert(all.end(), pairs[kd].begin(), pairs[kd].end()); }
+  for (int kd = 1; kd <= 5; ++kd) { hfirst[kd] = (int)all.size(); all.insert(all.end(), hpairs[kd].begin(), hpairs[kd].end()); }
+  std::vector<WgSpan> spans;
+  auto span = [&](WgSpan::Op op, WgSpan::Slab slab, int kind, int first, size_t count) {
+    if (count > 0) spans.push_back(WgSpan{op, slab, kind, first, (int)count});
+  };
+  const int njobs = (int)jobs.size();
+  const bool head_own = tp.head_split && (head_first < njobs || tp.headpairs());
+  span(WgSpan::INCONV, WgSpan::BATCH, 0, 0, tp.in_split);      // the input conv's dW / db from the dedicated reduction kernel
+  span(WgSpan::JOBS, WgSpan::BATCH, tp.wg == WG_GENERIC_FP32, 0, head_own ? head_first : njobs);
+  if (head_own) span(WgSpan::JOBS, WgSpan::HEAD, 0, head_first, njobs - head_first);
+  for (int kd = 1; kd <= 5; ++kd) {
+    // staged kinds 1 (128 x 256), 3 (256 x 128), 5 (256 x 256 halves) have transposed-read forms (3, 4, 5)
+    const int trk = kd == 1 ? 3 : (kd == 3 ? 4 : (kd == 5 ? 5 : (kd == 2 ? 2 : 0)));
+    // (with 64-channel blocks the staged head jobs are faster beside the side stream's neighbours)
+    if (trk != 0 && tp.pairk()) span(WgSpan::TR, WgSpan::HEAD, trk, hfirst[kd], hpairs[kd].size());
+    else span(WgSpan::PAIRS, WgSpan::HEAD, kd, hfirst[kd], hpairs[kd].size());
   }
-  if (wnp::ex(p).d_wgli) { (void)hipFree(wnp::ex(p).d_wgli); wnp::ex(p).d_wgli = nullptr; }
-  wnp::ex(p).n_wgli = (int)wgli.size();
-  if (!wgli.empty()) {
-    WN_HIP_CHECK(hipMalloc((void**)&wnp::ex(p).d_wgli, wgli.size() * sizeof(WnWgLayer)));
-    WN_HIP_CHECK(hipMemcpy(wnp::ex(p).d_wgli, wgli.data(), wgli.size() * sizeof(WnWgLayer), hipMemcpyHostToDevice));
-  }
-  if (wnp::ex(p).d_pairs) { (void)hipFree(wnp::ex(p).d_pairs); wnp::ex(p).d_pairs = nullptr; }
-  {
-    std::vector<WnWgPair> all;
-    for (int kd = 0; kd <= 2; ++kd) {
-      wnp::ex(p).pair_first[kd] = (int)all.size();
-      wnp::ex(p).pair_count[kd] = (int)pairs[kd].size();
-      all.insert(all.end(), pairs[kd].begin(), pairs[kd].end());
-    }
-    for (int kd = 1; kd <= 5; ++kd) {
-      wnp::ex(p).hpair_first[kd] = (int)all.size();
-      wnp::ex(p).hpair_count[kd] = (int)hpairs[kd].size();
-      all.insert(all.end(), hpairs[kd].begin(), hpairs[kd].end());
-    }
-    if (!all.empty()) {
-      WN_HIP_CHECK(hipMalloc((void**)&wnp::ex(p).d_pairs, all.size() * sizeof(WnWgPair)));
-      WN_HIP_CHECK(hipMemcpy(wnp::ex(p).d_pairs, all.data(), all.size() * sizeof(WnWgPair), hipMemcpyHostToDevice));
-    }
-  }
-  wnp::ex(p).jobs_layerk = layerk; wnp::ex(p).jobs_pairk = pairk; wnp::ex(p).jobs_mfused = mfused; wnp::ex(p).jobs_mtr = mtr; wnp::ex(p).jobs_deep16 = d16; wnp::ex(p).jobs_headpairs = headpairs; wnp::ex(p).jobs_inconvk = inconvk;
-  wnp::ex(p).jobs_fold = fold;
-  wnp::ex(p).njobs = (int)jobs.size(); wnp::ex(p).ncov = (int)cov.size();
-  wnp::ex(p).jobs_B = B; wnp::ex(p).jobs_T = T; wnp::ex(p).jobs_splits = L.bsplits; wnp::ex(p).jobs_drop = wnp::ex(p).drop_rate > 0.f;
-  wnp::ex(p).jobs_skipk = skipk;
+  const int n_side = (int)spans.size();
+  // transposed-read kernels: both taps of dW_d in one job; dW_r (+ M)
+  span(WgSpan::TR, WgSpan::BATCH, 1, pfirst[1], pairs[1].size());
+  span(WgSpan::TR, WgSpan::BATCH, tp.mfused ? 6 : 2, pfirst[2], pairs[2].size());
+  span(WgSpan::LAYERS, WgSpan::BATCH, 0, 0, wgl.size());
+  span(WgSpan::LAYERS, WgSpan::BATCH, 1, 0, wgli.size());
+  // folded skip path: M = Z^T dL/da (N*D x F0) and colsum(dL/da) into their own slab; else dW_s, db_s of every block
+  if (tp.mtr != 0) span(WgSpan::TR, WgSpan::MFOLD, tp.mtr, pfirst[0], pairs[0].size());
+  else if (tp.fold) span(WgSpan::SKIP, WgSpan::MFOLD, 0, 0, !tp.mfused);
+  else span(WgSpan::SKIP, WgSpan::BATCH, 0, 0, tp.skipk);
+  g.valid = false;
+  int rc = g.jobs.upload(jobs, 1);
+  if (!rc) rc = g.cov.upload(cov);
+  if (!rc) rc = g.layers.upload(wgl);
+  if (!rc) rc = g.inner.upload(wgli);
+  if (!rc) rc = g.pairs.upload(all);
+  if (rc) return rc;
+  g.h_cov.swap(cov); g.spans.swap(spans);
+  g.n_side = n_side; g.overlap = layerk || pairk; g.cov_head = head_own ? cov_head : (int)g.h_cov.size();
+  g.B = B; g.T = T; g.bsplits = L.bsplits; g.paths = tp;
+  g.valid = true;
   return WN_OK;
 }
 
@@ -237,6 +213,7 @@ int ensure_jobs(wn_plan* p, const WsLayout& L, int B, int T) {
 // gradient tensors; the phases of the step are its member functions, in launch order.
 // ------------------------------------------------------------------------------------------
 struct TrainCall {
+  wn_exec& e;                        // the calling thread's execution state for p
   wn_plan* p; const float* params; const float* x_full; const float* cond;
   int B, T, global_batch, n_replicas;
   float* grads; float* loss_out; float* pred_out; float* ws; hipStream_t s;
@@ -244,20 +221,26 @@ struct TrainCall {
   int64_t rows;
   float* inputs;
   const float* fragbase; float* slab;
-  // running max-abs scalars of the gradient tensors (operand scaling of the split-precision GEMMs): GF[i] | g_skipsum | GU[b] | GH[b] | GP[b][i]
-  float* am; int nf; float* am_gskip;
+  float* am; AbsmaxSlots slot;       // running max-abs scalars of the gradient tensors (operand scaling of the split-precision GEMMs)
+  int nf; float* am_gskip;
   const float* mlast = nullptr;      // the mapped condition (input of every conv_cond)
-  bool fold = false, cond_batched = false;
-  float* am_GF(int i) const { return am + i; }
-  float* am_GU(int b) const { return am + nf + 1 + b; }
-  float* am_GH(int b) const { return am + nf + 1 + p->N + b; }
-  float* am_GP(int b, int i) const { return am + nf + 1 + p->N + (p->N + 1) + b * (p->LPB - 1) + i; }
+  TrainPaths tp;                     // backward half: the kernel families of this call
+  bool cond_batched = false;
+  int64_t pm = 0;                    // folded skip path: row pitch of the slab of M = Z^T dL/da with the column sums behind it
+  float* am_GF(int i) const { return am + slot.gf(i); }
+  float* am_GU(int b) const { return am + slot.gu(b); }
+  float* am_GH(int b) const { return am + slot.gh(b); }
+  float* am_GP(int b, int i) const { return am + slot.gp(b, i); }
+  // flat-buffer offset of a tensor of block 0 and its distance to block 1's (evenly spaced blocks)
+  struct Strided { int64_t off, stride; };
+  Strided strided(int t0, int t1) const { return {p->tensors[t0].off, p->N > 1 ? p->tensors[t1].off - p->tensors[t0].off : 0}; }
+  Strided skip_w{0, 0}, skip_b{0, 0};   // conv_skip kernels / biases
 
   // ---- forward + loss (+ the armed step sample, the L2 loss term, the range flag): src/model.py:319-334 ----
   int forward_and_loss() {
     int rc;
     { const int rcs = shift_split(x_full, B, T, inputs, ws + L.yt, s); if (rcs) return rcs; }
-    if (wnp::ex(p).phase_on) (void)hipEventRecord(wnp::ex(p).phase_ev[0], s);
+    if (e.phase_on) (void)hipEventRecord(e.phase_ev[0], s);
     // (zeroed before the forward pass: a fused loss epilogue publishes the max-abs of d loss / d logits from there)
     WN_HIP_CHECK(hipMemsetAsync(am, 0, L.n_absmax * sizeof(float), s));
     // 256-class categorical head: the loss rides in the head's last conv (LossFuse) unless the caller wants the probabilities
@@ -270,15 +253,15 @@ struct TrainCall {
       lf.target = reinterpret_cast<const int32_t*>(ws + L.target);
       lf.gscale = 1.0f / (float)global_batch;          // compute_average_loss, src/model.py:328-329
       lf.loss_rows = ws + L.loss_rows; lf.g_logits = ws + L.GF.back(); lf.absmax_out = am_GF(nf - 1);
-      if (wnp::ex(p).step_sample && !wnp::ex(p).step_sample_det) {     // the armed sample_waveform(pred) draw of the step (src/model.py:338)
-        lf.sample_out = wnp::ex(p).step_sample; lf.inv_lv = 1.0f / (float)(1 << (p->c.bits - 1));
-        lf.seed = wnp::ex(p).step_sample_seed; lf.offset = wnp::ex(p).step_sample_off;
+      if (e.step_sample && !e.step_sample_det) {     // the armed sample_waveform(pred) draw of the step (src/model.py:338)
+        lf.sample_out = e.step_sample; lf.inv_lv = 1.0f / (float)(1 << (p->c.bits - 1));
+        lf.seed = e.step_sample_seed; lf.offset = e.step_sample_off;
       }
     }
     rc = forward_core(p, params, inputs, true, cond, B, T, true, ws, L, s, nullptr, fuse ? &lf : nullptr);
     if (rc) return rc;
-    if (lf.done && lf.sample_out) wnp::ex(p).step_sample = nullptr;     // drawn
-    if (wnp::ex(p).phase_on) (void)hipEventRecord(wnp::ex(p).phase_ev[1], s);
+    if (lf.done && lf.sample_out) e.step_sample = nullptr;     // drawn
+    if (e.phase_on) (void)hipEventRecord(e.phase_ev[1], s);
     rc = loss_stage(p, B, T, global_batch, true, ws, L, loss_out, am_GF(nf - 1), s, lf.done);
     if (rc) return rc;
     if (pred_out) {
@@ -286,21 +269,21 @@ struct TrainCall {
       else rc = hipMemcpyAsync(pred_out, ws + L.logits, rows * p->Cout * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess ? WN_OK : WN_E_HIP;
       if (rc) return rc;
     }
-    if (wnp::ex(p).step_sample) {
+    if (e.step_sample) {
       // sample_waveform(pred) of this step (src/model.py:338) drawn from the logits while they are still hot:
       // no (rows, C) probability tensor is written or re-read
-      float* so = wnp::ex(p).step_sample;
-      wnp::ex(p).step_sample = nullptr;
+      float* so = e.step_sample;
+      e.step_sample = nullptr;
       if (p->c.head == WN_HEAD_CATEGORICAL) {
-        if (wnp::ex(p).step_sample_det) {
+        if (e.step_sample_det) {
           wn_set_error("step sample: deterministic categorical draws go through wn_sample_waveform");
           return WN_E_UNSUPPORTED;
         }
-        rc = wn_launch_sample_rand_cat_logits(ws + L.logits, rows, p->Cout, p->c.bits, wnp::ex(p).step_sample_seed, wnp::ex(p).step_sample_off, so, s);
+        rc = wn_launch_sample_rand_cat_logits(ws + L.logits, rows, p->Cout, p->c.bits, e.step_sample_seed, e.step_sample_off, so, s);
       } else {
         // mixture heads: the model output IS the logits tensor
-        if (wnp::ex(p).step_sample_det) rc = wn_launch_sample_det(ws + L.logits, rows, p->Cout, p->c.num_mixtures, p->c.bits, so, s);
-        else rc = wn_launch_sample_rand(ws + L.logits, rows, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, wnp::ex(p).step_sample_seed, wnp::ex(p).step_sample_off, so, s);
+        if (e.step_sample_det) rc = wn_launch_sample_det(ws + L.logits, rows, p->Cout, p->c.num_mixtures, p->c.bits, so, s);
+        else rc = wn_launch_sample_rand(ws + L.logits, rows, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, e.step_sample_seed, e.step_sample_off, so, s);
       }
       if (rc) return rc;
     }
@@ -317,10 +300,10 @@ struct TrainCall {
       if (rc) return rc;
     }
     // (with dropout the split kernels read H * mask / (1 - rate) while only H is published: compare against limit * (1 - rate))
-    rc = wn_launch_guard_flag(ws + L.fwd_absmax, WN_RANGE_LIMIT * (wnp::ex(p).drop_rate > 0.f ? 1.f - wnp::ex(p).drop_rate : 1.f),
+    rc = wn_launch_guard_flag(ws + L.fwd_absmax, WN_RANGE_LIMIT * (e.drop_rate > 0.f ? 1.f - e.drop_rate : 1.f),
                               wn_debug_get(1) != 1, loss_out + 2, s);
     if (rc) return rc;
-    if (wnp::ex(p).phase_on) (void)hipEventRecord(wnp::ex(p).phase_ev[2], s);
+    if (e.phase_on) (void)hipEventRecord(e.phase_ev[2], s);
     return WN_OK;
   }
 
@@ -338,7 +321,7 @@ struct TrainCall {
   int head_backward() {
     int rc;
     float* head_out = p->c.use_skip ? ws + L.g_skipsum : ws + L.GH[p->N];
-    for (int i = (int)p->finals.size() - 1; i >= (fold ? 1 : 0); --i) {
+    for (int i = (int)p->finals.size() - 1; i >= (tp.fold ? 1 : 0); --i) {
       const ConvInfo& c = p->finals[i];
       float* dst = (i == 0) ? head_out : ws + L.GF[i - 1];
       // 128 / 256 input channels: the streamed kernel's second form in its backward-data instantiation
@@ -371,18 +354,14 @@ struct TrainCall {
   int chain_backward() {
     int rc;
     // folded skip path: the gradient of the skip sum is never formed; the blocks contract dL/da = GF[0] with V(b)
-    const float* g_skip = (p->c.use_skip && !fold) ? ws + L.g_skipsum : nullptr;
+    const float* g_skip = (p->c.use_skip && !tp.fold) ? ws + L.g_skipsum : nullptr;
     if (p->c.use_skip) {
       rc = wn_launch_fill(ws + L.GH[p->N], 0.f, rows * p->R, s);   // nothing flows into the last block output
       if (rc) return rc;
     }
     // Two products per launch (wn_bwd_pair.hip): g_x(b+1) and, from it in registers, g_u(b).  The chain is then
     //   g_u(N-1) | { g_x(b+1), g_u(b) } for b = N-2 .. 0 | g_x(0)   = N + 1 launches instead of 2 N.
-    const bool pairk = fold && p->N >= 2 && wnp::ex(p).drop_rate == 0.f && p->c.use_residual && (p->c.cond_inputs == 0 || cond_batched) &&
-                       (wn_bwd_pair_supported(p->R, p->D, p->KS, p->fold_F0) || wn_bwd_s128_supported(p->R, p->D, p->KS, p->fold_F0)) &&
-                       p->Dp == p->D &&
-                       // (the streamed R = 128 pair kernel indexes with 32-bit byte offsets: the two-launch chain takes over beyond)
-                       (p->R != 128 || (int64_t)rows * 2 * p->D * 4 < ((int64_t)1 << 32));
+    const bool pairk = tp.bwd_pairs();
     for (int b = p->N - 1; b >= 0; --b) {
       BlockPtrs k = block_ptrs(p, b, params, fragbase, B, T);
       deep16_ptrs(p, b, fragbase, k);
@@ -398,7 +377,7 @@ struct TrainCall {
         a.am_gu_in = am_GU(b + 1); a.am_gf = am_GF(0); a.am_gx = am_GH(b + 1); a.am_gu = am_GU(b);
         a.B = B; a.T = T; a.dil = k1.dil[0];
         if (!a.wx16 || !a.wu16) { wn_set_error("bwd_pair: weight images missing"); return WN_E_UNSUPPORTED; }
-        rc = p->R == 128 ? wn_launch_bwd_s128(a, s) : wn_launch_bwd_pair(a, s);
+        rc = tp.bwd == BWD_S128 ? wn_launch_bwd_s128(a, s) : wn_launch_bwd_pair(a, s);
         if (rc) return rc;
         if (b == 0) {
           // g_x(0): the gradient at the first block's input (only the input conv's weight gradients need it)
@@ -414,7 +393,7 @@ struct TrainCall {
       }
       BlockBufs f;
       memset(&f, 0, sizeof(f));
-      f.x = (wnp::ex(p).drop_rate > 0.f) ? ws + L.XD[b] : ws + L.H[b];
+      f.x = tp.drop ? ws + L.XD[b] : ws + L.H[b];
       for (int i = 0; i + 1 < p->LPB; ++i) f.P[i] = ws + L.P[b][i];
       f.AG = ws + L.AG[b];
       f.Z = ws + L.Z + (int64_t)b * rows * p->Dp; f.ldz = p->Dp;
@@ -422,10 +401,10 @@ struct TrainCall {
       memset(&bg, 0, sizeof(bg));
       bg.defer = true;
       for (int i = 0; i + 1 < p->LPB; ++i) bg.g_pi[i] = ws + L.GP[b][i];
-      if (deep16(p))
+      if (tp.deep16)
         for (int i = 0; i + 1 < p->LPB; ++i) bg.am_gp[i] = am_GP(b, i);
-      if (wnp::ex(p).drop_rate > 0.f) {
-        bg.drop_rate = wnp::ex(p).drop_rate; bg.drop_key = wn_dropout_key(wnp::ex(p).drop_seed, b, wnp::ex(p).drop_step); bg.g_xd = ws + L.gxd;
+      if (tp.drop) {
+        bg.drop_rate = e.drop_rate; bg.drop_key = wn_dropout_key(e.drop_seed, b, e.drop_step); bg.g_xd = ws + L.gxd;
       }
       // the last block's output gradient is identically zero when the head reads the skip sum
       // (with the skip head nothing flows into the last block's output: GH[N] was zero-filled above.  It is
@@ -442,7 +421,7 @@ struct TrainCall {
       bg.am_gxout = bg.g_xout ? am_GH(b + 1) : nullptr;
       bg.am_gskip = g_skip ? am_gskip : nullptr;
       bg.am_gu = am_GU(b); bg.am_gx = am_GH(b);
-      if (fold) { bg.g_fold = ws + L.GF[0]; bg.fold_F0 = p->fold_F0; bg.am_gfold = am_GF(0); }
+      if (tp.fold) { bg.g_fold = ws + L.GF[0]; bg.fold_F0 = p->fold_F0; bg.am_gfold = am_GF(0); }
       rc = block_backward(k, f, bg, s);
       if (rc) return rc;
       if (p->S == 0 && bg.g_xout == nullptr && g_skip) {
@@ -459,22 +438,10 @@ struct TrainCall {
 
   // folded skip path: M = Z^T dL/da -> dW_s, db_s of every block and dW_f0, db_f0 (three small weight-space products)
   int fold_weight_gradients() {
-    int rc = WN_OK;
-    // M = Z^T dL/da (N*D x F0) and colsum(dL/da) into their own slab, reduced, then the three small products
+    // M = Z^T dL/da and colsum(dL/da) are in their slab (the schedule's last span): reduced, then the three small products
     const int F0 = p->fold_F0;
-    const int64_t pm = (int64_t)p->N * p->D * F0 + F0;
-    if (wnp::ex(p).jobs_mtr != 0)
-      rc = wn_launch_wgrad_tr(wnp::ex(p).jobs_mtr, wnp::ex(p).d_pairs + wnp::ex(p).pair_first[0], wnp::ex(p).pair_count[0], ws, ws + L.mslab, pm, B, T,
-                              L.bsplits, s);
-    else if (!wnp::ex(p).jobs_mfused)
-    rc = wn_launch_wgrad_skip(ws + L.Z, p->Dp, ws + L.GF[0], F0, rows, p->N * p->D, F0, p->D, B * L.bsplits, ws + L.mslab, pm,
-                              0, (int64_t)p->D * F0, (int64_t)p->N * p->D * F0, 0, 1, am_GF(0), s);
+    int rc = wn_launch_reduce_table(ws + L.mslab, B * L.bsplits, pm, ws + L.mtot, p->d_cov_fold, 1, s, &p->h_cov_fold);
     if (rc) return rc;
-    rc = wn_launch_reduce_table(ws + L.mslab, B * L.bsplits, pm, ws + L.mtot, p->d_cov_fold, 1, s, &p->h_cov_fold);
-    if (rc) return rc;
-    const BlockInfo& b0 = p->blocks[0];
-    const int64_t wst = p->N > 1 ? p->tensors[p->blocks[1].conv_skip.kernel_t].off - p->tensors[b0.conv_skip.kernel_t].off : 0;
-    const int64_t bst = p->N > 1 ? p->tensors[p->blocks[1].conv_skip.bias_t].off - p->tensors[b0.conv_skip.bias_t].off : 0;
     // Y = [M; colsum] W_f0^T -> dW_s of every block and db_s;  dW_f0 = [W_s(all); sum b_s]^T [M; colsum];  db_f0 = colsum
     const ConvInfo& c0 = p->finals[0];
     const int nd1 = p->N * p->D + 1;
@@ -497,26 +464,22 @@ struct TrainCall {
     rc = wgrad(ws + L.wsall, p->S, p->S, 0, ws + L.mtot, F0, F0, 1, nd1, grads + p->tensors[c0.kernel_t].off, nullptr, nullptr,
                slab, s);
     if (rc) return rc;
-    rc = wn_launch_skip_scatter(ws + L.ytmp, ws + L.mtot + (int64_t)p->N * p->D * F0, p->tensors[b0.conv_skip.kernel_t].off, wst,
-                                p->tensors[b0.conv_skip.bias_t].off, bst, p->tensors[c0.bias_t].off, p->N, p->D, p->S, F0, grads, s);
-    if (rc) return rc;
-    return WN_OK;
+    return wn_launch_skip_scatter(ws + L.ytmp, ws + L.mtot + (int64_t)p->N * p->D * F0, skip_w.off, skip_w.stride, skip_b.off,
+                                  skip_b.stride, p->tensors[c0.bias_t].off, p->N, p->D, p->S, F0, grads, s);
   }
 
   // global conditioning of all blocks as one layer: per-utterance sums of d u out of the weight-gradient slab, g_m, dW_c, db_c
   int cond_weight_gradients() {
     int rc;
     const int D2 = 2 * p->D;
-    const BlockInfo& b0 = p->blocks[0];
-    const int64_t dst = p->N > 1 ? p->tensors[p->blocks[1].dil.back().bias_t].off - p->tensors[b0.dil.back().bias_t].off : 0;
-    const int64_t wst = p->N > 1 ? p->tensors[p->blocks[1].conv_cond.kernel_t].off - p->tensors[b0.conv_cond.kernel_t].off : 0;
-    const int64_t bst = p->N > 1 ? p->tensors[p->blocks[1].conv_cond.bias_t].off - p->tensors[b0.conv_cond.bias_t].off : 0;
-    rc = wn_launch_cond_gather(ws + L.bslab, p->nparams, L.bsplits, p->tensors[b0.dil.back().bias_t].off, dst, B, p->N, D2,
-                               ws + L.cbt, s);
+    const BlockInfo& b0 = p->blocks[0]; const BlockInfo& b1 = p->blocks[p->N > 1 ? 1 : 0];
+    const Strided db = strided(b0.dil.back().bias_t, b1.dil.back().bias_t);
+    const Strided cw = strided(b0.conv_cond.kernel_t, b1.conv_cond.kernel_t), cbi = strided(b0.conv_cond.bias_t, b1.conv_cond.bias_t);
+    rc = wn_launch_cond_gather(ws + L.bslab, p->nparams, L.bsplits, db.off, db.stride, B, p->N, D2, ws + L.cbt, s);
     if (rc) return rc;
     if (cond_small(p) && (int64_t)p->N * B * p->Cc <= L.slab_floats) {
       // g_m = sum_z dcb_z W_c(z)^T: one product per block into the (idle) slab, then their sum
-      rc = wn_launch_sgemm_small_batched(ws + L.cbt, p->N * D2, 1, D2, params + p->tensors[b0.conv_cond.kernel_t].off, 1, D2, wst,
+      rc = wn_launch_sgemm_small_batched(ws + L.cbt, p->N * D2, 1, D2, params + cw.off, 1, D2, cw.stride,
                                          slab, p->Cc, (int64_t)B * p->Cc, B, p->Cc, D2, p->N, nullptr, 0, s);
       if (rc) return rc;
       WnVecSumArgs v;
@@ -525,118 +488,83 @@ struct TrainCall {
     } else
     rc = Gemm(1, B, p->Cc, ceil32(p->Cc)).seg(ws + L.cbt, p->N * D2, p->N * D2, 0, fragbase + p->frag_condB).run(ws + L.g_m0, p->Cc, s);
     if (rc) return rc;
-    rc = wn_launch_cond_wgrad(mlast, ws + L.cbt, B, p->Cc, p->N, D2, grads, p->tensors[b0.conv_cond.kernel_t].off, wst,
-                              p->tensors[b0.conv_cond.bias_t].off, bst, s);
-    if (rc) return rc;
-    return WN_OK;
+    return wn_launch_cond_wgrad(mlast, ws + L.cbt, B, p->Cc, p->N, D2, grads, cw.off, cw.stride, cbi.off, cbi.stride, s);
   }
 
-  // ---- every weight gradient of the step: per-block kernels on the caller's stream, the low-occupancy leftovers (input
-  //      conv, head) beside them on a side stream, then the slab reductions into the flat gradient ----
+  // one launch of the schedule
+  int launch(const WgSpan& sp, hipStream_t st) {
+    const WgSchedule& g = e.wg;
+    float* out = ws + L.bslab; int64_t pitch = p->nparams; int splits = L.bsplits;
+    if (sp.slab == WgSpan::HEAD) { out = ws + L.hslab - L.head_base; pitch = L.head_span; splits = L.hsplits; }
+    if (sp.slab == WgSpan::MFOLD) { out = ws + L.mslab; pitch = pm; }
+    switch (sp.op) {
+      case WgSpan::INCONV:
+        return wn_launch_inconv_wgrad(inputs, ws + L.GH[0], B, T, p->R, p->KS, L.isplits, ws + L.islab, (int64_t)(p->KS + 1) * p->R,
+                                      0, (int64_t)p->KS * p->R, st);
+      case WgSpan::JOBS: return wn_launch_wgrad_batched(g.jobs.d + sp.first, sp.count, ws, out, pitch, B, T, splits, st, sp.kind != 0);
+      case WgSpan::PAIRS: return wn_launch_wgrad_pairs(sp.kind, g.pairs.d + sp.first, sp.count, ws, out, pitch, B, T, splits, st);
+      case WgSpan::TR:        // (kind 6: M into its own slab beside dW_r)
+        return wn_launch_wgrad_tr(sp.kind, g.pairs.d + sp.first, sp.count, ws, out, pitch, B, T, splits, st,
+                                  sp.kind == 6 ? ws + L.mslab : nullptr, sp.kind == 6 ? pm : 0);
+      case WgSpan::LAYERS: return wn_launch_wgrad_layers(sp.kind ? g.inner.d : g.layers.d, sp.count, p->R, ws, out, pitch, B, T, splits, st, sp.kind);
+      case WgSpan::SKIP:
+        if (sp.slab == WgSpan::MFOLD)
+          return wn_launch_wgrad_skip(ws + L.Z, p->Dp, ws + L.GF[0], p->fold_F0, rows, p->N * p->D, p->fold_F0, p->D, B * splits, out, pitch,
+                                      0, (int64_t)p->D * p->fold_F0, (int64_t)p->N * p->D * p->fold_F0, 0, 1, am_GF(0), st);
+        return wn_launch_wgrad_skip(ws + L.Z, p->Dp, ws + L.g_skipsum, p->S, rows, p->N * p->D, p->S, p->D, B * splits, out, pitch,
+                                    skip_w.off, skip_w.stride, skip_b.off, skip_b.stride, p->N, am_gskip, st);
+    }
+    return WN_E_INVALID;
+  }
+
+  // ---- every weight gradient of the step: the schedule's low-occupancy leftovers (input conv, head) on a side stream
+  //      beside the per-block kernels on the caller's, then the slab reductions into the flat gradient ----
   int weight_gradients() {
     int rc;
-    if (wnp::ex(p).phase_on) (void)hipEventRecord(wnp::ex(p).phase_ev[3], s);      // backward-data chain done
-    // the generic jobs left over (input conv, head) are few single-wave jobs: they run beside the
-    // per-block and skip kernels on a side stream (disjoint slab regions), joined before the reduce.
+    const WgSchedule& g = e.wg;
+    if (e.phase_on) (void)hipEventRecord(e.phase_ev[3], s);      // backward-data chain done
+    // the side spans run on disjoint slab regions and are joined before the reduce.
     // knob 9 = 1 keeps everything on the caller's stream (A/B of the overlap).
-    const bool fork = (wnp::ex(p).jobs_layerk || wnp::ex(p).jobs_pairk) && wn_debug_get(9) != 1;
-    if (fork && !wnp::ex(p).side) {
-      WN_HIP_CHECK(hipStreamCreateWithFlags(&wnp::ex(p).side, hipStreamNonBlocking));
-      WN_HIP_CHECK(hipEventCreateWithFlags(&wnp::ex(p).ev_fork, hipEventDisableTiming));
-      WN_HIP_CHECK(hipEventCreateWithFlags(&wnp::ex(p).ev_join, hipEventDisableTiming));
+    const bool fork = g.overlap && wn_debug_get(9) != 1;
+    if (fork && !e.side) {
+      WN_HIP_CHECK(hipStreamCreateWithFlags(&e.side, hipStreamNonBlocking));
+      WN_HIP_CHECK(hipEventCreateWithFlags(&e.ev_fork, hipEventDisableTiming));
+      WN_HIP_CHECK(hipEventCreateWithFlags(&e.ev_join, hipEventDisableTiming));
     }
     // Whatever happens after the fork, the caller's stream must not run ahead of the side stream's kernels (they
     // read and write the workspace and the gradient slab): an early error return joins through this guard.
     struct SideJoin {
-      wn_plan* p; hipStream_t s; bool armed;
+      wn_exec& e; hipStream_t s; bool armed;
       ~SideJoin() {
         if (!armed) return;
-        if (hipEventRecord(wnp::ex(p).ev_join, wnp::ex(p).side) != hipSuccess || hipStreamWaitEvent(s, wnp::ex(p).ev_join, 0) != hipSuccess)
-          (void)hipStreamSynchronize(wnp::ex(p).side);
+        if (hipEventRecord(e.ev_join, e.side) != hipSuccess || hipStreamWaitEvent(s, e.ev_join, 0) != hipSuccess)
+          (void)hipStreamSynchronize(e.side);
       }
-    } side_join{p, s, false};
+    } side_join{e, s, false};
     if (fork) {
-      WN_HIP_CHECK(hipEventRecord(wnp::ex(p).ev_fork, s));
-      WN_HIP_CHECK(hipStreamWaitEvent(wnp::ex(p).side, wnp::ex(p).ev_fork, 0));
+      WN_HIP_CHECK(hipEventRecord(e.ev_fork, s));
+      WN_HIP_CHECK(hipStreamWaitEvent(e.side, e.ev_fork, 0));
       side_join.armed = true;
     }
-    if (wnp::ex(p).jobs_inconvk) {
-      rc = wn_launch_inconv_wgrad(inputs, ws + L.GH[0], B, T, p->R, p->KS, L.isplits, ws + L.islab, (int64_t)(p->KS + 1) * p->R,
-                                  0, (int64_t)p->KS * p->R, fork ? wnp::ex(p).side : s);
-      if (rc) return rc;
-    }
-    const bool head_own = L.hsplits > 0 && (wnp::ex(p).head_first < wnp::ex(p).njobs || wnp::ex(p).jobs_headpairs);
-    rc = wn_launch_wgrad_batched(wnp::ex(p).d_jobs, head_own ? wnp::ex(p).head_first : wnp::ex(p).njobs, ws, ws + L.bslab, p->nparams, B, T, L.bsplits,
-                                 fork ? wnp::ex(p).side : s, p->LPB > 1 && !wnp::ex(p).jobs_deep16);
+    size_t i = 0;
+    for (; i < (size_t)g.n_side; ++i)
+      if ((rc = launch(g.spans[i], fork ? e.side : s))) return rc;
+    if (fork) WN_HIP_CHECK(hipEventRecord(e.ev_join, e.side));
+    for (; i < g.spans.size(); ++i)
+      if ((rc = launch(g.spans[i], s))) return rc;
+    if (tp.fold && (rc = fold_weight_gradients())) return rc;
+    if (fork) { WN_HIP_CHECK(hipStreamWaitEvent(s, e.ev_join, 0)); side_join.armed = false; }
+    if (cond_batched && (rc = cond_weight_gradients())) return rc;
+    // coverage entries 0, 1 are the input conv's kernel and bias: from their compact slab when the dedicated kernel ran;
+    // the head's entries come last: from the head's slab when it has one
+    const int cov0 = tp.in_split ? 2 : 0, ncov = (int)g.h_cov.size(), cov1 = g.cov_head;
+    rc = wn_launch_reduce_table(ws + L.bslab, B * L.bsplits, p->nparams, grads, g.cov.d + cov0, cov1 - cov0, s, g.h_cov.data() + cov0);
     if (rc) return rc;
-    if (head_own) {
-      // job and coverage offsets are offsets into the flat parameter buffer: the compact slab is addressed
-      // through a base shifted by -head_base with the head span as its row pitch
-      if (wnp::ex(p).head_first < wnp::ex(p).njobs) {
-        rc = wn_launch_wgrad_batched(wnp::ex(p).d_jobs + wnp::ex(p).head_first, wnp::ex(p).njobs - wnp::ex(p).head_first, ws, ws + L.hslab - L.head_base,
-                                     L.head_span, B, T, L.hsplits, fork ? wnp::ex(p).side : s);
-        if (rc) return rc;
-      }
-      if (wnp::ex(p).jobs_headpairs)
-        for (int kd = 1; kd <= 5; ++kd)
-          if (wnp::ex(p).hpair_count[kd] > 0) {
-            // staged kinds 1 (128 x 256), 3 (256 x 128), 5 (256 x 256 halves) have transposed-read forms (3, 4, 5)
-            const int trk = kd == 1 ? 3 : (kd == 3 ? 4 : (kd == 5 ? 5 : (kd == 2 ? 2 : 0)));
-            if (trk != 0 && wnp::ex(p).jobs_pairk)                 // (with 64-channel blocks the staged head jobs are faster beside the side stream's neighbours)
-              rc = wn_launch_wgrad_tr(trk, wnp::ex(p).d_pairs + wnp::ex(p).hpair_first[kd], wnp::ex(p).hpair_count[kd], ws, ws + L.hslab - L.head_base,
-                                      L.head_span, B, T, L.hsplits, fork ? wnp::ex(p).side : s);
-            else
-            rc = wn_launch_wgrad_pairs(kd, wnp::ex(p).d_pairs + wnp::ex(p).hpair_first[kd], wnp::ex(p).hpair_count[kd], ws, ws + L.hslab - L.head_base,
-                                       L.head_span, B, T, L.hsplits, fork ? wnp::ex(p).side : s);
-            if (rc) return rc;
-          }
-    }
-    if (fork) WN_HIP_CHECK(hipEventRecord(wnp::ex(p).ev_join, wnp::ex(p).side));
-    for (int kd = 1; kd <= 2; ++kd)
-      if (wnp::ex(p).jobs_pairk && wnp::ex(p).pair_count[kd] > 0) {
-        // transposed-read kernels: both taps of dW_d in one job; dW_r (+ M)
-        rc = wn_launch_wgrad_tr(kd == 2 && wnp::ex(p).jobs_mfused ? 6 : kd, wnp::ex(p).d_pairs + wnp::ex(p).pair_first[kd], wnp::ex(p).pair_count[kd], ws,
-                                ws + L.bslab, p->nparams, B, T, L.bsplits, s, ws + L.mslab,
-                                (int64_t)p->N * p->D * p->fold_F0 + p->fold_F0);
-        if (rc) return rc;
-      }
-    if (wnp::ex(p).jobs_layerk) {
-      rc = wn_launch_wgrad_layers(wnp::ex(p).d_wgl, p->N, p->R, ws, ws + L.bslab, p->nparams, B, T, L.bsplits, s);
-      if (rc) return rc;
-      rc = wn_launch_wgrad_layers(wnp::ex(p).d_wgli, wnp::ex(p).n_wgli, p->R, ws, ws + L.bslab, p->nparams, B, T, L.bsplits, s, 1);
-      if (rc) return rc;
-    }
-    if (fold) {
-      rc = fold_weight_gradients();
-      if (rc) return rc;
-    } else if (wnp::ex(p).jobs_skipk) {
-      const BlockInfo& b0 = p->blocks[0];
-      const int64_t wst = p->N > 1 ? p->tensors[p->blocks[1].conv_skip.kernel_t].off - p->tensors[b0.conv_skip.kernel_t].off : 0;
-      const int64_t bst = p->N > 1 ? p->tensors[p->blocks[1].conv_skip.bias_t].off - p->tensors[b0.conv_skip.bias_t].off : 0;
-      rc = wn_launch_wgrad_skip(ws + L.Z, p->Dp, ws + L.g_skipsum, p->S, rows, p->N * p->D, p->S, p->D,
-                                B * L.bsplits, ws + L.bslab, p->nparams, p->tensors[b0.conv_skip.kernel_t].off, wst,
-                                p->tensors[b0.conv_skip.bias_t].off, bst, p->N, am_gskip, s);
-      if (rc) return rc;
-    }
-    if (fork) { WN_HIP_CHECK(hipStreamWaitEvent(s, wnp::ex(p).ev_join, 0)); side_join.armed = false; }
-    if (cond_batched) {
-      rc = cond_weight_gradients();
-      if (rc) return rc;
-    }
-    // coverage entries 0, 1 are the input conv's kernel and bias: from their compact slab when the dedicated kernel ran
-    const int cov0 = wnp::ex(p).jobs_inconvk ? 2 : 0;
-    rc = wn_launch_reduce_table(ws + L.bslab, B * L.bsplits, p->nparams, grads, wnp::ex(p).d_cov + cov0,
-                                (head_own ? wnp::ex(p).cov_head_first : wnp::ex(p).ncov) - cov0, s, wnp::ex(p).h_cov.data() + cov0);
-    if (rc) return rc;
-    if (wnp::ex(p).jobs_inconvk) {
-      rc = wn_launch_reduce_table(ws + L.islab, B * L.isplits, (int64_t)(p->KS + 1) * p->R, grads, wnp::ex(p).d_cov, 2, s, wnp::ex(p).h_cov.data());
-      if (rc) return rc;
-    }
-    if (head_own) {
-      rc = wn_launch_reduce_table(ws + L.hslab - L.head_base, B * L.hsplits, L.head_span, grads, wnp::ex(p).d_cov + wnp::ex(p).cov_head_first,
-                                  wnp::ex(p).ncov - wnp::ex(p).cov_head_first, s, wnp::ex(p).h_cov.data() + wnp::ex(p).cov_head_first);
-      if (rc) return rc;
-    }
+    if (tp.in_split && (rc = wn_launch_reduce_table(ws + L.islab, B * L.isplits, (int64_t)(p->KS + 1) * p->R, grads, g.cov.d, 2, s, g.h_cov.data())))
+      return rc;
+    if (cov1 < ncov && (rc = wn_launch_reduce_table(ws + L.hslab - L.head_base, B * L.hsplits, L.head_span, grads, g.cov.d + cov1, ncov - cov1,
+                                                    s, g.h_cov.data() + cov1)))
+      return rc;
     if (!p->c.use_skip && p->S > 0) {
       for (const BlockInfo& bi : p->blocks) {     // unused skip convs: zero gradients
         rc = wn_launch_fill(grads + p->tensors[bi.conv_skip.kernel_t].off, 0.f, p->tensors[bi.conv_skip.kernel_t].len, s);
@@ -701,8 +629,13 @@ struct TrainCall {
     // conditioning of all blocks as one layer: the per-utterance sums of d u come out of the weight-gradient
     // slab afterwards instead of 2 column-sum launches + 3 tiny products per block
     cond_batched = p->frag_condB >= 0;
-    fold = fold_ok(p);                             // (the forward pass of this call made the same decision)
-    rc = ensure_jobs(p, L, B, T);
+    tp = train_paths(p, e, L, rows);               // (fold: the forward pass of this call made the same decision)
+    pm = (int64_t)p->N * p->D * p->fold_F0 + p->fold_F0;
+    if (p->blocks[0].has_skip) {
+      const BlockInfo& b0 = p->blocks[0]; const BlockInfo& b1 = p->blocks[p->N > 1 ? 1 : 0];
+      skip_w = strided(b0.conv_skip.kernel_t, b1.conv_skip.kernel_t); skip_b = strided(b0.conv_skip.bias_t, b1.conv_skip.bias_t);
+    }
+    rc = ensure_schedule(p, e, L, B, T, tp);
     if (rc) return rc;
     if ((rc = head_backward())) return rc;
     if ((rc = chain_backward())) return rc;
@@ -713,8 +646,8 @@ struct TrainCall {
       rc = wn_launch_axpy_table(grads, params, p->d_kdesc, (int)p->kdesc.size(), 2.0f * p->c.l2_reg_factor / (float)n_replicas, s);
       if (rc) return rc;
     }
-    if (wnp::ex(p).phase_on) {
-      (void)hipEventRecord(wnp::ex(p).phase_ev[4], s);
+    if (e.phase_on) {
+      (void)hipEventRecord(e.phase_ev[4], s);
     }
 
     return WN_OK;
@@ -734,7 +667,7 @@ extern "C" int wn_train_fwd_bwd(wn_plan* p, const float* params, const float* x_
                                 float* loss_out, float* pred_out, float* workspace, int64_t ws_floats,
                                 void* stream) {
   if (!p || !params || !x_full || !workspace || !loss_out || !grads || B < 1 || T < 1) { wn_set_error("train_fwd_bwd: bad arguments"); return WN_E_INVALID; }
-  TrainCall c;
+  TrainCall c{wnp::ex(p)};
   c.p = p; c.params = params; c.x_full = x_full; c.cond = cond; c.B = B; c.T = T;
   c.global_batch = global_batch > 0 ? global_batch : B;
   c.n_replicas = n_replicas > 0 ? n_replicas : 1;
@@ -745,11 +678,12 @@ extern "C" int wn_train_fwd_bwd(wn_plan* p, const float* params, const float* x_
   c.inputs = workspace + c.L.probs;
   c.am = workspace + c.L.absmax;
   c.nf = (int)p->finals.size();
-  c.am_gskip = c.am + c.nf;
+  c.slot = AbsmaxSlots{c.nf, p->N, p->LPB};
+  c.am_gskip = c.am + c.slot.gskip();
   // A caller may run the step as two calls (wn_plan_set_train_phases 1, then 2) and queue work of its own in between --
   // the Python mirror reads the loss and the metrics back from there, 4 ms before the step ends.  Everything the second
   // half needs lives in the workspace.
-  const int phases = wnp::ex(p).train_phases;
+  const int phases = c.e.train_phases;
   int rc = WN_OK;
   if (phases & 1) rc = c.forward_and_loss();
   if (!rc && (phases & 2)) rc = c.backward();

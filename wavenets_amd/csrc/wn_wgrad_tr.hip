@@ -46,7 +46,7 @@ __device__ __forceinline__ h8 wt_frag(const unsigned char* lanebase, int off) {
 // G2: G is two tensors of NC / 2 channels each (J.g_off | J.g2_off, row stride LDG both); the lower half's product goes to
 // (slab, w_off, b_off) as usual, the upper half's to (slab2, w2_off, b2_off), both with row pitch LDW.
 // XSEG > 0 (TAPS = 1, not G2): the KC channels of X are KC / XSEG tensors of XSEG channels each (row stride LDX = XSEG),
-// J.g2_off floats apart, of which the first J.pad_ exist (the rest reads as zero and its output rows are not written):
+// J.seg_stride floats apart, of which the first J.nseg exist (the rest reads as zero and its output rows are not written):
 // the gated activations z of several blocks (block-major Z) against ONE read of G -- the folded skip path's
 // M = Z^T dL/da (src/layers.py:216-217 and model.py:105-111 reversed) for 64- and 32-channel blocks.
 template <int KC, int NC, int TAPS, int LDX, int LDG, int LDW, int TKW, int TNW, bool G2 = false, int XSEG = 0>
@@ -81,9 +81,9 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
   // ---- this thread's pieces of a chunk: rows xr + XRP k of every x tap (4 channels at xc), rows gr + GRP k of g (4 at gc) ----
   const int xr = tid / XPR, xc = (tid % XPR) * 4;
   const int gr = tid / GPR, gc = (tid % GPR) * 4;
-  const int nseg = XSEG > 0 ? J.pad_ : 0;
+  const int nseg = XSEG > 0 ? J.nseg : 0;
   const bool xvalid = XSEG == 0 || xc / (XSEG > 0 ? XSEG : 1) < nseg;
-  const float* xbase = XSEG > 0 ? ws + J.x_off + (int64_t)(xvalid ? xc / (XSEG > 0 ? XSEG : 1) : 0) * J.g2_off + (int64_t)ub * T * LDX + xc % (XSEG > 0 ? XSEG : 1)
+  const float* xbase = XSEG > 0 ? ws + J.x_off + (int64_t)(xvalid ? xc / (XSEG > 0 ? XSEG : 1) : 0) * J.seg_stride + (int64_t)ub * T * LDX + xc % (XSEG > 0 ? XSEG : 1)
                                 : ws + J.x_off + (int64_t)ub * T * LDX + xc;
   const bool upper = G2 && gc >= NC / 2;                 // this thread's g piece belongs to the second tensor
   const float* gbase = upper ? ws + J.g2_off + (int64_t)ub * T * LDG + (gc - NC / 2) : ws + J.g_off + (int64_t)ub * T * LDG + gc;
