@@ -486,6 +486,30 @@ def loss_logistic(target: torch.Tensor, pred: torch.Tensor, num_mixtures: int,
   return -1.0 * torch.log(lik)
 
 
+def loss_logistic_exact(target: torch.Tensor, pred: torch.Tensor, num_mixtures: int,
+                        bits: int) -> torch.Tensor:
+  """The same discretised mixture of logistics with the bin mass taken on the negative side.
+
+  sigmoid(a) - sigmoid(b) loses the mass once both arguments are large and positive (a target above a sharp
+  component's mean: both sigmoids round to 1, the loss is inf where the mirrored target below the mean gives the exact
+  value).  sigmoid(x) = 1 - sigmoid(-x), so the mass is also sigmoid(-b) - sigmoid(-a); that form is taken when
+  a + b > 0 and both arguments are then <= the half-bin.  Same clamp at -7 (torch.clamp: the gradient passes at
+  ls == -7, as in loss_logistic) and same softmax.  This is the reference of the HIP loss kernel in both tails
+  (DESIGN.md section 17); loss_logistic stays as the source writes it."""
+  M = num_mixtures
+  w, mu, ls = pred[..., :M], pred[..., M:2 * M], pred[..., 2 * M:]
+  y = target.expand(*target.shape[:-1], M)
+  w = torch.softmax(w, dim=-1)
+  halfbit = 0.5 * 1 / (2 ** bits)
+  ls = torch.clamp(ls, min=-7.0)
+  inv = torch.exp(-1.0 * ls)
+  a, b = (y - mu + halfbit) * inv, (y - mu - halfbit) * inv
+  upper = (a + b) > 0
+  hi, lo = torch.where(upper, -b, a), torch.where(upper, -a, b)
+  lik = torch.sum(w * (torch.sigmoid(hi) - torch.sigmoid(lo)), dim=-1)
+  return -1.0 * torch.log(lik)
+
+
 def loss_gaussian(target: torch.Tensor, pred: torch.Tensor, num_mixtures: int) -> torch.Tensor:
   """Mixture of gaussians as written in src/model.py:517-532."""
   M = num_mixtures

@@ -125,8 +125,20 @@ int wn_launch_cat_loss_probs(const float* probs, const int32_t* target, int64_t 
 // mixture losses, one thread per (b,t) row; M <= 32.  Evaluated in double: with bits = 16 the
 // half-bin (src/model.py:538) is 7.6e-6, so sigmoid(a) - sigmoid(b) cancels ~5 digits and an
 // fp32 evaluation (the reference's own included) carries 1e-3..1e-2 relative noise per term.
+// The logistic bin mass sigmoid(a) - sigmoid(b) is taken on the negative side: above a sharp component's mean both
+// sigmoids round to 1 (from (y - mu) e^-ls ~ 37 on; digits go from ~20 on) and the mass is lost -- inf loss, NaN gradients
+// -- where the mirrored row below the mean is exact.  sigmoid(x) = 1 - sigmoid(-x): when a + b > 0 the mass is
+// sigmoid(-b) - sigmoid(-a), and sigmoid'(x) = sigmoid(x) sigmoid(-x) is even.  
 #define WN_MAXMIX 32
 __device__ __forceinline__ double wn_sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
+__device__ __forceinline__ double wn_dsigmoid_d(double x) { return wn_sigmoid_d(x) * wn_sigmoid_d(-x); }
+// the bin's edges (hi >= lo, hi + lo <= 0) on the side where the mass is sigmoid(hi) - sigmoid(lo); true: mirrored
+__device__ __forceinline__ bool wn_logistic_bin(double a, double b, double& hi, double& lo) {
+  const bool up = a + b > 0.0;
+  hi = up ? -b : a;
+  lo = up ? -a : b;
+  return up;
+}
 __global__ void wn_mix_loss_kernel(const float* pred, const float* y, int64_t rows, int M, int bits,
                                    int kind, float gscale, float* loss_rows, float* g_pred, float* absmax_out) {
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -148,7 +160,9 @@ __global__ void wn_mix_loss_kernel(const float* pred, const float* y, int64_t ro
     const double ls = fmax((double)p[2 * M + k], -7.0);
     if (kind == 1) {
       const double inv = exp(-ls);
-      comp[k] = wn_sigmoid_d((yy - mu + halfbit) * inv) - wn_sigmoid_d((yy - mu - halfbit) * inv);
+      double hi, lo;
+      wn_logistic_bin((yy - mu + halfbit) * inv, (yy - mu - halfbit) * inv, hi, lo);
+      comp[k] = wn_sigmoid_d(hi) - wn_sigmoid_d(lo);
     } else {
       const double sc = exp(ls);
       const double xx = fmin((yy - mu) / sc, 1e8);
@@ -168,11 +182,12 @@ __global__ void wn_mix_loss_kernel(const float* pred, const float* y, int64_t ro
     g[k] = (float)(dl * (w[k] * comp[k] - w[k] * lik));
     if (kind == 1) {
       const double inv = exp(-ls);
-      const double a = (yy - mu + halfbit) * inv, b = (yy - mu - halfbit) * inv;
-      const double sa = wn_sigmoid_d(a), sb = wn_sigmoid_d(b);
-      const double da = sa * (1.0 - sa), db = sb * (1.0 - sb);
-      g[M + k] = (float)(dl * (-w[k] * inv * (da - db)));
-      g[2 * M + k] = (float)(dl * lsmask * (-w[k] * (a * da - b * db)));
+      double hi, lo;
+      const bool up = wn_logistic_bin((yy - mu + halfbit) * inv, (yy - mu - halfbit) * inv, hi, lo);
+      const double dhi = wn_dsigmoid_d(hi), dlo = wn_dsigmoid_d(lo);
+      // mirrored: a = -lo, b = -hi, so sigmoid'(a) - sigmoid'(b) changes sign and a sigmoid'(a) - b sigmoid'(b) does not
+      g[M + k] = (float)(dl * (-w[k] * inv * (up ? dlo - dhi : dhi - dlo)));
+      g[2 * M + k] = (float)(dl * lsmask * (-w[k] * (hi * dhi - lo * dlo)));
     } else {
       const double sc = exp(ls);
       const double xr = (yy - mu) / sc;

@@ -883,6 +883,7 @@ extern "C" int wn_debug_ws_region(const wn_plan* p, int32_t B, int32_t T, int32_
           (size_t)(idx % inner) < L.P[idx / inner].size()) { *off = L.P[idx / inner][idx % inner]; *len = rows * p->D; }
       break;
     }
+    case 12: *off = L.loss_rows; *len = rows; break;
     default: break;
   }
   if (*off < 0) { wn_set_error("ws_region: no such region (%d, %d)", what, idx); return WN_E_INVALID; }
