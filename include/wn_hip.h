@@ -240,10 +240,21 @@ int wn_generate(wn_plan* p, const float* params, const float* window, const floa
  *   deterministic arg max ("first maximum wins").  The kept set does not depend on T.  Offered for up to 1024 classes
  *   (WN_E_UNSUPPORTED beyond).
  * seed: the Philox key of the draws.
- * A deterministic draw ignores temperature and top_k (arg max and mode do not depend on them); they are still checked.
- * {1.0f, 0, seed} is the draw of the entry points without controls, bit for bit.  The three fields are checked before
+ * top_p (nucleus; the last member, so {T, k, seed} initialisers leave it 0): 0 and 1 = off (the unmodified path, bit for
+ *   bit); a value in (0, 1) = on; anything else, NaN included, is WN_E_INVALID.  Categorical head only (on with a mixture
+ *   head is WN_E_INVALID), offered for up to 1024 classes (WN_E_UNSUPPORTED beyond).  Order: temperature -> top_k ->
+ *   top_p.  With K the set top_k kept (all classes when it is off), q_j = (p_j / p_max)^(1/T) for j in K and 0 elsewhere,
+ *   Q = sum q_j, and the classes ranked as for top_k (probability descending, class index ascending), the nucleus is
+ *   the shortest prefix of that ranking whose sum of q is >= top_p * Q: a prefix whose sum equals top_p * Q suffices,
+ *   it holds at least one class, and of the classes tied at the cut as many as needed are kept, lower class index
+ *   first.  The draw is the same inverse-CDF draw from q restricted to the nucleus; the Philox words keep their use.
+ *   All of this is fp32 arithmetic on q (sums, comparisons, one division).  The largest q is exactly 1 and Q <= 1024,
+ *   so top_p <= 2^-11 keeps exactly the first-ranked class: the arg max of the deterministic draw.
+ * A deterministic draw ignores temperature, top_k and top_p (arg max and mode do not depend on them); they are still
+ * checked.
+ * {1.0f, 0, seed} is the draw of the entry points without controls, bit for bit.  The fields are checked before
  * any other argument is looked at and before anything touches the device. */
-typedef struct wn_sampling { float temperature; int32_t top_k; uint64_t seed; } wn_sampling;
+typedef struct wn_sampling { float temperature; int32_t top_k; uint64_t seed; float top_p; } wn_sampling;
 /* wn_generate with the sampling controls in place of the seed; wn_generate is its {1.0f, 0, seed} case */
 int wn_generate_sampled(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                         int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling, float* out,

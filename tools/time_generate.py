@@ -1,10 +1,10 @@
 """Generation speed (the reference prints 'Speed of generation was ... samples/s', train.py:253-261):
 naive sliding window vs queued ring buffers on BASELINE configs[1] weights, batch B.
---temperature T / --top-k K anywhere on the command line: the sampling controls of the stochastic leg."""
+--temperature T / --top-k K / --top-p P anywhere on the command line: the sampling controls of the stochastic leg."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 controls = {}
-for flag, key, conv in (('--temperature', 'temperature', float), ('--top-k', 'top_k', int)):
+for flag, key, conv in (('--temperature', 'temperature', float), ('--top-k', 'top_k', int), ('--top-p', 'top_p', float)):
   if flag in sys.argv:
     i = sys.argv.index(flag)
     controls[key] = conv(sys.argv[i + 1])

@@ -33,6 +33,7 @@ config = {                       # defaults of the reference, train.py:22-50
     'steps_per_epoch': 0, 'synthetic_utterances': 256, 'sample_rate': 16000, 'results_dir': './results',
     'preview_length': 0, 'condition_classes': 2, 'labels': None,
     'preview_temperature': 1.0, 'preview_top_k': 0, 'preview_seed': None,   # WaveNet.generate's sampling controls
+    'top_p': 1.0,                  # ... and its nucleus control (categorical head only; 1.0 = off)
     'checkpoint_format': 'npz',    # 'h5': Keras .weights.h5 exchange files (weights only, as the reference writes them)
     # data parallel: clip every replica's gradient to clipnorm BEFORE the all-reduce (the Keras 3 order) instead of the
     # reduced gradient after it; configuration, not state: checkpoints do not carry it
@@ -77,6 +78,13 @@ def main():
     run_name = os.path.splitext(os.path.basename(args.configfile))[0]
   if args.epochs is not None:
     config['epochs'] = args.epochs
+
+  top_p = config['top_p']
+  if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0 < top_p <= 1:
+    raise SystemExit(f'top_p must be a number in (0, 1] (got {top_p!r})')
+  if top_p < 1 and config['sampling_function'] != 'categorical':
+    raise SystemExit(f"top_p applies to the categorical head only (got top_p: {top_p} with sampling_function: "
+                     f"{config['sampling_function']}); remove the key or set it to 1.0")
 
   import contextlib
   import torch.distributed as dist
@@ -218,7 +226,8 @@ def main():
       samples = model.generate(preview, batch_size=nprev, condition=cond[:nprev] if conditioned else None,
                                use_queues=config['layers_per_block'] == 1,
                                temperature=float(config['preview_temperature']), top_k=int(config['preview_top_k']),
-                               seed=None if config['preview_seed'] is None else int(config['preview_seed']))
+                               seed=None if config['preview_seed'] is None else int(config['preview_seed']),
+                               top_p=float(top_p))
     torch.cuda.synchronize()
     tictoc = time.time() - tic
     print(f'Generation took {tictoc}s')

@@ -20,7 +20,7 @@ ACTIVATIONS = {None: 0, 'linear': 0, 'relu': 1, 'leaky_relu': 2, 'tanh': 3, 'sig
 HEADS = {'categorical': 0, 'logistic': 1, 'gaussian': 2}
 WN_MAX_FINAL = 8
 WN_MAX_MAPPING = 8
-WN_TOP_K_MAX_CLASSES = 1024   # top_k is offered for up to this many classes (WN_SAMPLE_FUSED_MAXC)
+WN_TOP_K_MAX_CLASSES = 1024   # top_k and top_p are offered for up to this many classes (WN_SAMPLE_FUSED_MAXC)
 
 
 class WnConfig(C.Structure):
@@ -38,8 +38,8 @@ class WnConfig(C.Structure):
 
 
 class WnSampling(C.Structure):
-  """struct wn_sampling (include/wn_hip.h): temperature, top-k and Philox key of a stochastic draw."""
-  _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('seed', C.c_uint64)]
+  """struct wn_sampling (include/wn_hip.h): temperature, top-k, Philox key and top-p (last; 0 = off) of a stochastic draw."""
+  _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('seed', C.c_uint64), ('top_p', C.c_float)]
 
 
 class WnLayerDesc(C.Structure):

@@ -109,7 +109,8 @@ class SoundCallback:
   averaged weights (WaveNet.averaged_weights())."""
 
   def __init__(self, log_dir, sampling_frequency: int, samples: int, apply_mulaw: bool, epoch_frequency: int = 1,
-               condition=None, use_fast=False, initial_sample=None, model=None, temperature=1.0, top_k=0, seed=None):
+               condition=None, use_fast=False, initial_sample=None, model=None, temperature=1.0, top_k=0, seed=None,
+               top_p=1.0):
     if use_fast not in ['both', True, False]:
       raise ValueError('use_fast must be one of True, False, "both"')
     if epoch_frequency < 1:
@@ -124,7 +125,7 @@ class SoundCallback:
     self.use_fast = use_fast
     self.model = model
     # sampling controls of the generate calls (additions; WaveNet.generate)
-    self.temperature, self.top_k, self.seed = temperature, top_k, seed
+    self.temperature, self.top_k, self.seed, self.top_p = temperature, top_k, seed, top_p
 
   def set_model(self, model):
     self.model = model
@@ -144,7 +145,7 @@ class SoundCallback:
     import numpy as np
     modes = [('fast', True), ('standard', False)] if self.use_fast == 'both' else [('standard', self.use_fast)]
     generated = {}
-    controls = dict(temperature=self.temperature, top_k=self.top_k, seed=self.seed)
+    controls = dict(temperature=self.temperature, top_k=self.top_k, seed=self.seed, top_p=self.top_p)
     for key, queued in modes:
       generated[key] = self.model.generate(self.samples, batch_size=5, condition=self.condition, use_queues=queued,
                                             **controls)

@@ -784,9 +784,10 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
       const int row = tile * 32 + i;
       if (row >= a.B) break;                          // wave-uniform
       const float* l = a.ws + a.out_off + (int64_t)row * C;
-      // (a.ctl is a kernel argument: the branch on the sampling controls is uniform, and off takes the draw of before)
+      // (a.ctl is a kernel argument: the branch on the sampling controls is uniform, and off takes the draw of before;
+      // a step under top_p takes the sampler launch instead of this tail, gn_head_check)
       const float v = a.tail == 1 ? wn_cat_det_row(l, C, lane, a.inv_lv)
-                      : a.ctl.on() ? wn_cat_rand_row<true>(l, C, lane, q, row, a.seed, a.offset, a.inv_lv, a.ctl)
+                      : a.ctl.on() ? wn_cat_rand_row<true, false>(l, C, lane, q, row, a.seed, a.offset, a.inv_lv, a.ctl)
                                    : wn_cat_rand_row(l, C, lane, q, row, a.seed, a.offset, a.inv_lv);
       if (lane == 0) {
         if (a.samp) a.samp[row] = v;
@@ -822,6 +823,7 @@ static int gn_head_check(const WnGenHeadArgs& a) {
       return WN_E_UNSUPPORTED;
     }
   if ((a.tail == 2 || a.tail == 4) && !(a.ctl.inv_T > 0.f)) { wn_set_error("gen_head: sampling controls not set"); return WN_E_INVALID; }
+  if (a.tail == 2 && a.ctl.top_p > 0.f) { wn_set_error("gen_head: a draw under top_p takes the sampler launch, not this tail"); return WN_E_INVALID; }
   return WN_OK;
 }
 int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, hipStream_t s) {

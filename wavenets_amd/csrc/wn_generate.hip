@@ -112,7 +112,7 @@ int sample_rows(wn_plan* p, const float* logits_rows, int B, bool deterministic,
 
 // The sampling arguments of the *_sampled entry points, checked before anything touches the device or any other argument
 // is looked at (head: WN_HEAD_*, classes: the categorical row length).  On success *ctl holds the controls the kernels
-// take: top_k >= classes is off.
+// take: top_k >= classes is off, top_p = 1 is off.
 int wn_sampling_check(const char* who, const wn_sampling* sp, int head, int classes, WnSampleCtl* ctl) {
   if (!sp) { wn_set_error("%s: sampling is null", who); return WN_E_INVALID; }
   const float T = sp->temperature;
@@ -125,10 +125,25 @@ int wn_sampling_check(const char* who, const wn_sampling* sp, int head, int clas
     wn_set_error("%s: top_k applies to the categorical head only (got top_k = %d with a mixture head)", who, (int)sp->top_k);
     return WN_E_INVALID;
   }
+  const float tp = sp->top_p;
+  if (!(tp >= 0.f && tp <= 1.0f)) {                       // NaN fails both comparisons
+    wn_set_error("%s: top_p must lie in (0, 1], or be 0 for off (got %g)", who, (double)tp);
+    return WN_E_INVALID;
+  }
+  const bool topp = tp > 0.f && tp < 1.0f;
+  if (topp && head != WN_HEAD_CATEGORICAL) {
+    wn_set_error("%s: top_p applies to the categorical head only (got top_p = %g with a mixture head)", who, (double)tp);
+    return WN_E_INVALID;
+  }
   ctl->T = T; ctl->inv_T = 1.0f / T;
   ctl->top_k = (sp->top_k >= classes) ? 0 : sp->top_k;
+  ctl->top_p = topp ? tp : 0.f;
   if (ctl->top_k > 0 && classes > wn_sample_top_k_max_classes()) {
     wn_set_error("%s: top_k is offered for up to %d classes (got %d)", who, wn_sample_top_k_max_classes(), classes);
+    return WN_E_UNSUPPORTED;
+  }
+  if (topp && classes > wn_sample_top_k_max_classes()) {
+    wn_set_error("%s: top_p is offered for up to %d classes (got %d)", who, wn_sample_top_k_max_classes(), classes);
     return WN_E_UNSUPPORTED;
   }
   return WN_OK;
@@ -429,7 +444,8 @@ extern "C" int wn_generate_sampled(wn_plan* p, const float* params, const float*
       // categorical heads: the sampling tail and the emit ride in the head launch too
       // (up to 8 utterances = one row per wave of the head workgroup: with more, the rows of a wave run one after the other
       // and the tail kernel's one wave per row finishes sooner -- measured 0.074 vs 0.068 ms per step at B = 32)
-      head_tail = p->c.head == WN_HEAD_CATEGORICAL && p->Cout <= 256 && B <= 8;
+      // (a stochastic step under top_p takes the sampler launch as well: the head kernel is built without the nucleus search)
+      head_tail = p->c.head == WN_HEAD_CATEGORICAL && p->Cout <= 256 && B <= 8 && (deterministic || !(ctl.top_p > 0.f));
       if (head_tail) {
         ha.tail = deterministic ? 1 : 2;
         ha.inv_lv = 1.0f / (float)(1 << (p->c.bits - 1));

@@ -292,13 +292,15 @@ int64_t wn_gen_relay128_floats(int B, int nblocks);
 struct WnEmit { float* out; int length; int step; float* xin_slot; };
 #define WN_EMIT_NONE (WnEmit{nullptr, 0, 0, nullptr})
 // sampling controls of a stochastic draw (wn_sample.h; semantics: include/wn_hip.h, struct wn_sampling): temperature T with
-// inv_T = 1 / T finite, top_k = 0 off (callers pass 0 for top_k >= classes).  on() false = the draw without controls.
+// inv_T = 1 / T finite, top_k = 0 off (callers pass 0 for top_k >= classes), top_p in (0, 1) or 0 off (callers pass 0 for
+// 1).  on() false = the draw without controls.
 struct WnSampleCtl {
   float T, inv_T;
   int32_t top_k;
-  __host__ __device__ bool on() const { return T != 1.0f || top_k > 0; }
+  float top_p;
+  __host__ __device__ bool on() const { return T != 1.0f || top_k > 0 || top_p > 0.f; }
 };
-#define WN_SAMPLE_CTL_OFF (WnSampleCtl{1.0f, 1.0f, 0})
+#define WN_SAMPLE_CTL_OFF (WnSampleCtl{1.0f, 1.0f, 0, 0.f})
 // the head of a generation step in one launch (wn_gen.hip)
 #define WN_GEN_HEAD_MAX 4
 struct WnGenHeadArgs {
@@ -322,7 +324,7 @@ struct WnGenHeadArgs {
   float* samp;                     // [B] samples (or null)
   WnEmit em;                       // output rows / network input slot
   float* guard;                    // range guard of the generate call (hidden activations are cast to fp16 hi | lo), or null
-  WnSampleCtl ctl;                 // tails 2 and 4: temperature / top-k (set it: all-zero bytes are not 'off')
+  WnSampleCtl ctl;                 // tails 2 and 4: temperature / top-k, top_p off (set it: all-zero bytes are not 'off')
 };
 int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s);
 int wn_gen_blocks_supported(int R, int D, int KS);

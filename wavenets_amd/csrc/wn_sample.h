@@ -89,6 +89,10 @@ struct WnCatCtlView {
     const float v = p[j];
     const uint32_t k = key(v);
     if (!(k > thr || (k == thr && j <= idx_cut))) return 0.f;
+    return term(v);
+  }
+  // the term of a kept class whose probability is v
+  __device__ __forceinline__ float term(float v) const {
     const float r = fmaxf(v, 0.f) / pmax;
     return inv_T == 1.0f ? r : expf(inv_T * logf(r));      // r = 1 -> exactly 1; r = 0 -> 0
   }
@@ -96,7 +100,9 @@ struct WnCatCtlView {
 // Builds the view: one wave per row, all 64 lanes active, every lane gets the same view.  The k-th largest key by
 // bisection on the key (at most 31 rounds of count(key >= mid), a ballot + popcount per register slot for C <= 256, a
 // strided loop over the row beyond), then the ties at the threshold by class index with ballot prefix counts.
-template <typename P>
+// TOPP false: built without the top-p search (ctl.top_p must be off) -- the head kernel of queued generation, whose
+// register allocation the search would disturb on every step, the default one included.
+template <bool TOPP = true, typename P>
 __device__ __forceinline__ WnCatCtlView<P> wn_cat_ctl_view(P p, int C, int lane, WnSampleCtl ctl) {
   using V = WnCatCtlView<P>;
   V w{p, 1.0f, ctl.inv_T, 0u, 0x7fffffff};
@@ -112,7 +118,8 @@ __device__ __forceinline__ WnCatCtlView<P> wn_cat_ctl_view(P p, int C, int lane,
   }
   m = wn_wave_max(m);
   w.pmax = m > 0.f ? m : 1.0f;                       // an all-zero row stays all zero (the draw then returns class C - 1)
-  if (ctl.top_k <= 0 || ctl.top_k >= C) return w;
+  const bool topk = ctl.top_k > 0 && ctl.top_k < C, topp = TOPP && ctl.top_p > 0.f && ctl.top_p < 1.0f;
+  if (!topk && !topp) return w;
   // count of classes whose key is >= t (t > 0 excludes the empty register slots, key 0) / == t, wave-uniform
   auto count_ge = [&](uint32_t t) {
     int c = 0;
@@ -124,14 +131,7 @@ __device__ __forceinline__ WnCatCtlView<P> wn_cat_ctl_view(P p, int C, int lane,
     }
     return c;
   };
-  // largest thr with count(key >= thr) >= top_k: lo always satisfies it (count(key >= 0) = C > top_k), hi never does
-  uint32_t lo = 0u, hi = V::key(m) + 1u;
-  while (hi - lo > 1u) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (count_ge(mid) >= ctl.top_k) lo = mid; else hi = mid;
-  }
-  w.thr = lo;
-  int need = ctl.top_k - count_ge(lo + 1u);               // of the ties at thr, the first `need` by class index
+  int need = 0;
   // slot s = classes 64 s .. 64 s + 63 in lane order; returns true once the need-th tie is found
   auto take = [&](int s, bool tie) {
     const unsigned long long mask = __ballot(tie);
@@ -141,15 +141,73 @@ __device__ __forceinline__ WnCatCtlView<P> wn_cat_ctl_view(P p, int C, int lane,
     w.idx_cut = 64 * s + __builtin_ctzll(hit);
     return true;
   };
+  // idx_cut: of the classes up to index cap whose key is t, the need-th by class index
+  auto cut_ties = [&](uint32_t t, int cap) {
+    if (regs) {
+      bool done = false;
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        if (!done) done = take(s, lane + 64 * s < C && kr[s] == t && lane + 64 * s <= cap);
+    } else {
+      for (int s = 0; 64 * s < C; ++s)
+        if (take(s, 64 * s + lane < C && V::key(p[min(64 * s + lane, C - 1)]) == t && 64 * s + lane <= cap)) break;
+    }
+  };
+  if (topk) {
+    // largest thr with count(key >= thr) >= top_k: lo always satisfies it (count(key >= 0) = C > top_k), hi never does
+    uint32_t lo = 0u, hi = V::key(m) + 1u;
+    while (hi - lo > 1u) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      if (count_ge(mid) >= ctl.top_k) lo = mid; else hi = mid;
+    }
+    need = ctl.top_k - count_ge(lo + 1u);                 // of the ties at thr, the first `need` by class index
+    cut_ties(lo, 0x7fffffff);
+    w.thr = lo;
+  }
+  if constexpr (!TOPP) return w;
+  if (!topp) return w;
+  // top-p on the set K that top-k kept (wk; all classes when top-k is off): with q_j = wk[j] and Q = sum q, the shortest
+  // prefix of the same ranking whose sum q reaches top_p Q.  mass(t) = sum of q over key >= t, every lane's terms in the
+  // order lane, lane + 64, ... and then wn_wave_sum, whatever t: each addition is monotone in its operands, so mass is
+  // monotone in t also as rounded, and where the partial sums are exactly representable the decisions are exact.
+  const V wk = w;
+  float qr[4] = {0.f, 0.f, 0.f, 0.f};
   if (regs) {
-    bool done = false;
 #pragma unroll
     for (int s = 0; s < 4; ++s)
-      if (!done) done = take(s, lane + 64 * s < C && kr[s] == lo);
-  } else {
-    for (int s = 0; 64 * s < C; ++s)
-      if (take(s, 64 * s + lane < C && V::key(p[min(64 * s + lane, C - 1)]) == lo)) break;
+      if (lane + 64 * s < C) qr[s] = wk[lane + 64 * s];
   }
+  auto mass_ge = [&](uint32_t t) {
+    float a = 0.f;
+    if (regs) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) a += kr[s] >= t ? qr[s] : 0.f;
+    } else {
+      for (int j = lane; j < C; j += 64) a += V::key(p[j]) >= t ? wk[j] : 0.f;
+    }
+    return wn_wave_sum(a);
+  };
+  const float Q = mass_ge(wk.thr);
+  if (!(Q > 0.f)) return w;                               // all-zero row
+  const float target = ctl.top_p * Q;
+  // largest thr with mass(key >= thr) >= target: lo = K's own threshold always satisfies it (target <= Q), hi never does
+  // (nothing lies above the largest key and target > 0).  At most 31 rounds, a wave sum each.
+  uint32_t lo = wk.thr, hi = V::key(m) + 1u;
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (mass_ge(mid) >= target) lo = mid; else hi = mid;
+  }
+  // mass(lo + 1) < target <= mass(lo): classes of K tie at lo, each with the term q_thr > 0; the smallest n with
+  // above + n q_thr >= target of them are kept, by class index
+  const float above = mass_ge(lo + 1u), q_thr = wk.term(__builtin_bit_cast(float, lo));
+  int n = (int)fminf(ceilf((target - above) / q_thr), 1024.f);
+  while (n > 1 && above + (float)(n - 1) * q_thr >= target) --n;
+  while (n < 1 || (n < C && above + (float)n * q_thr < target)) ++n;
+  // (n beyond the number of ties -- the rounding of mass(lo) against above + n q_thr -- keeps them all)
+  need = n;
+  w.thr = lo;
+  w.idx_cut = lo == wk.thr ? wk.idx_cut : 0x7fffffff;     // at K's own threshold only K's ties count
+  cut_ties(lo, w.idx_cut);
   return w;
 }
 
@@ -170,8 +228,8 @@ __device__ __forceinline__ float wn_cat_det_row(const float* l, int C, int lane,
 // Categorical head, stochastic draw straight from the logits: the probabilities are those wn_softmax_kernel stores, kept
 // in the LDS row q[0..C) instead of a (rows, C) tensor in HBM, so the drawn class is the one
 // sample_waveform(softmax(logits)) draws.  Every lane returns the sample value.
-// CTL: the draw under the sampling controls, from the view of the same LDS row.
-template <bool CTL = false>
+// CTL: the draw under the sampling controls, from the view of the same LDS row (TOPP: wn_cat_ctl_view).
+template <bool CTL = false, bool TOPP = CTL>
 __device__ __forceinline__ float wn_cat_rand_row(const float* l, int C, int lane, float* q, int64_t row, uint64_t seed,
                                                  uint64_t offset, float inv_lv, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF) {
   auto keep = [&](int j, float v) { q[j] = v; };
@@ -185,7 +243,7 @@ __device__ __forceinline__ float wn_cat_rand_row(const float* l, int C, int lane
   __builtin_amdgcn_wave_barrier();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   int result;
-  if constexpr (CTL) result = wn_draw_cat_row(wn_cat_ctl_view((const float*)q, C, lane, ctl), C, lane, row, seed, offset);
+  if constexpr (CTL) result = wn_draw_cat_row(wn_cat_ctl_view<TOPP>((const float*)q, C, lane, ctl), C, lane, row, seed, offset);
   else result = wn_draw_cat_row((const float*)q, C, lane, row, seed, offset);
   return (float)result * inv_lv - 1.0f;
 }

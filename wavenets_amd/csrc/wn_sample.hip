@@ -114,9 +114,12 @@ __global__ void wn_sample_rand_mix_kernel(const float* pred, int64_t rows, int M
 int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind,
                           uint64_t seed, uint64_t offset, float* out, hipStream_t s, WnSampleCtl ctl, WnEmit em) {
   if (rows <= 0) return WN_OK;
-  if (M > 0 && ctl.top_k > 0) { wn_set_error("sample_rand: top_k applies to the categorical head only"); return WN_E_INVALID; }
-  if (M <= 0 && ctl.top_k > 0 && C > WN_SAMPLE_FUSED_MAXC) {
-    wn_set_error("sample_rand: top_k over %d classes > %d", C, WN_SAMPLE_FUSED_MAXC);
+  if (M > 0 && (ctl.top_k > 0 || ctl.top_p > 0.f)) {
+    wn_set_error("sample_rand: top_k and top_p apply to the categorical head only");
+    return WN_E_INVALID;
+  }
+  if (M <= 0 && (ctl.top_k > 0 || ctl.top_p > 0.f) && C > WN_SAMPLE_FUSED_MAXC) {
+    wn_set_error("sample_rand: top_k / top_p over %d classes > %d", C, WN_SAMPLE_FUSED_MAXC);
     return WN_E_UNSUPPORTED;
   }
   if (M <= 0 && em.out) return wn_launch_sample_rand_cat_logits(pred, rows, C, bits, seed, offset, out, s, ctl, em);

@@ -696,9 +696,10 @@ class WaveNet(torch.nn.Module):
     _lib.check(_lib.lib().wn_quantize(_lib.ptr(x), _lib.ptr(idx), x.numel(), self.bits, _lib.stream_ptr()))
     return idx
 
-  def _sampling(self, temperature, top_k, seed, classes):
+  def _sampling(self, temperature, top_k, seed, classes, top_p=1.0):
     """The sampling controls of a stochastic draw as the C struct (semantics: include/wn_hip.h, struct wn_sampling),
-    checked as the library checks them, before any work is queued.  classes: row length of a categorical prediction."""
+    checked as the library checks them, before any work is queued.  classes: row length of a categorical prediction.
+    top_p: a real number in (0, 1]; 1.0 is off."""
     if isinstance(top_k, bool) or not isinstance(top_k, int):
       raise ValueError(f'top_k must be an int (got {top_k!r})')
     if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
@@ -713,20 +714,31 @@ class WaveNet(torch.nn.Module):
       raise ValueError(f'top_k applies to the categorical head only (got top_k = {top_k} with {self.sampling_function})')
     if 0 < top_k < classes and classes > _lib.WN_TOP_K_MAX_CLASSES:
       raise ValueError(f'top_k is offered for up to {_lib.WN_TOP_K_MAX_CLASSES} classes (got {classes})')
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float, np.integer, np.floating)):
+      raise ValueError(f'top_p must be a real number in (0, 1] (got {top_p!r})')
+    tp = np.float32(top_p)
+    if not (float(top_p) > 0 and tp > 0 and tp <= 1):        # NaN fails; so does a value that rounds to 0 in fp32
+      raise ValueError(f'top_p must lie in (0, 1] (got {top_p!r})')
+    if tp < 1 and self.sampling_function != 'categorical':
+      raise ValueError(f'top_p applies to the categorical head only (got top_p = {top_p} with {self.sampling_function})')
+    if tp < 1 and classes > _lib.WN_TOP_K_MAX_CLASSES:
+      raise ValueError(f'top_p is offered for up to {_lib.WN_TOP_K_MAX_CLASSES} classes (got {classes})')
     key = 0x0402 if seed is None else seed & 0xFFFFFFFFFFFFFFFF
-    return _lib.WnSampling(float(t), top_k, key)
+    return _lib.WnSampling(float(t), top_k, key, float(tp))
 
-  def sample_waveform(self, inputs, deterministic=False, temperature=1.0, top_k=0, seed=None):
+  def sample_waveform(self, inputs, deterministic=False, temperature=1.0, top_k=0, seed=None, top_p=1.0):
     """src/model.py:393-503: (B,T,C_out) -> (B,T,1).  Stochastic draws use Philox keyed by the
     reference's seed (4,2) -> 0x0402 plus a per-call offset (TF's stream is not reproducible).
     temperature / top_k / seed (additions): categorical rows are drawn from p^(1/T) over the
     top_k most probable classes (ties: lower class index first; 0 or >= classes = all), mixture rows from
-    [w / T | mu | s + ln T]; seed replaces the key 0x0402.  The defaults are the draw without them, bit for bit."""
+    [w / T | mu | s + ln T]; seed replaces the key 0x0402.  top_p in (0, 1] (categorical only; 1.0 = off): of the classes
+    top_k kept, the shortest prefix of the same ranking whose tempered mass reaches top_p of the total.  The defaults
+    are the draw without them, bit for bit."""
     pred = torch.as_tensor(inputs, dtype=torch.float32, device=self._device).contiguous()
     if pred.dim() != 3:
       raise ValueError('prediction must have shape (batch, samples, channels)')
     B, T, Cc = pred.shape
-    sampling = self._sampling(temperature, top_k, seed, Cc)
+    sampling = self._sampling(temperature, top_k, seed, Cc, top_p)
     out = torch.empty(B, T, 1, dtype=torch.float32, device=self._device)
     self._sample_calls += 1
     _lib.check(_lib.lib().wn_sample_waveform_sampled(_lib.HEADS[self.sampling_function], _lib.ptr(pred), B * T, Cc,
@@ -752,12 +764,12 @@ class WaveNet(torch.nn.Module):
 
   # ------------------------------------------------------------------ generation
   def generate(self, length, batch_size: int = 1, condition=None, sample=None,
-               use_queues=False, deterministic=False, temperature=1.0, top_k=0, seed=None):
+               use_queues=False, deterministic=False, temperature=1.0, top_k=0, seed=None, top_p=1.0):
     """src/model.py:258-307 (intended semantics; the reference's kwarg / rank bugs are not
     reproduced).  Returns (B, length, 1).
-    temperature / top_k / seed (additions) as in sample_waveform; an int seed is the Philox key of
+    temperature / top_k / seed / top_p (additions) as in sample_waveform; an int seed is the Philox key of
     the draws and seeds the initial noise window when `sample` is None.  seed=None is seed=0x0402."""
-    sampling = self._sampling(temperature, top_k, seed, 2 ** self.bits)
+    sampling = self._sampling(temperature, top_k, seed, 2 ** self.bits, top_p)
     if self.conditioning is not None and condition is None:
       raise ValueError('Conditioning must be provided.')
     if condition is not None:
