@@ -268,12 +268,14 @@ def layer_forward(x: torch.Tensor, layer_params: Sequence[torch.Tensor], *,
                   dilations: Sequence[int], activation_name: Optional[str],
                   residual: bool, has_skip: bool, cond: Optional[torch.Tensor] = None,
                   drop: Optional[Tuple[float, int]] = None,
-                  inner_branch: Optional[Sequence[torch.Tensor]] = None, kink_log: Optional[list] = None
-                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+                  inner_branch: Optional[Sequence[torch.Tensor]] = None, kink_log: Optional[list] = None,
+                  taps: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
   """WaveNetLayer.call, src/layers.py:178-224 (dropout omitted: rate 0 in parity runs).
 
   layer_params order: [dil kernels/biases ...], conv1 k/b, [conv_skip k/b], [conv_cond k/b].
   cond: (B, T, Cc) or (B, 1, Cc) (broadcast over T), already mapped.
+  taps: when given, receives the block's pre-gate u = [filter | gate] (conditioning included), the sigmoid gate and
+  z = tanh * gate (the graph's own tensors, so autograd can be asked for their gradients).
   """
   cur = _ParamCursor(list(layer_params))
   res = x
@@ -303,7 +305,10 @@ def layer_forward(x: torch.Tensor, layer_params: Sequence[torch.Tensor], *,
     h = h + conv1x1(cond, kc, bc)                  # src/layers.py:203-204
   D = h.shape[-1] // 2
   t, s = h[..., :D], h[..., D:]                    # src/layers.py:208
-  z = torch.tanh(t) * torch.sigmoid(s)             # src/layers.py:210
+  gate = torch.sigmoid(s)
+  z = torch.tanh(t) * gate                         # src/layers.py:210
+  if taps is not None:
+    taps['u'], taps['gate'], taps['z'] = h, gate, z
   x_out = conv1x1(z, kr, br)                       # src/layers.py:213
   skip = conv1x1(z, ks, bs) if has_skip else x_out  # src/layers.py:216-219
   if residual:
@@ -381,7 +386,7 @@ def model_forward(x: torch.Tensor, params: Sequence[torch.Tensor], cfg: OracleCo
   if cfg.conditioning == 'global':
     c = mapping_forward(cond, params, cfg).unsqueeze(1)   # (B,1,Cc), broadcast = tf.repeat
   h = causal_conv1d(x, ck, cb, 1)                          # src/model.py:228
-  skips, inter = [], {'h': [h]}
+  skips, inter = [], {'h': [h], 'u': [], 'gate': [], 'z': []}
   npb = _params_per_block(cfg)
   lpb = cfg.layers_per_block
   for b in range(cfg.blocks):
@@ -389,11 +394,14 @@ def model_forward(x: torch.Tensor, params: Sequence[torch.Tensor], cfg: OracleCo
     drop = None
     if dropout is not None and dropout[0] > 0:          # (rate, seed, step): training-mode dropout
       drop = (dropout[0], dropout_key(dropout[1], b, dropout[2]))
+    taps = {}
     h, sk = layer_forward(h, lp, dilations=dil[b * lpb:(b + 1) * lpb],
                           activation_name=cfg.activation, residual=cfg.use_residual,
                           has_skip=cfg.skip_channels is not None, cond=c, drop=drop,
-                          inner_branch=inner_branch[b] if inner_branch is not None else None, kink_log=kink_log)
+                          inner_branch=inner_branch[b] if inner_branch is not None else None, kink_log=kink_log, taps=taps)
     skips.append(sk)
+    for key in ('u', 'gate', 'z'):                       # per block: pre-gate, sigmoid gate, gated activation
+      inter[key].append(taps[key])
     inter['h'].append(h)
   if cfg.use_skip:
     h = skips[0]
