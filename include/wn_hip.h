@@ -136,7 +136,10 @@ int wn_prof_read(wn_plan* p, int32_t* launches, float* avg_ms);
  * what: 0 H[idx] | 1 Z[idx] | 2 saved sigmoid[idx] | 3 skip sum | 4 head activation[idx] | 5 logits |
  *       6 dL/d(final[idx] pre-activation) | 7 dL/d(skip sum) | 8 dL/du[idx] | 9 dL/dH[idx] | 10 max-abs slots |
  *       11 activated output of non-gated dilated conv i of block b, idx = b * (layers_per_block - 1) + i (any layout) |
- *       12 the per-row losses (B * T; overwritten by the L2 term's norms when l2_reg_factor > 0) */
+ *       12 the per-row losses (B * T; overwritten by the L2 term's norms when l2_reg_factor > 0) |
+ *       13 dL/d(pre-activation output of that conv): GP[b][i], idx and length (rows * D) as for 11 |
+ *       14 XD[idx], the dropped copy of block input idx (rows * channels).  It exists only while the calling state's
+ *          dropout rate is above 0; with dropout off it is WN_E_INVALID, like every other absent region */
 int wn_debug_ws_region(const wn_plan* p, int32_t B, int32_t T, int32_t what, int32_t idx, int64_t* off,
                        int64_t* len);
 /* the whole residual-block stack of a forward pass: one event pair per pass from the first block launch to

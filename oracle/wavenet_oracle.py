@@ -256,6 +256,15 @@ def dropout_key(seed: int, block: int, step: int) -> int:
 def dropout_keep_mask(n: int, key: int, rate: float) -> torch.Tensor:
   """Keep-mask of the product's stateless dropout hash over element indices 0..n-1 (the TF
   random stream of tf.keras.layers.Dropout, src/layers.py:108-111, is not reproducible)."""
+  if n <= 1 << 32:
+    # every index below 2^32 (hi = 0): the same hash in wrapping uint32 arithmetic, a few passes over a quarter of the bytes
+    x = np.arange(n, dtype=np.uint32)
+    x ^= np.uint32(int(_hash32(np.array([key & 0xFFFFFFFF], dtype=np.uint64))[0]))
+    x ^= x >> np.uint32(16); x *= np.uint32(0x7feb352d)
+    x ^= x >> np.uint32(15); x *= np.uint32(0x846ca68b)
+    x ^= x >> np.uint32(16)
+    x >>= np.uint32(8)
+    return torch.from_numpy(x.astype(np.float32) * np.float32(1.0 / 16777216.0) >= np.float32(rate))
   idx = np.arange(n, dtype=np.uint64)
   lo = idx & np.uint64(0xFFFFFFFF)
   hi = idx >> np.uint64(32)
@@ -275,7 +284,9 @@ def layer_forward(x: torch.Tensor, layer_params: Sequence[torch.Tensor], *,
   layer_params order: [dil kernels/biases ...], conv1 k/b, [conv_skip k/b], [conv_cond k/b].
   cond: (B, T, Cc) or (B, 1, Cc) (broadcast over T), already mapped.
   taps: when given, receives the block's pre-gate u = [filter | gate] (conditioning included), the sigmoid gate and
-  z = tanh * gate (the graph's own tensors, so autograd can be asked for their gradients).
+  z = tanh * gate (the graph's own tensors, so autograd can be asked for their gradients); 'xd', the input of the first
+  conv (the dropped copy of x under dropout, x itself otherwise); 'pre' and 'p', the pre-activation and the activated
+  output of every non-gated conv of the stack (empty lists at depth 1).
   """
   cur = _ParamCursor(list(layer_params))
   res = x
@@ -283,7 +294,9 @@ def layer_forward(x: torch.Tensor, layer_params: Sequence[torch.Tensor], *,
   if drop is not None:                             # src/layers.py:192-196: conv input only
     rate, key = drop
     keep = dropout_keep_mask(x.numel(), key, rate).view(x.shape).to(x.dtype)
-    h = x * keep * (1.0 / (1.0 - np.float32(rate)).astype(np.float32).item())
+    # (the scale as wn_launch_dropout forms it: one float32 division)
+    h = x * keep * float(np.float32(1) / (np.float32(1) - np.float32(rate)))
+  xd, pres, acts = h, [], []
   n = len(dilations)
   for i, d in enumerate(dilations):
     kern, b = cur.take(2)
@@ -293,6 +306,8 @@ def layer_forward(x: torch.Tensor, layer_params: Sequence[torch.Tensor], *,
       br_i = inner_branch[i] if inner_branch is not None else None
       pre = h
       h, nov = activation_with_branch(pre, activation_name, br_i)
+      pres.append(pre)
+      acts.append(h)
       if kink_log is not None and br_i is not None and activation_name in ('relu', 'leaky_relu'):
         own = (pre >= 0) if activation_name == 'leaky_relu' else (pre > 0)
         over = own != br_i.to(torch.bool)
@@ -309,6 +324,7 @@ def layer_forward(x: torch.Tensor, layer_params: Sequence[torch.Tensor], *,
   z = torch.tanh(t) * gate                         # src/layers.py:210
   if taps is not None:
     taps['u'], taps['gate'], taps['z'] = h, gate, z
+    taps['xd'], taps['pre'], taps['p'] = xd, pres, acts
   x_out = conv1x1(z, kr, br)                       # src/layers.py:213
   skip = conv1x1(z, ks, bs) if has_skip else x_out  # src/layers.py:216-219
   if residual:
@@ -386,7 +402,7 @@ def model_forward(x: torch.Tensor, params: Sequence[torch.Tensor], cfg: OracleCo
   if cfg.conditioning == 'global':
     c = mapping_forward(cond, params, cfg).unsqueeze(1)   # (B,1,Cc), broadcast = tf.repeat
   h = causal_conv1d(x, ck, cb, 1)                          # src/model.py:228
-  skips, inter = [], {'h': [h], 'u': [], 'gate': [], 'z': []}
+  skips, inter = [], {'h': [h], 'u': [], 'gate': [], 'z': [], 'xd': [], 'pre': [], 'p': []}
   npb = _params_per_block(cfg)
   lpb = cfg.layers_per_block
   for b in range(cfg.blocks):
@@ -400,7 +416,8 @@ def model_forward(x: torch.Tensor, params: Sequence[torch.Tensor], cfg: OracleCo
                           has_skip=cfg.skip_channels is not None, cond=c, drop=drop,
                           inner_branch=inner_branch[b] if inner_branch is not None else None, kink_log=kink_log, taps=taps)
     skips.append(sk)
-    for key in ('u', 'gate', 'z'):                       # per block: pre-gate, sigmoid gate, gated activation
+    # per block: pre-gate, sigmoid gate, gated activation, first conv's input, inner convs before / after the activation
+    for key in ('u', 'gate', 'z', 'xd', 'pre', 'p'):
       inter[key].append(taps[key])
     inter['h'].append(h)
   if cfg.use_skip:

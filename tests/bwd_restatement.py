@@ -1,14 +1,21 @@
-"""What every kernel of the backward phase of one training pass should have produced FROM ITS OWN INPUTS, in float64.
+"""What every kernel of the block stack's forward and of the backward phase of one training pass should have produced
+FROM ITS OWN INPUTS, in float64.
 
 Not a conftest and not a test: a plain helper (tests/test_bwd_restatement_cpu.py pins it against fp64 autograd of the
-oracle, tests/test_gpu_bwd_tile_walk.py compares the HIP kernels with it).  It is plain torch float64 on whatever
-device its inputs live on and never calls into libwn_hip.
+oracle, tests/test_gpu_bwd_tile_walk.py and tests/test_gpu_deep_tile_walk.py compare the HIP kernels with it).  It is
+plain torch float64 on whatever device its inputs live on and never calls into libwn_hip.
 
 A product is restated from the tensors its kernel read, not from other restated values: `GH[b]` from the stored `GU[b]`
 and `GH[b+1]`, `GU[b]` from the stored `GH[b+1]`, `AG[b]`, `Z[b]` and so on.  An error in one kernel therefore shows in
 that kernel's tensor alone, at the size of the error, and a chain of 7 blocks does not blur it.
 
-Scope: `layers_per_block == 1`, no dropout.
+Scope: any `layers_per_block`, with or without dropout, time-invariant (global) conditioning; `restate` is the backward
+phase (DESIGN.md sections 18, 19), `restate_forward` the block stack's forward, the input conv and the skip sum (section
+19).  The head's forward (HA, logits, loss rows) is not restated: HA and GF[nf] are taken as given.
+
+Notation: block b has the convs i = 0..L-1 (L = layers_per_block) with dilations d_i = dilation_schedule[b L + i].  Conv 0
+reads X_0 = XD[b] under dropout and H[b] otherwise, conv i > 0 reads X_i = P[b][i-1]; the output gradient of the last conv
+is G_{L-1} = GU[b], that of an inner conv G_i = GP[b][i], taken at its PRE-activation output.
 
 Workspace tensors (`ws`, keyed as below, each `(B, T, channels)`; regions of WaveNet.training_intermediate):
 
@@ -21,7 +28,13 @@ Workspace tensors (`ws`, keyed as below, each `(B, T, channels)`; regions of Wav
   ('GU', b)             region 8   d loss / d u of block b, [filter half | gate half]
   ('GH', b) b = 0..N    region 9   d loss / d H[b]
   'skipsum', 'g_skipsum' regions 3, 7   unfolded passes with use_skip only
+  ('P', b, i)  i = 0..L-2  region 11  activated output of inner conv i of block b
+  ('GP', b, i) i = 0..L-2  region 13  d loss / d (pre-activation output of inner conv i of block b)
+  ('XD', b)                region 14  dropped copy of H[b] (dropout passes only)
 """
+import functools
+
+import numpy as np
 import torch
 
 from oracle import wavenet_oracle as O
@@ -80,17 +93,89 @@ def gate_bwd(g_z, ag, z):
   return torch.cat([g_z * ag * (1 - a * a), g_z * z * (1 - ag)], dim=-1)
 
 
-def restate(cfg, params, x_in, cond, ws, folded):
+@functools.lru_cache(maxsize=8)
+def _keep_cpu(n, key, rate):
+  return O.dropout_keep_mask(n, key, rate)
+
+
+def drop_scale(rate):
+  """s = 1 / (1 - rate) as wn_launch_dropout forms it: in float32."""
+  return float(np.float32(1) / (np.float32(1) - np.float32(rate)))
+
+
+def keep_mask(like, b, dropout):
+  """keep_b of block b over the elements of `like` (B, T, R) in their workspace order; dropout = (rate, seed, step)."""
+  rate, seed, step = dropout
+  return _keep_cpu(like.numel(), O.dropout_key(seed, b, step), rate).view(like.shape).to(like.device)
+
+
+def _conv(x, w, bias, d):
+  """Causal dilated conv: sum_j shift_back(x, (KS - 1 - j) d) W[j] + bias."""
+  KS = w.shape[0]
+  return sum(_shift_back(x, (KS - 1 - j) * d) @ w[j] for j in range(KS)) + bias
+
+
+def _mapped(cfg, P, cond):
+  m = cond
+  for j in range(len(O.mapping_widths(cfg))):
+    m = O.activation(m @ P[f'mapping{j}/kernel'] + P[f'mapping{j}/bias'], cfg.mapping_activation)
+  return m
+
+
+def restate_forward(cfg, params, x_in, cond, ws, folded, dropout=None):
+  """The block stack's forward, the input conv and the skip sum; arguments as for `restate`.  ws needs H, Z, P and, under
+  dropout, XD.
+
+  Returns {key: float64 tensor}: ('H', b) for b = 0..N, ('XD', b) under dropout, ('P', b, i), ('AG', b), ('Z', b) and
+  'skipsum' (unfolded passes with use_skip).
+
+  XD[b] = where(keep_b, H[b] s, 0): the kernel does ONE fp32 multiply.  For float32-valued H the float64 product H s is
+  exact (24 + 24 significant bits), so rounding the returned tensor to float32 once IS that multiply and the comparison with
+  the kernel's XD is bitwise; for float64 H (the CPU pin) it is the oracle's own expression."""
+  N, L, D = cfg.blocks, cfg.layers_per_block, cfg.D
+  dil = O.dilation_schedule(cfg)
+  P = params
+  drop = dropout is not None and dropout[0] > 0
+  out = {('H', 0): _conv(x_in, P['causal/kernel'], P['causal/bias'], 1)}
+  crow = None
+  if cfg.conditioning == 'global':
+    crow = _mapped(cfg, P, cond)[:, None, :]         # (B, 1, Cc): the same row for every t of an utterance
+  for b in range(N):
+    x = ws['H', b]
+    if drop:
+      out['XD', b] = torch.where(keep_mask(x, b, dropout), x * drop_scale(dropout[0]), torch.zeros_like(x))
+      x = ws['XD', b]
+    for i in range(L - 1):
+      out['P', b, i] = O.activation(_conv(x, P[f'block{b}/dil{i}/kernel'], P[f'block{b}/dil{i}/bias'], dil[b * L + i]),
+                                    cfg.activation)
+      x = ws['P', b, i]
+    u = _conv(x, P[f'block{b}/dil{L - 1}/kernel'], P[f'block{b}/dil{L - 1}/bias'], dil[b * L + L - 1])
+    if crow is not None:
+      u = u + crow @ P[f'block{b}/conv_cond/kernel'][0] + P[f'block{b}/conv_cond/bias']
+    ag = torch.sigmoid(u[..., D:])
+    out['AG', b] = ag
+    out['Z', b] = torch.tanh(u[..., :D]) * ag
+    h = ws['Z', b][..., :D] @ P[f'block{b}/conv1/kernel'][0] + P[f'block{b}/conv1/bias']
+    out['H', b + 1] = h + ws['H', b] if cfg.use_residual else h          # the residual is the UNDROPPED block input
+  if cfg.use_skip and not folded:
+    conv = 'conv_skip' if cfg.skip_channels is not None else 'conv1'     # (no skip convs: the pre-residual 1x1 output)
+    out['skipsum'] = sum(ws['Z', b][..., :D] @ P[f'block{b}/{conv}/kernel'][0] + P[f'block{b}/{conv}/bias']
+                         for b in range(N))
+  return out
+
+
+def restate(cfg, params, x_in, cond, ws, folded, dropout=None):
   """cfg: O.OracleConfig.  params: {variable name: float64 tensor}.  x_in: (B, T, 1) raw input samples (the model's
   inputs, x[:, :-1]).  cond: (B, cond_inputs) or None.  ws: the workspace tensors of the module docstring, float64.
   folded: the pass contracted the skip path into the head's first conv (split-precision passes with a hidden head layer
   and skip_channels): no skip sum and no gradient of it exist, the blocks read GF[0] = dL/da through V(b) = W_s(b) W_f0.
 
-  Returns {key: float64 tensor}: ('GH', b), ('GU', b), ('GF', i) for i < nf, 'g_skipsum' (unfolded skip heads) and
-  ('param', name) for every trainable variable."""
-  if cfg.layers_per_block != 1:
-    raise NotImplementedError('layers_per_block > 1: the inner gradients have no workspace region')
-  N, KS, D = cfg.blocks, cfg.kernel_size, cfg.D
+  dropout: (rate, seed, step) of the pass, or None; with a rate above 0 ws holds ('XD', b).
+
+  Returns {key: float64 tensor}: ('GH', b), ('GU', b), ('GP', b, i), ('GF', i) for i < nf, 'g_skipsum' (unfolded skip
+  heads) and ('param', name) for every trainable variable."""
+  N, KS, D, L = cfg.blocks, cfg.kernel_size, cfg.D, cfg.layers_per_block
+  drop = dropout is not None and dropout[0] > 0
   S = cfg.skip_channels
   nf = len(cfg.final_layers_channels)
   dil = O.dilation_schedule(cfg)
@@ -123,8 +208,6 @@ def restate(cfg, params, x_in, cond, ws, folded):
     g_skip_fold = g_a @ w_f0.T                     # d loss / d skip sum, formed here only for dW_s / db_s
     skipsum = sum(Z(b) @ P[f'block{b}/conv_skip/kernel'][0] + P[f'block{b}/conv_skip/bias'] for b in range(N))
   for b in range(N):
-    d = dil[b]
-    w_d = P[f'block{b}/dil0/kernel']               # (KS, R, 2D)
     w_r = P[f'block{b}/conv1/kernel'][0]           # (D, R)
     # g_o: gradient at the 1x1 conv's output (before the residual add)
     g_o = GH(b + 1)
@@ -138,15 +221,26 @@ def restate(cfg, params, x_in, cond, ws, folded):
       else:
         g_z = g_z + g_skip @ w_s.T
     out['GU', b] = gate_bwd(g_z, ws['AG', b], Z(b))
-    # reversed dilated conv of the STORED g_u
-    g_x = sum(_shift_fwd(GU(b), (KS - 1 - j) * d) @ w_d[j].T for j in range(KS))
-    if cfg.use_residual:
-      g_x = g_x + GH(b + 1)
-    out['GH', b] = g_x
-    # parameter gradients of the block
-    out['param', f'block{b}/dil0/kernel'] = torch.stack(
-        [_outer(_shift_back(ws['H', b], (KS - 1 - j) * d), GU(b)) for j in range(KS)])
-    out['param', f'block{b}/dil0/bias'] = _rows(GU(b)).sum(0)
+    # the stack, last conv first: reversed dilated conv of the STORED output gradient G_i of conv i (G_{L-1} = GU[b],
+    # G_i = GP[b][i]); below an inner conv the derivative of its activation, through the STORED activated output
+    for i in range(L - 1, -1, -1):
+      d = dil[b * L + i]
+      w_d = P[f'block{b}/dil{i}/kernel']           # (KS, cin, cout)
+      g_i = GU(b) if i == L - 1 else ws['GP', b, i]
+      g_x = sum(_shift_fwd(g_i, (KS - 1 - j) * d) @ w_d[j].T for j in range(KS))
+      if i > 0:
+        out['GP', b, i - 1] = g_x * dact_from_output(ws['P', b, i - 1], cfg.activation)
+      else:
+        if drop:                                   # the mask of the forward; the residual term below is unmasked
+          g_x = torch.where(keep_mask(g_x, b, dropout), g_x * drop_scale(dropout[0]), torch.zeros_like(g_x))
+        if cfg.use_residual:
+          g_x = g_x + GH(b + 1)
+        out['GH', b] = g_x
+      # parameter gradients of conv i from the input it read
+      x_i = ws['P', b, i - 1] if i > 0 else (ws['XD', b] if drop else ws['H', b])
+      out['param', f'block{b}/dil{i}/kernel'] = torch.stack(
+          [_outer(_shift_back(x_i, (KS - 1 - j) * d), g_i) for j in range(KS)])
+      out['param', f'block{b}/dil{i}/bias'] = _rows(g_i).sum(0)
     out['param', f'block{b}/conv1/kernel'] = _outer(Z(b), g_o)[None]
     out['param', f'block{b}/conv1/bias'] = _rows(g_o).sum(0)
     if S is not None:

@@ -205,3 +205,49 @@ def test_plan_describe_text_is_the_recorded_one(lib):
   finally:
     lib.wn_debug_set(1, 0)
 
+
+
+def test_ws_regions_of_the_inner_gradients_and_the_dropped_inputs(lib):
+  """wn_debug_ws_region 13 = GP[b][i] (indexed and sized as region 11) and 14 = XD[idx], which exists only while the
+  calling state's dropout rate is above 0; absent regions are WN_E_INVALID."""
+  B, T = 2, 300
+  rows = B * T
+
+  def region(p, what, idx):
+    off, ln = C.c_int64(), C.c_int64()
+    rc = lib.wn_debug_ws_region(p, B, T, what, idx, C.byref(off), C.byref(ln))
+    return rc, off.value, ln.value
+
+  p = C.c_void_p(_plan(lib, _cfg(blocks=5, layers_per_block=5, channels=32, dilation_bound=256, activation='leaky_relu',
+                                 final_layers_channels=[128])))
+  assert p.value, lib.wn_last_error_string()
+  try:
+    total = lib.wn_plan_workspace_floats(p, B, T, 1)
+    spans = []
+    for idx in range(5 * 4):
+      rc11, o11, l11 = region(p, 11, idx)
+      rc13, o13, l13 = region(p, 13, idx)
+      assert rc11 == rc13 == _lib.WN_OK and l11 == l13 == rows * 32 and o11 != o13
+      assert 0 <= o13 and o13 + l13 <= total
+      spans += [(o11, l11), (o13, l13)]
+    assert region(p, 13, 20)[0] == region(p, 13, -1)[0] == _lib.WN_E_INVALID
+    assert region(p, 14, 0)[0] == _lib.WN_E_INVALID                       # dropout off: never laid out
+    assert lib.wn_plan_set_dropout(p, 0.1, 123, 1) == _lib.WN_OK
+    total = lib.wn_plan_workspace_floats(p, B, T, 1)
+    for idx in range(5):
+      rc, off, ln = region(p, 14, idx)
+      assert rc == _lib.WN_OK and ln == rows * 32 and 0 <= off and off + ln <= total
+      spans.append((off, ln))
+      assert off != region(p, 0, idx)[1]                                  # a copy, not H[idx] itself
+    assert region(p, 14, 5)[0] == _lib.WN_E_INVALID
+    spans.sort()
+    assert all(a + n <= b for (a, n), (b, _) in zip(spans, spans[1:]))    # no two of these regions overlap
+    assert lib.wn_plan_set_dropout(p, 0.0, 123, 1) == _lib.WN_OK
+    assert region(p, 14, 0)[0] == _lib.WN_E_INVALID
+  finally:
+    lib.wn_plan_destroy(p)
+  p = C.c_void_p(_plan(lib, _cfg(blocks=4, channels=32, skip_channels=64, final_layers_channels=[32])))
+  try:
+    assert region(p, 13, 0)[0] == _lib.WN_E_INVALID                       # depth 1: no inner convs
+  finally:
+    lib.wn_plan_destroy(p)

@@ -808,7 +808,10 @@ extern "C" int64_t wn_plan_workspace_floats(const wn_plan* p, int32_t B, int32_t
 // length), so that parity tests can compare saved activations and data gradients with the oracle's.
 //   what: 0 block input H[idx] (idx 0..N) | 1 gated activations Z of block idx | 2 saved sigmoid of block idx |
 //         3 skip sum | 4 head activation idx | 5 logits | 6 d loss / d (final layer idx output, pre-activation) |
-//         7 d loss / d skip sum | 8 d loss / d u of block idx ([rows][2D]) | 9 d loss / d H[idx] | 10 running max-abs slots
+//         7 d loss / d skip sum | 8 d loss / d u of block idx ([rows][2D]) | 9 d loss / d H[idx] | 10 running max-abs slots |
+//         11 activated output of non-gated conv i of block b (idx = b * (LPB - 1) + i, [rows][D]) | 12 loss rows |
+//         13 d loss / d (pre-activation output of that conv), indexed and laid out as 11 |
+//         14 dropped copy XD[idx] of block input idx ([rows][R]; only while the calling state's dropout rate is > 0)
 // Which kernel family each phase of a pass selects for this plan under the calling thread's switches -- the fast paths are
 // shape-specialised, everything else takes composed paths that are several times slower; this makes
 // the choice visible (WaveNet.kernel_report(), bench.py "kernel_families", WN_LOG_KERNELS=1 prints it once per plan).
@@ -884,6 +887,13 @@ extern "C" int wn_debug_ws_region(const wn_plan* p, int32_t B, int32_t T, int32_
       break;
     }
     case 12: *off = L.loss_rows; *len = rows; break;
+    case 13: {                           // gradient at the pre-activation output of that conv (same indexing as 11)
+      const int inner = p->LPB - 1;
+      if (inner > 0 && idx >= 0 && idx < p->N * inner && (size_t)(idx / inner) < L.GP.size() &&
+          (size_t)(idx % inner) < L.GP[idx / inner].size()) { *off = L.GP[idx / inner][idx % inner]; *len = rows * p->D; }
+      break;
+    }
+    case 14: if (in(L.XD.size())) { *off = L.XD[idx]; *len = rows * p->R; } break;   // (dropout off: never laid out)
     default: break;
   }
   if (*off < 0) { wn_set_error("ws_region: no such region (%d, %d)", what, idx); return WN_E_INVALID; }

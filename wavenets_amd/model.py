@@ -453,7 +453,10 @@ class WaveNet(torch.nn.Module):
 
   def training_intermediate(self, what: int, idx: int, B: int, T: int):
     """View on an intermediate the last loss_and_grads call (B utterances, T predicted samples) left in the
-    training workspace (wn_debug_ws_region; parity tests compare these with the oracle's autograd values)."""
+    training workspace (wn_debug_ws_region; parity tests compare these with the oracle's autograd values).
+    what 0..12 as listed in include/wn_hip.h; 13: GP[b][i], the gradient at the pre-activation output of inner conv i of
+    block b (idx = b * (layers_per_block - 1) + i, as for 11); 14: XD[idx], the dropped copy of block input idx, which
+    exists only with dropout > 0 (ValueError otherwise, as for every absent region)."""
     off, ln = C.c_int64(), C.c_int64()
     _lib.check(_lib.lib().wn_debug_ws_region(self._plan, B, T, what, idx, C.byref(off), C.byref(ln)))
     return self._ws['train'][off.value:off.value + ln.value]
