@@ -177,6 +177,25 @@ int wn_train_fwd_bwd(wn_plan* p, const float* params, const float* x_full, const
                      float* loss_out, float* pred_out, float* workspace, int64_t ws_floats,
                      void* stream);
 
+/* ---- Vector-Jacobian product of the network: the backward pass from a gradient the CALLER supplies (custom losses) ----
+ * Must follow a wn_forward_training(p, params, x, cond, B, T, ..., workspace) on the SAME workspace, in the same thread
+ * state (math mode, dropout rate / seed / step), with no other pass on that workspace in between: the saved activations
+ * are read from there.
+ * g_out (B,T,C_out): gradient w.r.t. what g_kind names: 0 = the output of WaveNet.call (probabilities for the
+ * categorical head -- the softmax vector-Jacobian product q (g - <g, q>) is formed from the logits in the workspace --,
+ * linear mixture parameters otherwise), 1 = the pre-softmax logits.  Plain fp32: a non-finite g_out gives non-finite
+ * gradients.
+ * grads: d<g_out, out>/d(params), the whole flat buffer, every tensor written (overwritten, not accumulated).
+ * g_x (B,T,1) and g_cond (B,cond_inputs): the gradients at the input waveform and the condition; optional (NULL = not
+ * formed).  Nothing of the built-in losses is added: no 1/global_batch, no L2 term.  wn_plan_set_train_phases and an
+ * armed step sample do not apply.
+ * WN_E_INVALID (checked before the device is touched): a null plan / params / x / g_out / grads / workspace, cond null
+ * on a conditioned plan, B < 1 or T < 1, g_kind outside {0, 1}, g_cond on a plan without conditioning, a workspace
+ * smaller than wn_plan_workspace_floats(p, B, T, 1). */
+int wn_vjp(wn_plan* p, const float* params, const float* x, const float* cond, int32_t B, int32_t T,
+           const float* g_out, int32_t g_kind, float* grads, float* g_x, float* g_cond,
+           float* workspace, int64_t ws_floats, void* stream);
+
 /* ---- WaveNet.test_step loss, src/model.py:362-381 (forward + loss only); loss_out: 3 device floats as above ---- */
 int wn_eval_loss(wn_plan* p, const float* params, const float* x_full, const float* cond,
                  int32_t B, int32_t T, int32_t global_batch, float* loss_out, float* pred_out,

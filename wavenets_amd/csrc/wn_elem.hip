@@ -535,6 +535,36 @@ int wn_launch_inconv_fwd(const float* x, const float* w, const float* bias, int 
   return WN_OK;
 }
 
+// The same conv's gradient at its input (wn_vjp): gx[b][t] = sum_tap sum_c w[tap][c] g[b][t + (KS-1-tap)][c], g = d / d y; a tap
+// whose row lies at or beyond T belongs to no frame of the utterance and is dropped (utterances never mix).  One wave per
+// (b, t), persistent; a lane sums its channels lane, lane + 64, ... tap by tap, then wn_wave_sum.  Any R, any KS.
+__global__ __launch_bounds__(256) void wn_inconv_bwd_data_kernel(const float* g, const float* w, int B, int T, int R, int KS,
+                                                                 float* gx) {
+  const int lane = threadIdx.x & 63;
+  const int64_t rows = (int64_t)B * T, stride = (int64_t)gridDim.x * 4;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += stride) {
+    const int t = (int)(row % T);
+    float acc = 0.f;
+    for (int tap = 0; tap < KS; ++tap) {
+      const int d = KS - 1 - tap;
+      if (t + d >= T) continue;                          // (wave-uniform)
+      const float* gr = g + (row + d) * R;
+      const float* wr = w + (int64_t)tap * R;
+      for (int c = lane; c < R; c += 64) acc = fmaf(wr[c], gr[c], acc);
+    }
+    acc = wn_wave_sum(acc);
+    if (lane == 0) gx[row] = acc;
+  }
+}
+int wn_launch_inconv_bwd_data(const float* g, const float* w, int B, int T, int R, int KS, float* gx, hipStream_t s) {
+  const int64_t rows = (int64_t)B * T;
+  if (rows <= 0) return WN_OK;
+  hipLaunchKernelGGL(wn_inconv_bwd_data_kernel, dim3((unsigned)std::min<int64_t>((rows + 3) / 4, 2048)), dim3(256), 0, s, g, w, B, T,
+                     R, KS, gx);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // Skip path folded into the head's first convolution (training passes).
 //   reference: skip_b = W_s(b)^T z_b + b_s(b)  (src/layers.py:216-217), x = sum_b skip_b  (src/model.py:235-236),

@@ -367,6 +367,8 @@ int wn_launch_inconv_wgrad(const float* x, const float* g, int B, int T, int R, 
                            int64_t P, int64_t w_off, int64_t b_off, hipStream_t s);
 int wn_launch_inconv_fwd(const float* x, const float* w, const float* bias, int B, int T, int R, int KS, float* y,
                          float* absmax_out, hipStream_t s);
+// gradient of that conv at its input: gx (B,T) from g = d / d y (B,T,R); any R, any KS
+int wn_launch_inconv_bwd_data(const float* g, const float* w, int B, int T, int R, int KS, float* gx, hipStream_t s);
 // out[0] = 1 when the split-precision kernels were fed a forward activation at or beyond `limit` (or a non-finite one)
 int wn_launch_guard_flag(const float* absmax, float limit, int enabled, float* out, hipStream_t s);
 // dst[0] = max(dst[0], src[0]) on the bit patterns (non-negative floats; inf / NaN stay on top)
@@ -385,6 +387,10 @@ int wn_launch_softmax(const float* logits, float* probs, int64_t rows, int C, hi
 int wn_launch_cat_loss(const float* logits, const int32_t* target, int64_t rows, int C,
                        float gscale, float* loss_rows, float* g_logits, float* absmax_out, hipStream_t s,
                        float* sample_out = nullptr, int bits = 8, uint64_t seed = 0, uint64_t offset = 0);
+// seed of a backward pass from a caller's gradient g (rows, C): dl = g (through_softmax 0) or the softmax vector-Jacobian
+// product q (g - <g, q>), q = softmax(logits); max-abs of dl published to absmax_out
+int wn_launch_vjp_seed(const float* logits, const float* g, int64_t rows, int C, int through_softmax, float* dl,
+                       float* absmax_out, hipStream_t s);
 // from_probs variant used by WaveNet.loss_fn(target, pred) on materialised probabilities
 int wn_launch_cat_loss_probs(const float* probs, const int32_t* target, int64_t rows, int C,
                              float* loss_rows, hipStream_t s);

@@ -100,6 +100,73 @@ int wn_launch_cat_loss(const float* logits, const int32_t* target, int64_t rows,
   return WN_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Seeds of a backward pass that starts from a caller's gradient (wn_vjp): they leave
+// d<g, out>/d(logits) where the loss kernels above leave d loss / d logits, with the same max-abs publication (the
+// split-precision backward products scale their operand by that slot).
+// Softmax vector-Jacobian product: g is the gradient at the probabilities q = softmax(l) that wn_softmax_kernel wrote
+// (the row in either storage form holds the same bits),  dot = sum_j g_j q_j  (a lane sums its classes lane, lane + 64, ...
+// in that order, then wn_wave_sum),  dl_j = q_j (g_j - dot).  Plain fp32, nothing clipped: a non-finite g gives a
+// non-finite row.  Persistent waves, one row at a time per wave, one publication per wave.
+template <bool REGS>
+__global__ __launch_bounds__(256) void wn_softmax_vjp_kernel(const float* logits, const float* g, int64_t rows, int C,
+                                                             float* dl, float* absmax_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  float gmax = 0.f;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += stride) {
+    const float* gr = g + row * C;
+    float* dr = dl + row * C;
+    auto vjp = [&](const auto& r) {
+      float dot = 0.f;
+      r.each([&](int j, float q) { dot += gr[j] * q; });
+      dot = wn_wave_sum(dot);
+      r.each([&](int j, float q) {
+        const float d = q * (gr[j] - dot);
+        dr[j] = d;
+        gmax = fmaxf(gmax, fabsf(d));
+      });
+    };
+    if (REGS) {
+      float v[4];
+      wn_cat_load4(logits + row * C, C, lane, v);
+      vjp(WnSoftmaxRegs(v, C, lane));
+    } else {
+      vjp(WnSoftmaxLoop(logits + row * C, C, lane));
+    }
+  }
+  if (absmax_out) {
+    gmax = wn_wave_max(gmax);
+    if (lane == 0) wn_absmax_publish(absmax_out, gmax);
+  }
+}
+// identity seed (gradient given at the logits, or at the linear parameters of a mixture head): a copy with the publication
+__global__ __launch_bounds__(256) void wn_seed_copy_kernel(const float* g, int64_t n, float* dl, float* absmax_out) {
+  float gmax = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float v = g[i];
+    dl[i] = v;
+    gmax = fmaxf(gmax, fabsf(v));
+  }
+  if (absmax_out) {
+    gmax = wn_wave_max(gmax);
+    if ((threadIdx.x & 63) == 0) wn_absmax_publish(absmax_out, gmax);
+  }
+}
+int wn_launch_vjp_seed(const float* logits, const float* g, int64_t rows, int C, int through_softmax, float* dl,
+                       float* absmax_out, hipStream_t s) {
+  if (rows <= 0 || C <= 0) return WN_OK;
+  if (!through_softmax) {
+    hipLaunchKernelGGL(wn_seed_copy_kernel, dim3(wn_blocks(rows * C, 256, 2048)), dim3(256), 0, s, g, rows * C, dl, absmax_out);
+  } else {
+    const dim3 grid((unsigned)std::min<int64_t>((rows + 3) / 4, 256 * 8));
+    if (C <= 256) hipLaunchKernelGGL(wn_softmax_vjp_kernel<true>, grid, dim3(256), 0, s, logits, g, rows, C, dl, absmax_out);
+    else hipLaunchKernelGGL(wn_softmax_vjp_kernel<false>, grid, dim3(256), 0, s, logits, g, rows, C, dl, absmax_out);
+  }
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
 __global__ __launch_bounds__(256) void wn_cat_loss_probs_kernel(const float* probs,
                                                                 const int32_t* target, int64_t rows,
                                                                 int C, float* loss_rows) {

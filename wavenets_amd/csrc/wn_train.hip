@@ -226,6 +226,7 @@ struct TrainCall {
   const float* mlast = nullptr;      // the mapped condition (input of every conv_cond)
   TrainPaths tp;                     // backward half: the kernel families of this call
   bool cond_batched = false;
+  float* g_x = nullptr; float* g_cond = nullptr;   // wn_vjp: gradients at the input waveform / the condition (null: not formed)
   int64_t pm = 0;                    // folded skip path: row pitch of the slab of M = Z^T dL/da with the column sums behind it
   float* am_GF(int i) const { return am + slot.gf(i); }
   float* am_GU(int b) const { return am + slot.gu(b); }
@@ -235,6 +236,19 @@ struct TrainCall {
   struct Strided { int64_t off, stride; };
   Strided strided(int t0, int t1) const { return {p->tensors[t0].off, p->N > 1 ? p->tensors[t1].off - p->tensors[t0].off : 0}; }
   Strided skip_w{0, 0}, skip_b{0, 0};   // conv_skip kernels / biases
+
+  // what every entry point sets the same way: buffers, the training layout of (B, T), the max-abs slots (host only)
+  void bind(wn_plan* p_, const float* params_, const float* cond_, int B_, int T_, float* grads_, float* workspace, hipStream_t s_) {
+    p = p_; params = params_; x_full = nullptr; cond = cond_; B = B_; T = T_; global_batch = B_; n_replicas = 1;
+    grads = grads_; loss_out = nullptr; pred_out = nullptr; ws = workspace; s = s_;
+    L = make_layout(p, B, T, true);
+    rows = (int64_t)B * T;
+    inputs = workspace + L.probs;
+    am = workspace + L.absmax;
+    nf = (int)p->finals.size();
+    slot = AbsmaxSlots{nf, p->N, p->LPB};
+    am_gskip = am + slot.gskip();
+  }
 
   // ---- forward + loss (+ the armed step sample, the L2 loss term, the range flag): src/model.py:319-334 ----
   int forward_and_loss() {
@@ -581,12 +595,19 @@ struct TrainCall {
     if (p->c.cond_inputs > 0) {
       const float* gm_cur = ws + L.g_m0;      // gradient w.r.t. post-activation output of the last Dense
       float* gm_other = ws + L.g_m1;
+      if (g_cond && p->mapping.empty())       // the blocks read the condition itself
+        WN_HIP_CHECK(hipMemcpyAsync(g_cond, gm_cur, (int64_t)B * p->Cc * sizeof(float), hipMemcpyDeviceToDevice, s));
       for (int j = (int)p->mapping.size() - 1; j >= 0; --j) {
         const ConvInfo& c = p->mapping[j];
         const float* yin = (j == 0) ? cond : ws + L.M[j - 1];
         // pre-activation gradient g_pre = g * act'(M[j])  (tiny: B x width)
         rc = wn_launch_dact_mul(gm_cur, ws + L.M[j], gm_other, (int64_t)B * c.cout, p->c.mapping_activation, s);
         if (rc) return rc;
+        if (j == 0 && g_cond) {   // wn_vjp: the gradient at the condition, g_pre W_0^T (B x cond_inputs)
+          rc = wn_launch_sgemm_small_batched(gm_other, c.cout, 1, 0, params + p->tensors[c.kernel_t].off, 1, c.cout, 0, g_cond, c.cin, 0,
+                                             B, c.cin, c.cout, 1, nullptr, 0, s);
+          if (rc) return rc;
+        }
         if (cond_small(p)) {
           // dW = yin^T g_pre (cin x cout, contraction over the B utterances), db = column sums of g_pre
           rc = wn_launch_sgemm_small_batched(yin, 1, c.cin, 0, gm_other, c.cout, 1, 0, grads + p->tensors[c.kernel_t].off, c.cout, 0,
@@ -617,7 +638,8 @@ struct TrainCall {
     return WN_OK;
   }
 
-  int backward() {
+  // ---- the backward pass from d / d logits in GF.back() (max-abs in am_GF(nf - 1)): of a loss of the step, or a caller's ----
+  int backward_from_logits() {
     int rc;
     fragbase = ws + L.frag;
     slab = ws + L.slab;
@@ -641,6 +663,15 @@ struct TrainCall {
     if ((rc = chain_backward())) return rc;
     if ((rc = weight_gradients())) return rc;
     if ((rc = mapping_backward())) return rc;
+    // the input conv's data gradient: GH[0] is formed by every chain (only wn_vjp asks for it)
+    if (g_x)
+      return wn_launch_inconv_bwd_data(ws + L.GH[0], params + p->tensors[p->causal.kernel_t].off, B, T, p->R, p->KS, g_x, s);
+    return WN_OK;
+  }
+
+  int backward() {
+    int rc = backward_from_logits();
+    if (rc) return rc;
     // ---- L2 regulariser, src/model.py:331-334: its gradient (the loss term is formed with the loss, above) ----
     if (p->c.l2_reg_factor > 0.f) {
       rc = wn_launch_axpy_table(grads, params, p->d_kdesc, (int)p->kdesc.size(), 2.0f * p->c.l2_reg_factor / (float)n_replicas, s);
@@ -668,18 +699,12 @@ extern "C" int wn_train_fwd_bwd(wn_plan* p, const float* params, const float* x_
                                 void* stream) {
   if (!p || !params || !x_full || !workspace || !loss_out || !grads || B < 1 || T < 1) { wn_set_error("train_fwd_bwd: bad arguments"); return WN_E_INVALID; }
   TrainCall c{wnp::ex(p)};
-  c.p = p; c.params = params; c.x_full = x_full; c.cond = cond; c.B = B; c.T = T;
+  c.bind(p, params, cond, B, T, grads, workspace, (hipStream_t)stream);
+  c.x_full = x_full;
   c.global_batch = global_batch > 0 ? global_batch : B;
   c.n_replicas = n_replicas > 0 ? n_replicas : 1;
-  c.grads = grads; c.loss_out = loss_out; c.pred_out = pred_out; c.ws = workspace; c.s = (hipStream_t)stream;
-  c.L = make_layout(p, B, T, true);
+  c.loss_out = loss_out; c.pred_out = pred_out;
   if (ws_floats < c.L.total) { wn_set_error("train_fwd_bwd: workspace too small (%lld < %lld floats)", (long long)ws_floats, (long long)c.L.total); return WN_E_INVALID; }
-  c.rows = (int64_t)B * T;
-  c.inputs = workspace + c.L.probs;
-  c.am = workspace + c.L.absmax;
-  c.nf = (int)p->finals.size();
-  c.slot = AbsmaxSlots{c.nf, p->N, p->LPB};
-  c.am_gskip = c.am + c.slot.gskip();
   // A caller may run the step as two calls (wn_plan_set_train_phases 1, then 2) and queue work of its own in between --
   // the Python mirror reads the loss and the metrics back from there, 4 ms before the step ends.  Everything the second
   // half needs lives in the workspace.
@@ -688,6 +713,31 @@ extern "C" int wn_train_fwd_bwd(wn_plan* p, const float* params, const float* x_
   if (phases & 1) rc = c.forward_and_loss();
   if (!rc && (phases & 2)) rc = c.backward();
   return rc;
+}
+
+// Backward pass from a caller's gradient at the network output (include/wn_hip.h): the saved activations of the
+// wn_forward_training call before it are in the workspace; the seed kernel stands where the loss stage stands in a step.
+extern "C" int wn_vjp(wn_plan* p, const float* params, const float* x, const float* cond, int32_t B, int32_t T,
+                      const float* g_out, int32_t g_kind, float* grads, float* g_x, float* g_cond,
+                      float* workspace, int64_t ws_floats, void* stream) {
+  if (!p || !params || !x || !g_out || !grads || !workspace) { wn_set_error("vjp: bad arguments (null plan, params, x, g_out, grads or workspace)"); return WN_E_INVALID; }
+  if (B < 1 || T < 1) { wn_set_error("vjp: B and T must be >= 1 (got %d, %d)", (int)B, (int)T); return WN_E_INVALID; }
+  if (g_kind != 0 && g_kind != 1) { wn_set_error("vjp: g_kind must be 0 (network output) or 1 (logits) (got %d)", (int)g_kind); return WN_E_INVALID; }
+  if (p->c.cond_inputs > 0 && !cond) { wn_set_error("vjp: the plan is conditioned and cond is null"); return WN_E_INVALID; }
+  if (p->c.cond_inputs <= 0 && g_cond) { wn_set_error("vjp: g_cond on a plan without conditioning"); return WN_E_INVALID; }
+  TrainCall c{wnp::ex(p)};
+  c.bind(p, params, cond, B, T, grads, workspace, (hipStream_t)stream);
+  c.g_x = g_x; c.g_cond = g_cond;
+  if (ws_floats < c.L.total) { wn_set_error("vjp: workspace too small (%lld < %lld floats)", (long long)ws_floats, (long long)c.L.total); return WN_E_INVALID; }
+  hipStream_t s = c.s;
+  // the weight-gradient schedule reads the input waveform from the workspace (a training step's shift_split leaves it there)
+  WN_HIP_CHECK(hipMemcpyAsync(c.inputs, x, c.rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+  // (the forward pass without a fused loss writes none of these slots)
+  WN_HIP_CHECK(hipMemsetAsync(c.am, 0, c.L.n_absmax * sizeof(float), s));
+  const int rc = wn_launch_vjp_seed(workspace + c.L.logits, g_out, c.rows, p->Cout,
+                                    g_kind == 0 && p->c.head == WN_HEAD_CATEGORICAL, workspace + c.L.GF.back(), c.am_GF(c.nf - 1), s);
+  if (rc) return rc;
+  return c.backward_from_logits();
 }
 
 extern "C" int wn_adam_step_guarded(wn_plan* p, float* params, const float* grads, float* m, float* v, int64_t step,

@@ -93,6 +93,81 @@ class _Mean:
     return self.total / max(self.count, 1)
 
 
+class _NetFn(torch.autograd.Function):
+  """WaveNet.differentiable: wn_forward_training on the model's training workspace, wn_vjp from the gradient autograd
+  hands back.  Inputs (x, cond, flat_params) and a zero-size anchor that keeps the node alive."""
+
+  @staticmethod
+  def forward(ctx, x, cond, flat_params, anchor, model, drop, want_probs):
+    L = _lib.lib()
+    B, T = x.shape[0], x.shape[1]
+    x, cond = x.detach(), (cond.detach() if cond is not None else None)
+    # the workspace layout depends on the dropout rate in force: set it first (off unless this pass draws a mask)
+    if drop:
+      model._arm_dropout()
+    else:
+      model._set_dropout_state(0.0, 0)
+    state = (model.dropout if drop else 0.0, model._drop_armed_step if drop else 0)
+    try:
+      ws = model._workspace('train', L.wn_plan_workspace_floats(model._plan, B, T, 1))
+      model._train_gen += 1
+      out = torch.empty(B, T, model.spec.out_channels, dtype=torch.float32, device=model._device)
+
+      def run():
+        _lib.check(L.wn_forward_training(model._plan, _lib.ptr(flat_params), _lib.ptr(x), _lib.ptr(cond), B, T,
+                                         _lib.ptr(out) if want_probs else None, None if want_probs else _lib.ptr(out),
+                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+      run()
+      mode = L.wn_debug_value(1)
+      slot = L.wn_plan_range_slot(model._plan, B, T, 1)
+      if model.range_check and mode != 1 and model._guard_over(ws[slot:slot + 1].clone(), drop):
+        with model.exact_fp32():
+          run()
+        mode = 1
+    finally:
+      model._set_dropout_state(model.dropout, model._drop_armed_step)
+    ctx.model, ctx.mode, ctx.drop_state, ctx.stamp, ctx.done = model, mode, state, model._train_gen, False
+    ctx.want_probs = want_probs
+    ctx.save_for_backward(x, cond)
+    return out
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable          # second derivatives are refused, not returned without a graph
+  def backward(ctx, g):
+    model = ctx.model
+    if ctx.done:
+      raise RuntimeError('differentiable: this graph has already been run backward (one pass of activations is kept: '
+                         'retain_graph re-runs are not supported; call differentiable again)')
+    if model._train_gen != ctx.stamp:
+      raise RuntimeError('differentiable: another pass used the training workspace between forward and backward '
+                         '(loss_and_grads / train_step, call(training=True) or another differentiable), or the '
+                         'weights changed (optimizer step, set_weights): the saved activations are gone or stale; '
+                         'one graph is alive at a time')
+    model._not_averaged('backward of differentiable')
+    ctx.done = True
+    x, cond = ctx.saved_tensors
+    flat_params = model.flat_params                # (read in place: the optimizer writes it through the library)
+    L = _lib.lib()
+    B, T = x.shape[0], x.shape[1]
+    g = g.to(torch.float32).contiguous()
+    need_x, need_c, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+    g_x = torch.empty_like(x) if need_x else None
+    g_c = torch.empty_like(cond) if (need_c and cond is not None) else None
+    ws = model._ws['train']
+    # the math mode and the mask of the pass that was kept, whatever the calling thread's are now
+    prev = L.wn_debug_value(1)
+    L.wn_debug_set(1, ctx.mode)
+    model._set_dropout_state(*ctx.drop_state)
+    try:
+      _lib.check(L.wn_vjp(model._plan, _lib.ptr(flat_params), _lib.ptr(x), _lib.ptr(cond), B, T, _lib.ptr(g),
+                          0 if ctx.want_probs else 1, _lib.ptr(model.flat_grads), _lib.ptr(g_x), _lib.ptr(g_c),
+                          _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    finally:
+      L.wn_debug_set(1, prev)
+      model._set_dropout_state(model.dropout, model._drop_armed_step)
+    return g_x, g_c, (model.flat_grads.clone() if need_p else None), None, None, None, None
+
+
 class WaveNet(torch.nn.Module):
   """WaveNet model class (src/model.py:11-556)."""
   _TAIL_METRICS = 5      # device-reduced metric slots behind {loss, reg_loss, range_flag} in the gradient bucket
@@ -162,6 +237,11 @@ class WaveNet(torch.nn.Module):
     self._log_mirror, self._log_event = None, None
     self._drop_step = 0                   # training calls made so far (dropout mask counter; saved by io.save_weights)
     self._fused_step_sample = True        # train_step draws its metric sample inside the library
+    self._drop_armed_step = 0             # the mask counter last handed to the library
+    # generation stamp of the 'train' workspace: every pass that writes it bumps the stamp, and the backward of a
+    # differentiable() graph refuses to run on activations that are no longer its own
+    self._train_gen = 0
+    self._vjp_anchor = None
     # structure handles (attribute names of the reference)
     dil = s.dilations
     lpb = s.layers_per_block
@@ -298,6 +378,7 @@ class WaveNet(torch.nn.Module):
 
   def set_weights(self, weights):
     self._not_averaged('set_weights')
+    self._train_gen += 1                  # a differentiable() graph of the old weights is void
     if len(weights) != len(self._names):
       raise ValueError(f'expected {len(self._names)} arrays, got {len(weights)}')
     for t, w in zip(self.trainable_variables, weights):
@@ -403,6 +484,7 @@ class WaveNet(torch.nn.Module):
     out = torch.empty(B, T, self.spec.out_channels, dtype=torch.float32, device=self._device)
     fn = L.wn_forward_training if training else L.wn_forward
     if training:
+      self._train_gen += 1
       # the Dropout layers are active (src/layers.py:195-196): a fresh mask per call, as in a training step
       self._arm_dropout()
 
@@ -493,6 +575,7 @@ class WaveNet(torch.nn.Module):
     if self.dropout > 0:
       step = self._drop_step * self._world() + self._rank() + 1
       _lib.check(_lib.lib().wn_plan_set_dropout(self._plan, self.dropout, self._seed, step))
+      self._drop_armed_step = step
       self._drop_step += 1
 
   def loss_and_grads(self, data, global_batch=None, n_replicas=None, want_pred=False, want_sample=False,
@@ -519,6 +602,7 @@ class WaveNet(torch.nn.Module):
     L = _lib.lib()
     self._log_kernels_once()
     ws = self._workspace('train', L.wn_plan_workspace_floats(self._plan, B, T, 1))
+    self._train_gen += 1
     # train_step keeps {loss, reg_loss} in the gradient bucket's tail (one all-reduce); other callers get their own tensor
     loss = self._grad_bucket[self.flat_params.numel():] if _loss_in_bucket else \
         torch.empty(3, dtype=torch.float32, device=self._device)
@@ -688,6 +772,47 @@ class WaveNet(torch.nn.Module):
       elif not hasattr(metric, 'update_state_device'):
         metric.update_state(x[:, 1:, :], sample)
     return {m.name: m.result() for m in self.metrics if m.name != 'reg_loss'}
+
+  # ------------------------------------------------------------------ autograd
+  def differentiable(self, inputs, training=False, output='probs'):
+    """The network as one ``torch.autograd`` node: returns ``(B, T, C_out)`` with a ``grad_fn``, for losses the training
+    step does not have built in (masks, weights, label smoothing, distillation, a loss on the expected sample, a gradient
+    at the input waveform or the condition).  DESIGN.md section 20.
+
+    ``output='probs'`` is what ``call()`` returns, ``'logits'`` the pre-softmax head output; for the mixture heads both
+    are the same linear parameters.  A loss of the form ``-log p[target]`` on ``'probs'`` meets ``0 * inf`` where a
+    probability underflows: such losses take ``output='logits'`` and ``torch.log_softmax``.  A non-finite gradient
+    handed to ``backward`` gives non-finite gradients (nothing is clipped or guarded there).
+
+    ``training=True`` on a model with ``dropout > 0`` draws a fresh mask exactly as ``call(training=True)`` does;
+    otherwise the Dropout layers are off for the pass.  The forward range guard is that of ``call()``: a tripped pass is
+    repeated in exact fp32, and backward runs in the math mode (and on the mask) of the pass that was kept, wherever
+    it is called from.
+
+    ``backward`` always leaves d<g, out>/d(theta) in ``model.flat_grads`` (overwritten, as ``loss_and_grads`` does; nothing
+    of the built-in losses is added: no 1/global_batch, no L2 term), so ``model.optimizer.apply_gradients(model)`` takes
+    the step.  It also reaches ``flat_params.grad`` only after ``flat_params.requires_grad_(True)``; the gradients at
+    the waveform and the condition are formed only when those tensors require grad.  Under data parallelism the caller
+    reduces ``flat_grads`` itself (``dp.allreduce_gradients``).
+
+    One graph is alive at a time: the saved activations live in the model's training workspace.  ``backward`` raises
+    RuntimeError when another pass used that workspace since (``loss_and_grads``, ``train_step``,
+    ``call(training=True)``, another ``differentiable``), when the weights changed since (``optimizer.apply_gradients``,
+    ``finalize_variable_values``, ``set_weights``), on a second run of the same graph (``retain_graph``) and under
+    ``create_graph=True`` (no second derivatives).  Writing ``flat_params`` by hand in between is not detected."""
+    if output not in ('probs', 'logits'):
+      raise ValueError(f"output must be 'probs' or 'logits' (got {output!r})")
+    self._not_averaged('differentiable')
+    x, cond = self._split_inputs(inputs)
+    if self._vjp_anchor is None:
+      # the node must exist even when no input asks for a gradient (flat_grads is its product): a zero-size input that does
+      self._vjp_anchor = torch.zeros(0, dtype=torch.float32, device=self._device, requires_grad=True)
+    return _NetFn.apply(x, cond, self.flat_params, self._vjp_anchor, self, bool(training and self.dropout > 0),
+                        output == 'probs')
+
+  def _set_dropout_state(self, rate, step):
+    if self.dropout > 0:
+      _lib.check(_lib.lib().wn_plan_set_dropout(self._plan, rate, self._seed, step))
 
   # ------------------------------------------------------------------ sampling / loss
   def prepare_target(self, x):

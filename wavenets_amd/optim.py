@@ -75,6 +75,7 @@ class Adam:
     mode tripped and the caller repeats the step with the exact-fp32 kernels, see WaveNet.train_step)."""
     self.build(model)
     self.iterations += 1
+    model._train_gen = getattr(model, '_train_gen', 0) + 1      # the weights move: a differentiable() graph of the old ones is void
     if self.use_ema:
       f = self.ema_overwrite_frequency
       _lib.check(_lib.lib().wn_adam_step_ema(
@@ -98,4 +99,5 @@ class Adam:
     if getattr(model, '_averaged', None) is not None:
       raise RuntimeError('finalize_variable_values inside averaged_weights(): leave the scope first')
     self.build(model)
+    model._train_gen = getattr(model, '_train_gen', 0) + 1
     model.flat_params.data.copy_(self.ema)
