@@ -142,12 +142,15 @@ struct WnWgPair {
   int64_t w_off, b_off;            // dW[k][n] -> slab row + w_off + k * N + n; db -> slab row + b_off (or < 0)
   int64_t gmax_off;                // running max-abs of G, or < 0
   int32_t shift;                   // X row = t - shift
-  union { int32_t pad_; int32_t nseg; };   // segmented X (kinds 7 / 8): segments of X this job reads
+  union { int32_t pad_; int32_t nseg; };   // segmented X (kinds 7 / 8): segments of X this job reads (>= 1)
   // transposed-read kernel, two-source form (kind 6): the upper half of G's columns comes from a second tensor and its
   // product goes to a second slab -- dW_r = z^T g_o and M = z^T dL/da (folded skip path) from ONE read of z
   // (segmented X: seg_stride = floats between two segments of X, in g2_off's place)
   union { int64_t g2_off; int64_t seg_stride; };
   int64_t w2_off, b2_off, gmax2_off;
+  // segmented X with a second operand per segment (kind 7): dW_r(b) = z(b)^T g_o(b) of each 64-channel block beside M from
+  // the same read of z -- g_o [rows][64], its running max-abs (or < 0), dW_r / db_r inside a row of the second slab
+  struct Seg { int64_t g_off, gmax_off, w_off, b_off; } seg[2];
 };
 int wn_wgrad_pair_kind(int K, int N);
 int wn_launch_wgrad_pairs(int kind, const WnWgPair* d_jobs, int njobs, float* ws, float* slab, int64_t P, int B, int T,

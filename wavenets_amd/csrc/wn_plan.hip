@@ -231,8 +231,8 @@ TrainPaths train_paths(const wn_plan* p) {
   // other shapes stay on the generic job table (deeper stacks without split-precision images: in exact fp32)
   t.wg = layerk ? (p->LPB > 1 ? WG_LAYER_INNER : WG_LAYER) : pairk ? WG_TR_PAIRS : (p->LPB > 1 && !t.deep16) ? WG_GENERIC_FP32 : WG_GENERIC;
   // the folded skip path's M = Z^T dL/da: in the dW_r jobs of 128-channel blocks (one read of z); 64- / 32-channel
-  // blocks: transposed-read jobs over the z of four / eight blocks at a time against one read of dL/da (wn_wgrad_tr
-  // kinds 7 / 8); other widths: wn_wgrad_skip_kernel
+  // blocks: transposed-read jobs over the z of two / eight blocks at a time against one read of dL/da (wn_wgrad_tr
+  // kinds 7 / 8), the 64-channel ones with the blocks' dW_r, db_r from the same read of z; other widths: wn_wgrad_skip_kernel
   const bool m128 = t.fold && p->fold_F0 == 128 && p->Dp == p->D && p->S > 0;
   t.mfused = pairk && p->D == 128 && m128;
   t.mtr = (layerk && m128) ? (p->D == 64 ? 7 : (p->D == 32 ? 8 : 0)) : 0;
@@ -840,6 +840,7 @@ extern "C" int wn_plan_describe(const wn_plan* p, char* buf, int32_t len) {
   const char* wg = "";
   switch (tp.wg) {
     case WG_LAYER_INNER: wg = "one workgroup per (conv, utterance, time range): the last conv + 1x1 of a block as for depth 1, inner convs through the kernel's INNER form (wn_wgrad_layer_kernel)"; break;
+    // (pinned byte for byte by the golden describe text: with the folded skip path's kind-7 jobs dW_r, db_r come from those)
     case WG_LAYER: wg = "one workgroup per (block, utterance, time range) for dW_d, db_d, dW_r, db_r (wn_wgrad_layer_kernel)"; break;
     case WG_TR_PAIRS:
       wg = tp.mfused ? "two jobs per block on transposed LDS reads: both taps of dW_d from one read of du; dW_r together with the "

@@ -75,6 +75,7 @@ struct TrainPaths {
   WgFamily wg = WG_GENERIC;
   BwdFamily bwd = BWD_BLOCKS;
   int mtr = 0;             // M = Z^T dL/da of the folded skip path as wn_wgrad_tr jobs over several blocks' z (kind 7 / 8), or 0
+                           // (kind 7: the jobs carry the blocks' dW_r, db_r too and the layer kernel runs without its 1x1 part)
   bool mfused = false;     // ... or riding in the dW_r jobs of WG_TR_PAIRS
   // the skip convs' own weight-gradient kernel | skip path folded into the head's first conv | deeper stacks train in split
   // precision (inner gradients carry max-abs slots) | some head layer has a staged pair kind
@@ -110,7 +111,7 @@ template <class T> struct DevTable {
 struct WgSpan {
   enum Op : uint8_t { INCONV, JOBS, PAIRS, TR, LAYERS, SKIP } op;
   enum Slab : uint8_t { BATCH, HEAD, MFOLD } slab;   // batched slab | the head's compact slab and time split | the slab of M
-  int kind;            // PAIRS / TR: the kernel's kind; JOBS: 1 = exact fp32; LAYERS: 1 = the inner table, INNER form
+  int kind;            // PAIRS / TR: the kernel's kind; JOBS: 1 = exact fp32; LAYERS: 1 = the inner table, INNER form; 2 = without the 1x1 part
   int first, count;    // entries of the op's table
 };
 

@@ -125,7 +125,10 @@ int ensure_schedule(const wn_plan* p, wn_exec& e, const WsLayout& L, int B, int 
     }
   }
   if (tp.mtr != 0) {
-    const int per = 256 / p->D;                               // blocks per job
+    // 64-channel blocks: dW_r, db_r of the job's blocks ride along (one read of z for both; the layer table then runs
+    // without its 1x1 part)
+    const bool zonce = tp.mtr == 7;
+    const int per = zonce ? 2 : 256 / p->D;                   // blocks per job
     for (int b0 = 0; b0 < p->N; b0 += per) {
       WnWgPair w;
       memset(&w, 0, sizeof(w));
@@ -137,6 +140,12 @@ int ensure_schedule(const wn_plan* p, wn_exec& e, const WsLayout& L, int B, int 
       w.b_off = b0 == 0 ? (int64_t)p->N * p->D * p->fold_F0 : -1;       // colsum(dL/da) once
       w.gmax_off = L.absmax + slot.gf(0);
       w.w2_off = w.b2_off = w.gmax2_off = -1;
+      for (int sg = 0; zonce && sg < 2; ++sg) {               // (a segment that does not exist repeats the first: never written)
+        const int b = b0 + (sg < w.nseg ? sg : 0);
+        const BlockInfo& bi = p->blocks[b];
+        w.seg[sg].g_off = L.GH[b + 1]; w.seg[sg].gmax_off = am_GH(b + 1);
+        w.seg[sg].w_off = p->tensors[bi.conv1.kernel_t].off; w.seg[sg].b_off = p->tensors[bi.conv1.bias_t].off;
+      }
       pairs[0].push_back(w);
     }
   }
@@ -188,7 +197,7 @@ int ensure_schedule(const wn_plan* p, wn_exec& e, const WsLayout& L, int B, int 
   // transposed-read kernels: both taps of dW_d in one job; dW_r (+ M)
   span(WgSpan::TR, WgSpan::BATCH, 1, pfirst[1], pairs[1].size());
   span(WgSpan::TR, WgSpan::BATCH, tp.mfused ? 6 : 2, pfirst[2], pairs[2].size());
-  span(WgSpan::LAYERS, WgSpan::BATCH, 0, 0, wgl.size());
+  span(WgSpan::LAYERS, WgSpan::BATCH, tp.mtr == 7 ? 2 : 0, 0, wgl.size());
   span(WgSpan::LAYERS, WgSpan::BATCH, 1, 0, wgli.size());
   // folded skip path: M = Z^T dL/da (N*D x F0) and colsum(dL/da) into their own slab; else dW_s, db_s of every block
   if (tp.mtr != 0) span(WgSpan::TR, WgSpan::MFOLD, tp.mtr, pfirst[0], pairs[0].size());
@@ -517,10 +526,11 @@ struct TrainCall {
                                       0, (int64_t)p->KS * p->R, st);
       case WgSpan::JOBS: return wn_launch_wgrad_batched(g.jobs.d + sp.first, sp.count, ws, out, pitch, B, T, splits, st, sp.kind != 0);
       case WgSpan::PAIRS: return wn_launch_wgrad_pairs(sp.kind, g.pairs.d + sp.first, sp.count, ws, out, pitch, B, T, splits, st);
-      case WgSpan::TR:        // (kind 6: M into its own slab beside dW_r)
+      case WgSpan::TR:        // (kind 6: M into its own slab beside dW_r; kind 7: dW_r into the batched slab beside M)
         return wn_launch_wgrad_tr(sp.kind, g.pairs.d + sp.first, sp.count, ws, out, pitch, B, T, splits, st,
-                                  sp.kind == 6 ? ws + L.mslab : nullptr, sp.kind == 6 ? pm : 0);
-      case WgSpan::LAYERS: return wn_launch_wgrad_layers(sp.kind ? g.inner.d : g.layers.d, sp.count, p->R, ws, out, pitch, B, T, splits, st, sp.kind);
+                                  sp.kind == 6 ? ws + L.mslab : (sp.kind == 7 ? ws + L.bslab : nullptr),
+                                  sp.kind == 6 ? pm : (sp.kind == 7 ? p->nparams : 0));
+      case WgSpan::LAYERS: return wn_launch_wgrad_layers(sp.kind == 1 ? g.inner.d : g.layers.d, sp.count, p->R, ws, out, pitch, B, T, splits, st, sp.kind);
       case WgSpan::SKIP:
         if (sp.slab == WgSpan::MFOLD)
           return wn_launch_wgrad_skip(ws + L.Z, p->Dp, ws + L.GF[0], p->fold_F0, rows, p->N * p->D, p->fold_F0, p->D, B * splits, out, pitch,

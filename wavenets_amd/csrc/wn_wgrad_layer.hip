@@ -19,13 +19,16 @@
 using namespace wn_split16;
 
 // C32 = R / 32 = D / 32 (1 or 2).  Channel order of a stage: x[t-d] (R) | x[t] (R) | du (2D) | z (D) | go (R);
-// INNER: x[t-d] (R) | x[t] (R) | du (R)
-template <int C32, bool INNER>
+// INNER: x[t-d] (R) | x[t] (R) | du (R).  NO1X1: x[t-d] (R) | x[t] (R) | du (2D) -- the gated conv alone, same dW_d tiles in
+// the same order: dW_r, db_r come from the job that reads z for the folded skip path's M (wn_wgrad_tr.hip, kind 7)
+template <int C32, bool INNER, bool NO1X1 = false>
 __global__ __launch_bounds__(256, 2) void wn_wgrad_layer_kernel(const WnWgLayer* layers, float* ws, float* slab,
                                                                 int64_t P, int B, int T, int spb) {
-  constexpr int R = 32 * C32, NCH = INNER ? 3 * R : 6 * R;
+  static_assert(!(INNER && NO1X1), "INNER has no 1x1 part already");
+  constexpr bool ONE = !INNER && !NO1X1;                // the 1x1 part (z | go units, accr, dbr) is here
+  constexpr int R = 32 * C32, NCH = INNER ? 3 * R : (NO1X1 ? 4 * R : 6 * R);
   constexpr int DUW = INNER ? R : 2 * R;                // channels (= row stride) of du
-  constexpr int NXU = INNER ? 2 * 2 * R : 2 * 4 * R;    // stride-R units of a workgroup: (x[t-d] | x[t] (| z | go)) x two halves
+  constexpr int NXU = ONE ? 2 * 4 * R : 2 * 2 * R;    // stride-R units of a workgroup: (x[t-d] | x[t] (| z | go)) x two halves
   constexpr int NU = 1 + (NXU + 255) / 256;             // one du unit + the stride-R units of a thread
   constexpr int PLANE = NCH * 32;                       // bytes of one fp16 plane of a stage
   constexpr int STAGE = 2 * PLANE;
@@ -132,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void wn_wgrad_layer_kernel(const WnWgLayer*
   const int xt = (C32 == 2) ? wave : (wave >> 1);       // x tile (tap-major: tap = xt / C32, k tile = xt % C32)
   const int j0 = (C32 == 2 || INNER) ? 0 : (wave & 1);  // first du tile
   const bool has_d = !INNER || C32 == 2 || (wave & 1) == 0;   // owns dW_d tiles (INNER, C32 = 1: two tiles for four waves)
-  const bool has_r = !INNER && ((C32 == 2) || wave == 0);     // owns a dW_r tile
+  const bool has_r = ONE && ((C32 == 2) || wave == 0);        // owns a dW_r tile
   const int zt = (C32 == 2) ? (wave >> 1) : 0, gt = (C32 == 2) ? (wave & 1) : 0;
   f32x16 acc[NJ], accr;
 #pragma unroll
@@ -214,19 +217,21 @@ __global__ __launch_bounds__(256, 2) void wn_wgrad_layer_kernel(const WnWgLayer*
   __syncthreads();
   for (int c = tid; c < NCH; c += 256) {
     if (c >= 2 * R && c < 2 * R + DUW) { if (Ld.dbd_off >= 0) row[Ld.dbd_off + (c - 2 * R)] = bpart[c] + bpart[NCH + c]; }
-    else if (!INNER && c >= 5 * R) row[Ld.dbr_off + (c - 5 * R)] = bpart[c] + bpart[NCH + c];
+    else if (ONE && c >= 5 * R) row[Ld.dbr_off + (c - 5 * R)] = bpart[c] + bpart[NCH + c];
   }
 }
 
 int wn_wgrad_layer_supported(int R, int D, int KS) { return R == D && (R == 32 || R == 64) && KS == 2; }
 
-// inner: every entry is a non-gated conv of a deeper stack (x_off, du_off = its output gradient [rows][R], dwd_off, dbd_off,
-// gmax_u_off, dilation; the 1x1 fields are ignored)
+// inner = 1: every entry is a non-gated conv of a deeper stack (x_off, du_off = its output gradient [rows][R], dwd_off,
+// dbd_off, gmax_u_off, dilation; the 1x1 fields are ignored); inner = 2: the gated conv of every entry, its 1x1 fields ignored
 int wn_launch_wgrad_layers(const WnWgLayer* d_layers, int nlayers, int R, float* ws, float* slab, int64_t P, int B,
                            int T, int splits_per_b, hipStream_t s, int inner) {
   if (nlayers <= 0) return WN_OK;
   const dim3 grid((unsigned)(B * splits_per_b), (unsigned)nlayers);
-  if (R == 64 && inner) hipLaunchKernelGGL((wn_wgrad_layer_kernel<2, true>), grid, dim3(256), 0, s, d_layers, ws, slab, P, B, T, splits_per_b);
+  if (R == 64 && inner == 2) hipLaunchKernelGGL((wn_wgrad_layer_kernel<2, false, true>), grid, dim3(256), 0, s, d_layers, ws, slab, P, B, T, splits_per_b);
+  else if (inner == 2) { wn_set_error("wgrad_layers: no form without the 1x1 part at width %d", R); return WN_E_UNSUPPORTED; }
+  else if (R == 64 && inner) hipLaunchKernelGGL((wn_wgrad_layer_kernel<2, true>), grid, dim3(256), 0, s, d_layers, ws, slab, P, B, T, splits_per_b);
   else if (R == 32 && inner) hipLaunchKernelGGL((wn_wgrad_layer_kernel<1, true>), grid, dim3(256), 0, s, d_layers, ws, slab, P, B, T, splits_per_b);
   else if (R == 64) hipLaunchKernelGGL((wn_wgrad_layer_kernel<2, false>), grid, dim3(256), 0, s, d_layers, ws, slab, P, B, T, splits_per_b);
   else if (R == 32) hipLaunchKernelGGL((wn_wgrad_layer_kernel<1, false>), grid, dim3(256), 0, s, d_layers, ws, slab, P, B, T, splits_per_b);

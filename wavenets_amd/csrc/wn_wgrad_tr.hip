@@ -49,24 +49,34 @@ __device__ __forceinline__ h8 wt_frag(const unsigned char* lanebase, int off) {
 // J.seg_stride floats apart, of which the first J.nseg exist (the rest reads as zero and its output rows are not written):
 // the gated activations z of several blocks (block-major Z) against ONE read of G -- the folded skip path's
 // M = Z^T dL/da (src/layers.py:216-217 and model.py:105-111 reversed) for 64- and 32-channel blocks.
-template <int KC, int NC, int TAPS, int LDX, int LDG, int LDW, int TKW, int TNW, bool G2 = false, int XSEG = 0>
+// GSEG (XSEG > 0, two segments): every segment has a second operand of its own, J.seg[s].g_off of XSEG channels (row stride
+// XSEG) with its own max-abs scale, staged between X and G: [dW_r(b) | M(b)] = z(b)^T [g_o(b) | dL/da] from one read of z.
+// The extra product is block-diagonal: a wave's row tile meets one 32-column tile of its own segment's g_o (one more
+// accumulator tile) and goes to (slab2, J.seg[s].w_off, J.seg[s].b_off) with row pitch XSEG; M goes to slab as without.
+template <int KC, int NC, int TAPS, int LDX, int LDG, int LDW, int TKW, int TNW, bool G2 = false, int XSEG = 0, bool GSEG = false>
 __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* jobs, float* ws, float* slab, int64_t P, int B,
                                                              int T, int spb, float* slab2, int64_t P2) {
-  constexpr int XC = TAPS * KC, NCH = XC + NC;                  // LDS channels: x taps | g
+  constexpr int XC = TAPS * KC, GC0 = XC + (GSEG ? KC : 0), NCH = GC0 + NC;   // LDS channels: x taps | (segments' g_o) | g
   constexpr int PITCH = NCH * 2 + 64;                           // bytes per time row of a plane (the pad spreads 4 rows over the banks)
   constexpr int PLANE = WT_ROWS * PITCH, STAGE = 2 * PLANE;
   constexpr int KT = XC / 32, NT = NC / 32;
   static_assert((KT / TKW) * (NT / TNW) == 8 && KT % TKW == 0 && NT % TNW == 0, "8 waves tile the output block");
   static_assert((PITCH / 4) % 64 == 16, "row pitch must rotate the banks by a quarter");
   static_assert(XSEG == 0 || (TAPS == 1 && !G2 && LDX == XSEG && KC % XSEG == 0 && XSEG % 32 == 0), "segmented X");
+  static_assert(!GSEG || (XSEG > 0 && KC == 2 * XSEG && TKW == 1 && NT / TNW == XSEG / 32), "one g_o tile per wave");
   constexpr int XPR = KC / 4, GPR = NC / 4;                     // 16-byte pieces per row
   constexpr int XRP = 512 / XPR, GRP = 512 / GPR;               // rows per pass of the 512 threads
   constexpr int XP = WT_ROWS / XRP, GP = WT_ROWS / GRP;         // passes per chunk
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
-  static_assert(2 * STAGE <= 160 * 1024 && GRP * NC * 4 <= 2 * STAGE, "LDS");
+  // GSEG: behind the two stages, the chunk's g_o rows once more as fp32 [row][KC] per stage: db_r is summed from them in the
+  // order of wn_wgrad_layer_kernel (8 consecutive rows, then the running sum of each half of a 16-row chunk, then the two
+  // halves), so that it is the per-block kernel's db_r bit for bit wherever the time ranges agree
+  constexpr int FBS = GSEG ? WT_ROWS * KC * 4 : 0;             // bytes of one stage's fp32 rows
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE + 2 * FBS];
+  static_assert(2 * STAGE + 2 * FBS <= 160 * 1024 && (GRP * NC + (GSEG ? 2 * KC : 0)) * 4 <= 2 * STAGE, "LDS");
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tl = lane & 31, h = lane >> 5;
   const WnWgPair J = jobs[blockIdx.y];
+  const WnWgPair::Seg* const segs = jobs[blockIdx.y].seg;
   const int split = blockIdx.x;
   const int ub = split / spb, sp = split % spb;
   int len = (T + spb - 1) / spb;
@@ -88,9 +98,18 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
   const bool upper = G2 && gc >= NC / 2;                 // this thread's g piece belongs to the second tensor
   const float* gbase = upper ? ws + J.g2_off + (int64_t)ub * T * LDG + (gc - NC / 2) : ws + J.g_off + (int64_t)ub * T * LDG + gc;
   const float gs_t = upper ? gsc2 : gsc;
-  struct Regs { f32x4 xs[TAPS][XP]; f32x4 gv[GP]; };     // one chunk in flight: x[t - shift] (| x[t]), g
+  // GSEG: this thread's piece of a segment's g_o sits at the channels of its x piece; scaled by that segment's max-abs
+  const int hseg = (GSEG && xvalid) ? xc / (XSEG > 0 ? XSEG : 1) : 0;
+  const float* hbase = GSEG ? ws + segs[hseg].g_off + (int64_t)ub * T * XSEG + xc % (XSEG > 0 ? XSEG : 1) : nullptr;
+  float hs_t = 1.0f;
+  if constexpr (GSEG) {
+    float unused;
+    if (segs[hseg].gmax_off >= 0) pow2_scale(ws[segs[hseg].gmax_off], hs_t, unused);
+  }
+  struct Regs { f32x4 xs[TAPS][XP]; f32x4 gv[GP]; f32x4 hv[GSEG ? XP : 1]; };   // one chunk in flight: x[t - shift] (| x[t]), g (, g_o)
   Regs ra, rb;
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};
+  float hsum = 0.f;                                      // GSEG, threads 0 .. 2 KC - 1: g_o channel tid % KC, half tid / KC of every 16-row chunk
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
   // Every request is UNCONDITIONAL (row index clamped into the utterance, rows outside the range zeroed when the chunk is
@@ -105,6 +124,7 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
       const int tc = min(t, T - 1);
       if (XSEG > 0) {
         xs[0][k] = ldg4(xbase + (int64_t)tc * LDX);
+        if constexpr (GSEG) q.hv[k] = ldg4(hbase + (int64_t)tc * XSEG);
       } else {
         xs[0][k] = ldg4(xbase + (int64_t)max(tc - d, 0) * LDX);
         if constexpr (TAPS == 2) xs[1][k] = ldg4(xbase + (int64_t)tc * LDX);
@@ -135,6 +155,14 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
         *reinterpret_cast<h4*>(row + (tp * KC + xc) * 2) = hi;
         *reinterpret_cast<h4*>(row + PLANE + (tp * KC + xc) * 2) = lo;
       }
+      if constexpr (GSEG) {
+        h4 hi, lo;
+        const f32x4 g4 = ((interior || t < r1) && xvalid) ? q.hv[k] : zero4;
+        split4s(g4, hs_t, hi, lo);
+        *reinterpret_cast<f32x4*>(smem + 2 * STAGE + stage * FBS + ((xr + XRP * k) * KC + xc) * 4) = g4;
+        *reinterpret_cast<h4*>(row + (XC + xc) * 2) = hi;
+        *reinterpret_cast<h4*>(row + PLANE + (XC + xc) * 2) = lo;
+      }
     }
 #pragma unroll
     for (int k = 0; k < GP; ++k) {
@@ -143,8 +171,8 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
       const f32x4 g4 = (interior || t0 + gr + GRP * k < r1) ? gv[k] : zero4;
       split4s(g4, gs_t, hi, lo);
       bsum[0] += g4.x; bsum[1] += g4.y; bsum[2] += g4.z; bsum[3] += g4.w;
-      *reinterpret_cast<h4*>(row + (XC + gc) * 2) = hi;
-      *reinterpret_cast<h4*>(row + PLANE + (XC + gc) * 2) = lo;
+      *reinterpret_cast<h4*>(row + (GC0 + gc) * 2) = hi;
+      *reinterpret_cast<h4*>(row + PLANE + (GC0 + gc) * 2) = lo;
     }
   };
 
@@ -158,10 +186,28 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
     for (int j = 0; j < TNW; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  // GSEG: row tile kt0 lies in segment wseg; this wave's tile of z^T g_o takes column tile wave / WKD of that segment's g_o
+  const int wseg = GSEG ? 32 * kt0 / (XSEG > 0 ? XSEG : 1) : 0;
+  const int ht = wave / WKD;
+  f32x16 accr;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) accr[r] = 0.f;
   // lane part of every transposed read: row 8 h + q, columns 16 g + 4 p (q = (lane & 15) >> 2, p = lane & 3, g = (lane >> 4) & 1)
   const int lb = (8 * h + ((lane & 15) >> 2)) * PITCH + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
   auto compute = [&](int stage) {
     const unsigned char* base = smem + stage * STAGE + lb;
+    if constexpr (GSEG) {
+      if (wave < 2 * KC / 64) {                            // (wave-uniform: a wave holds one half)
+        const float* fb = reinterpret_cast<const float*>(smem + 2 * STAGE + stage * FBS) + (8 * (tid / KC)) * KC + tid % KC;
+#pragma unroll
+        for (int c16 = 0; c16 < WT_ROWS / 16; ++c16) {
+          float s8 = 0.f;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s8 += fb[(16 * c16 + e) * KC];
+          hsum += s8;
+        }
+      }
+    }
     wn_static_for<2>([&](auto kc) {
       constexpr int ks = decltype(kc)::value;
       constexpr int ro = ks * 16 * PITCH;
@@ -173,12 +219,17 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
       }
 #pragma unroll
       for (int j = 0; j < TNW; ++j) {
-        const h8 bh = wt_frag<PITCH>(base, ro + (XC + 32 * (nt0 + j)) * 2);
-        const h8 bl = wt_frag<PITCH>(base, ro + PLANE + (XC + 32 * (nt0 + j)) * 2);
+        const h8 bh = wt_frag<PITCH>(base, ro + (GC0 + 32 * (nt0 + j)) * 2);
+        const h8 bl = wt_frag<PITCH>(base, ro + PLANE + (GC0 + 32 * (nt0 + j)) * 2);
 #pragma unroll
         for (int i = 0; i < TKW; ++i) {
           mfma3(ah[i], al[i], bh, bl, acc[i][j]);
         }
+      }
+      if constexpr (GSEG) {
+        const h8 bh = wt_frag<PITCH>(base, ro + (XC + XSEG * wseg + 32 * ht) * 2);
+        const h8 bl = wt_frag<PITCH>(base, ro + PLANE + (XC + XSEG * wseg + 32 * ht) * 2);
+        mfma3(ah[0], al[0], bh, bl, accr);
       }
     });
   };
@@ -235,6 +286,24 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_tr_kernel(const WnWgPair* job
       for (int r = 0; r < 16; ++r) tbase[wn_drow(r, h) * LDW] = acc[i][j][r] * iv;
     }
   }
+  if constexpr (GSEG) {
+    if (wseg < nseg) {                                     // dW_r of this wave's segment (wave-uniform)
+      float sc, iv = 1.0f;
+      if (segs[wseg].gmax_off >= 0) pow2_scale(ws[segs[wseg].gmax_off], sc, iv);
+      float* tbase = slab2 + (int64_t)split * P2 + segs[wseg].w_off + (int64_t)(32 * kt0 - XSEG * wseg) * XSEG + 32 * ht + tl;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tbase[wn_drow(r, h) * XSEG] = accr[r] * iv;
+    }
+    // db_r: the two halves' sums of the g_o rows as staged (their own region behind the other operand's partial sums)
+    float* hpart = reinterpret_cast<float*>(smem) + GRP * NC;
+    if (tid < 2 * KC) hpart[tid] = hsum;
+    __syncthreads();
+    for (int n = tid; n < KC; n += 512) {
+      const int sg = n / (XSEG > 0 ? XSEG : 1);
+      if (sg >= nseg || segs[sg].b_off < 0) continue;
+      slab2[(int64_t)split * P2 + segs[sg].b_off + n % (XSEG > 0 ? XSEG : 1)] = hpart[n] + hpart[KC + n];
+    }
+  }
   if (J.b_off >= 0 || (G2 && J.b2_off >= 0)) {           // bias sums: the row groups hold partial sums of every column
     float* bpart = reinterpret_cast<float*>(smem);        // (every wave is past its last LDS read: the loop ends with a barrier)
 #pragma unroll
@@ -275,8 +344,12 @@ int wn_launch_wgrad_tr(int kind, const WnWgPair* d_jobs, int njobs, float* ws, f
       if (!slab2) { wn_set_error("wgrad_tr: kind 6 needs the second slab"); return WN_E_INVALID; }
       WT_LAUNCH(128, 256, 1, 128, 128, 128, 1, 4, true);
       break;
-    // M = Z^T dL/da: the z of four 64-channel (kind 7) or eight 32-channel blocks (kind 8) against one read of dL/da
-    case 7: WT_LAUNCH(256, 128, 1, 64, 128, 128, 2, 2, false, 64); break;
+    // [dW_r(b) | M(b)] = z(b)^T [g_o(b) | dL/da] of two 64-channel blocks from one read of their z (kind 7: dW_r, db_r into
+    // the second slab); M = Z^T dL/da of eight 32-channel blocks against one read of dL/da (kind 8)
+    case 7:
+      if (!slab2) { wn_set_error("wgrad_tr: kind 7 needs the second slab"); return WN_E_INVALID; }
+      WT_LAUNCH(128, 128, 1, 64, 128, 128, 1, 2, false, 64, true);
+      break;
     case 8: WT_LAUNCH(256, 128, 1, 32, 128, 128, 2, 2, false, 32); break;
     default: wn_set_error("wgrad_tr: unknown kind %d", kind); return WN_E_UNSUPPORTED;
   }
