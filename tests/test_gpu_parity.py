@@ -1150,6 +1150,44 @@ def test_weight_gradient_schedule_follows_every_key_change(name):
   assert any(not torch.equal(a, b) for a, b in zip(first[(False, (2, 97))], first[(True, (2, 97))]))   # two math modes really ran
 
 
+@pytest.mark.parametrize('channels,finals', [(64, [128, 256]), (128, [128, 64])])
+def test_generation_paths_follow_every_key_change(channels, finals):
+  """The kernel paths of a queued generate call are decided per call (wnp::gen_paths) and the cached block table is keyed
+  by (B, 128-channel images): ONE model through B = 2 stochastic -> B = 9 (past the head tail's 8 utterances: a sampler
+  launch of its own) -> top_p (head launch without the tail) -> deterministic -> (128 channels: the one-workgroup chain
+  under knob 2, then the relay again) -> exact fp32 (per-block launches, no table) -> the first state again.  In every
+  state the queued samples are the sliding window's; every revisit gives the samples of the first visit, and the first
+  visit those of a fresh model built directly in that state.  Correctness against the oracle is the parity tests' job."""
+  import contextlib
+  from wavenets_amd import _lib
+  kw = dict(blocks=3, channels=channels, skip_channels=256, dilation_bound=4, final_layers_channels=finals,
+            activation='leaky_relu', bits=8)
+  _, _, model = make_pair(seed=19, bias_range=0.3, **kw)
+  ws = {B: O.synthetic_waveform(B, model.receptive_field, seed=40 + B).to(dev()) for B in (2, 9)}
+
+  def run(m, state, queued):
+    B, top_p, det, knob2, exact = state
+    _lib.lib().wn_debug_set(2, knob2)
+    with (m.exact_fp32() if exact else contextlib.nullcontext()):
+      return m.generate(6, sample=ws[B], use_queues=queued, deterministic=det, top_p=top_p).clone()
+  #          B  top_p  det    knob 2  exact fp32
+  states = [(2, 1.0, False, 0, False), (9, 1.0, False, 0, False), (2, 0.9, False, 0, False), (2, 1.0, True, 0, False)]
+  if channels == 128:
+    states += [(2, 1.0, False, 1, False), (2, 1.0, False, 0, False)]
+  states += [(2, 1.0, False, 0, True), (2, 1.0, False, 0, False)]
+  first = {}
+  try:
+    for state in states:
+      got = run(model, state, True)
+      assert torch.equal(got, run(model, state, False)), ('sliding window', state)
+      if state not in first:
+        first[state] = got
+        assert torch.equal(got, run(make_pair(seed=19, bias_range=0.3, **kw)[2], state, True)), ('fresh', state)
+      assert torch.equal(got, first[state]), ('revisit', state)
+  finally:
+    _lib.lib().wn_debug_set(2, 0)
+
+
 @pytest.mark.parametrize('B,T', [(1, 20), (3, 97)])
 def test_wide_blocks_gradients_ragged(B, T, math_mode):
   """128-channel blocks (BASELINE configs[3] width): the forward is two split-precision contractions with the

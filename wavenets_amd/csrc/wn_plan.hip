@@ -146,7 +146,7 @@ void exec_release(wn_exec* e) {
   if (e->ev_ffork) (void)hipEventDestroy(e->ev_ffork);
   if (e->ev_fjoin) (void)hipEventDestroy(e->ev_fjoin);
   if (e->side) (void)hipStreamDestroy(e->side);
-  if (e->d_gen) (void)hipFree(e->d_gen);
+  e->gen.release();
   if (g_bound_exec == e) g_bound_exec = nullptr;
   delete e;
 }
@@ -251,6 +251,72 @@ TrainPaths train_paths(const wn_plan* p, const wn_exec& e, const WsLayout& L, in
   // (the streamed R = 128 pair kernel indexes with 32-bit byte offsets: the two-launch chain takes over beyond)
   t.rows32 = rows * 2 * p->D * 4 < ((int64_t)1 << 32);
   return t;
+}
+
+// every layer of `finals` from `first` to `end` is one the split-precision rows GEMM of the generation head takes
+static bool gen_head_layers_ok(const wn_plan* p, size_t first, size_t end) {
+  for (size_t i = first; i < end; ++i) {
+    const ConvInfo& c = p->finals[i];
+    if (!(c.frag16 >= 0 && c.cout % 32 == 0 && c.cout >= 64 && c.cout <= 256 && c.cin % 16 == 0 && c.cin <= 256)) return false;
+  }
+  return true;
+}
+
+// Which kernels a queued generate call of `length` samples at B utterances takes under knobs 1 and 2 (the one decision:
+// the phases of GenCall read it)
+GenPaths gen_paths(const wn_plan* p, int B, int length, int cu_count, bool relay_area, bool deterministic, const WnSampleCtl& ctl) {
+  GenPaths g;
+  const bool split = wn_debug_get(1) != 1;
+  const int RF = wn_plan_receptive_field(p);
+  const size_t nf = p->finals.size();
+  // the chain kernels (input conv + every block in one launch) when the split-precision block kernel is the one the sliding
+  // window uses; otherwise the blocks run as separate launches (the chains index rings and rows with 32-bit arithmetic)
+  const bool fits32 = (int64_t)(RF + 1) * B * std::max(p->R, p->D) < (1LL << 31) && (int64_t)RF + length < (1LL << 31) &&
+                      (int64_t)p->N * B * p->D < (1LL << 31);
+  const bool chain64 = p->fused16_ok && p->LPB == 1 && split && fits32 && wn_gen_blocks_supported(p->R, p->D, p->KS) &&
+                       p->N <= wn_gen_chain_max_blocks();
+  // 128-channel blocks: every block of a step in one launch of wn_gen_chain128_kernel
+  const bool chain128 = !chain64 && p->LPB == 1 && p->Dp == p->D && wn_gen_block128_supported(p->R, p->D, p->KS) &&
+                        !p->blocks.empty() && p->blocks[0].f16nat >= 0 && p->blocks[0].conv1.frag16 >= 0 && split && fits32;
+  // ... as a relay over one workgroup per block (wn_gen_relay128_kernel) unless knob 2 asks for the single workgroup
+  // (only while every workgroup of a step can be resident at once -- one per CU: a workgroup waits for its predecessor
+  // inside the launch; with more workgroups than CUs the chain would still drain as long as they start in index order,
+  // which HIP does not promise)
+  const bool relay = chain128 && relay_area && wn_debug_get(2) == 0 && (int64_t)((B + 31) / 32) * p->N <= cu_count;
+  g.chain = chain64 ? GEN_CHAIN64 : relay ? GEN_RELAY128 : chain128 ? GEN_CHAIN128 : GEN_BLOCKS;
+  g.inconv_in_chain = chain64 || (chain128 && p->KS == 2);
+  // the folded form (skip sum and the head's first conv as one contraction, as in forward_core): half the columns
+  g.fold = fold_ok(p);
+  g.skipw = g.fold ? p->fold_F0 : p->Sh;
+  g.skip_img = g.fold ? p->frag16_foldF : p->frag16_skipF;
+  g.first_final = g.fold ? 1 : 0;
+  g.hc0 = (g.fold && p->c.use_skip) ? g.skipw : p->Hin;
+  // (the 128-channel chains carry the folded contraction only -- 128 columns)
+  const bool skip_in_chain = (chain64 && p->c.use_skip && g.skip_img >= 0 && wn_gen_skip_fusable(g.skipw)) ||
+                             (chain128 && g.fold && p->c.use_skip && g.skipw == 128 && g.skip_img >= 0);
+  g.skip = skip_in_chain ? GEN_SKIP_IN_CHAIN : p->c.use_skip ? GEN_SKIP_LAUNCH : GEN_SKIP_NONE;
+  // the whole head in one launch when every layer is one the split-precision rows GEMM would take
+  const size_t ff = (size_t)g.first_final;
+  const bool hc_ok = g.hc0 % 16 == 0 && g.hc0 <= 256;
+  const bool head_fused = chain64 && nf > ff && (int)(nf - ff) <= WN_GEN_HEAD_MAX && hc_ok && gen_head_layers_ok(p, ff, nf);
+  // mixture heads: the same launch with the exact-fp32 last layer (3 x mixtures columns: no split-precision image) and the
+  // mixture sampler behind the split-precision layers -- one launch instead of layers + 1 + sampler
+  bool head_mix = !head_fused && split && p->c.head != WN_HEAD_CATEGORICAL && p->c.num_mixtures > 0 && nf >= ff + 2 &&
+                  (int)(nf - ff - 1) <= WN_GEN_HEAD_MAX && hc_ok && fits32 && gen_head_layers_ok(p, ff, nf - 1);
+  if (head_mix) {
+    const ConvInfo& cl = p->finals.back();
+    head_mix = cl.cout == 3 * p->c.num_mixtures && cl.cout <= 32 && cl.cin % 64 == 0 && cl.cin <= 256 && cl.fragF >= 0;
+  }
+  g.head = head_fused ? GEN_HEAD_FUSED : head_mix ? GEN_HEAD_MIX : GEN_HEAD_LAYERS;
+  g.pre_in_head = head_fused;
+  // (up to 8 utterances = one row per wave of the head workgroup: with more, the rows of a wave run one after the other
+  // and the tail kernel's one wave per row finishes sooner -- measured 0.074 vs 0.068 ms per step at B = 32)
+  // (a stochastic step under top_p takes the sampler launch as well: the head kernel is built without the nucleus search)
+  const bool cat = p->c.head == WN_HEAD_CATEGORICAL;
+  g.head_tail = head_fused && cat && p->Cout <= 256 && B <= 8 && (deterministic || !(ctl.top_p > 0.f));
+  g.sampler = (g.head_tail || head_mix) ? GEN_SAMPLE_IN_HEAD : deterministic ? GEN_SAMPLE_DET
+              : (!cat || wn_sample_from_logits_supported(p->Cout)) ? GEN_SAMPLE_RAND : GEN_SAMPLE_ROWS;
+  return g;
 }
 
 WsLayout make_layout(const wn_plan* p, int B, int T, bool training) {

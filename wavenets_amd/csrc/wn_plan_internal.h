@@ -93,6 +93,39 @@ struct TrainPaths {
   }
 };
 
+// Which kernels a queued generate call takes: decided once per call (gen_paths, wn_plan.hip), read by the phases of
+// GenCall (wn_generate.hip).
+// blocks of a step: one launch each | wn_gen_chain kernels (32 / 64 channels, input conv included) | 128 channels in one
+// workgroup per utterance tile (wn_gen_chain128_kernel) | ... as a relay over one workgroup per block (wn_gen_relay128_kernel)
+enum GenChain { GEN_BLOCKS, GEN_CHAIN64, GEN_CHAIN128, GEN_RELAY128 };
+enum GenSkip { GEN_SKIP_NONE, GEN_SKIP_IN_CHAIN, GEN_SKIP_LAUNCH };   // no skip connections | in the chain launch | a contraction of its own
+// one contraction per layer | every layer in one launch (wn_gen_head_kernel) | ... with the exact-fp32 last layer and the
+// mixture sampler behind the split-precision layers
+enum GenHead { GEN_HEAD_LAYERS, GEN_HEAD_FUSED, GEN_HEAD_MIX };
+// the head launch samples and emits | arg max + emit | Philox draw + emit | softmax, sampler and emit as three launches
+enum GenSampler { GEN_SAMPLE_IN_HEAD, GEN_SAMPLE_DET, GEN_SAMPLE_RAND, GEN_SAMPLE_ROWS };
+struct GenPaths {
+  GenChain chain = GEN_BLOCKS;
+  bool inconv_in_chain = false;   // the input causal conv rides in the chain launch
+  // the skip contraction: folded with the head's first conv (half the columns, as in forward_core) or the reference's skip
+  // sum; its width, its split-precision image (or < 0), the first head layer behind it and that layer's input width
+  GenSkip skip = GEN_SKIP_NONE;
+  bool fold = false;
+  int skipw = 0, first_final = 0, hc0 = 0;
+  int64_t skip_img = -1;
+  GenHead head = GEN_HEAD_LAYERS;
+  bool pre_in_head = false;       // the pre kernel's work of step tau + 1 rides in the head launch of step tau
+  bool head_tail = false;         // categorical heads: the sampling tail and the emit ride in the head launch too
+  GenSampler sampler = GEN_SAMPLE_DET;
+  bool chain128() const { return chain == GEN_CHAIN128 || chain == GEN_RELAY128; }
+  bool table() const { return chain != GEN_BLOCKS; }   // the chain reads the device block table (GenTable)
+  bool operator==(const GenPaths& o) const {
+    return chain == o.chain && inconv_in_chain == o.inconv_in_chain && skip == o.skip && fold == o.fold && skipw == o.skipw &&
+           first_final == o.first_final && hc0 == o.hc0 && skip_img == o.skip_img && head == o.head &&
+           pre_in_head == o.pre_in_head && head_tail == o.head_tail && sampler == o.sampler;
+  }
+};
+
 // owning device copy of a host table
 template <class T> struct DevTable {
   T* d = nullptr;
@@ -133,12 +166,25 @@ struct WgSchedule {
   void release() { valid = false; jobs.release(); layers.release(); inner.release(); pairs.release(); cov.release(); }
 };
 
+// The per-block offsets the generation chains read, for one batch size (ensure_gen_table, wn_generate.hip).  Valid for its
+// key (B, chain128) only; `valid` is false from before the upload of a rebuild until it has succeeded.
+struct GenTable {
+  bool valid = false;
+  int B = 0;
+  bool chain128 = false;      // the table carries the 128-channel chain's images (BlockInfo::f16nat)
+  DevTable<WnGenBlock> blocks;
+  WnGenBlock blk0[3]{};       // entries 0..2 by value (the chain's first fetches do not wait for the table)
+  int64_t bias_stride = 0;    // conv1 biases at a uniform stride (the chain fetches them without the table), or 0
+  void release() { valid = false; blocks.release(); }
+};
+
 }  // namespace wnp
 
 // The mutable side of a plan: per-caller state of the orchestration ("a wn_plan is immutable and shareable
 // across streams").  One per stream of execution: dropout counter, the armed step sample, phase selection, the cached
-// weight-gradient job tables and generation block table of the last (B, T) it ran (device memory it owns), its side
-// stream and events, its profiling events.  A caller that drives one plan from several host threads / streams creates
+// weight-gradient schedule of the last (B, T) it trained and the generation block table of the last batch size it
+// generated (device memory they own, freed by exec_release), its side stream and events, its profiling events.  A
+// caller that drives one plan from several host threads / streams creates
 // one wn_exec per thread (wn_exec_create) and binds it there (wn_exec_bind: thread-local); unbound callers share the
 // plan's own.
 struct wn_exec {
@@ -148,16 +194,12 @@ struct wn_exec {
   // armed by wn_plan_arm_step_sample: the next training step also draws sample_waveform(pred)
   float* step_sample = nullptr; int step_sample_det = 0; uint64_t step_sample_seed = 0, step_sample_off = 0;
   wnp::WgSchedule wg;           // the cached weight-gradient schedule of the last (B, T) layout it trained
-  // side stream: the low-occupancy generic weight-gradient jobs overlap the per-block / skip kernels
+  wnp::GenTable gen;            // the cached block table of the generation chains, for the last batch size it generated
+  // side stream: the side spans of the weight-gradient schedule run beside the per-block / skip kernels
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   hipEvent_t ev_ffork = nullptr, ev_fjoin = nullptr;   // forward pass: the fold's weight preparation beside the block chain
-  WnGenBlock* d_gen = nullptr;  // fused generation step: per-block offsets for one batch size
-  WnGenBlock gen_blk0[3]{};
-  int64_t gen_bias_stride = 0;
   int train_phases = 3;   // wn_plan_set_train_phases: bit 0 forward + loss (+ step sample), bit 1 backward + weight gradients
-  int gen_B = 0;
-  bool gen_chain128 = false;   // the cached generation table carries the 128-channel chain's images
   // optional HIP-event timing of the fused block-forward launches (bench.py roofline leg)
   std::vector<hipEvent_t> prof_ev;   // pairs (start, stop)
   std::vector<int> prof_cnt;         // launches between the events of pair i
@@ -407,6 +449,8 @@ bool fold_ok(const wn_plan* p);
 bool head_pairs_ok(const wn_plan* p);
 TrainPaths train_paths(const wn_plan* p);   // the plan-level part; the per-call part as of a call without dropout or splits
 TrainPaths train_paths(const wn_plan* p, const wn_exec& e, const WsLayout& L, int64_t rows);
+// (cu_count: the device's compute units; relay_area: the generation workspace carries the relay's granule areas)
+GenPaths gen_paths(const wn_plan* p, int B, int length, int cu_count, bool relay_area, bool deterministic, const WnSampleCtl& ctl);
 int64_t slab_need(int B, int T, int K, int N);
 // ---- wn_block.hip ----
 int wgrad(const float* x, int ldx, int K, int shift, const float* g, int ldg, int N, int B, int T,
