@@ -281,7 +281,32 @@ typedef struct wn_sampling { float temperature; int32_t top_k; uint64_t seed; fl
 int wn_generate_sampled(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                         int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling, float* out,
                         float* workspace, int64_t ws_floats, void* stream);
+/* One piece of a sequence: the samples first .. first + length - 1, out (B, length).  wn_generate_sampled is its
+ * (window, first = 0) case.  The pieces of a sequence, concatenated, are bit for bit the one call of the total length
+ * with the same arguments: the Philox counter, the relay's epoch, the window parity and tau follow the index in the
+ * sequence, only the output column is step - first.
+ *   window != NULL begins a sequence and requires first == 0: window copy, priming pass (queued), then the steps.
+ *   window == NULL goes on at first >= 1, on a workspace in which the samples 0 .. first - 1 were made by earlier calls
+ *     with the same p, params, B, queued and seed.  It runs no priming pass and no weight preparation: the weight images
+ *     and the condition biases of the priming pass are in the workspace (queued: cond may be NULL; the sliding window
+ *     maps the condition in every step and needs it).  Between two calls the caller may copy the floats of
+ *     wn_generate_state_range away and back; nothing else in the workspace changes from step to step.
+ *   The range guard and the relay's give-up word (wn_generate_guard_slot) are cleared at the start of every call and
+ *     speak of that call's steps.  A continuation in exact-fp32 mode (wn_debug_set(1, 1)) reads only what a
+ *     split-precision priming pass left as well; the reverse does not hold (an exact-fp32 priming pass prepares no folded
+ *     skip images and clears no relay area): a sequence begun in exact-fp32 mode stays there.
+ *   On the 64-channel chain the head launch of a step carries the next step's pre work only when that step belongs to
+ *     the same call; the first step of a continuation does its own (the launch step 1 takes): the same arithmetic.
+ * WN_E_INVALID, before the device is touched: first < 0; window with first != 0; window == NULL with first == 0;
+ * first + length > 2^31 - 1 (steps are 32-bit in the launch arguments). */
+int wn_generate_chunk(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                      int64_t first, int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
+                      float* out, float* workspace, int64_t ws_floats, void* stream);
 int64_t wn_generate_workspace_floats(const wn_plan* p, int32_t B, int32_t queued);
+/* The one contiguous part of the generation workspace that steps write and a continuation reads, as a float offset and a
+ * float count.  queued: from the raw-sample slots to the end of the layout (rings, inner rings, per-step rows, partial
+ * accumulators, the relay's granule area, the head rows); sliding window: the two window buffers. */
+int wn_generate_state_range(const wn_plan* p, int32_t B, int32_t queued, int64_t* offset, int64_t* floats);
 /* float offset, inside the caller's generation workspace, of the call's range-guard slot.  After wn_generate (stream
  * synchronised) the float is >= wn_range_limit() if and only if some split-precision kernel of the call was fed an
  * |activation| at or beyond that limit: the priming pass (residual stream, skip sum, head activations), and in EVERY

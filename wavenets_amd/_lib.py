@@ -111,6 +111,9 @@ _SIGS = {
                               _P, C.c_int64, _P]),
     'wn_generate_sampled': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(WnSampling), _P,
                                       _P, C.c_int64, _P]),
+    'wn_generate_chunk': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(WnSampling), _P, _P, C.c_int64, _P]),
+    'wn_generate_state_range': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'wn_generate_workspace_floats': (C.c_int64, [_P, C.c_int32, C.c_int32]),
     'wn_generate_guard_slot': (C.c_int64, [_P, C.c_int32, C.c_int32]),
     'wn_layer_saved_floats': (C.c_int64, [C.POINTER(WnLayerDesc), C.c_int32, C.c_int32]),

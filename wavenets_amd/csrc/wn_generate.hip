@@ -149,12 +149,16 @@ int ensure_gen_table(const wn_plan* p, wn_exec& e, const GenLayout& G, const WsL
 }
 
 // ------------------------------------------------------------------------------------------
-// One call of wn_generate_sampled: the caller's buffers, the generation layout of B, the priming layout, the rings and
-// the kernel paths of the call; its phases are the member functions, in launch order.
+// One call of wn_generate_chunk: the caller's buffers, the generation layout of B, the priming layout, the rings and
+// the kernel paths of the call; its phases are the member functions, in launch order.  A call makes the samples
+// first .. first + length - 1 of a sequence; every `step` below is the index in the sequence, and everything between two
+// steps lives in the workspace (xin, the rings, the relay's granule area; the weight images and cb of the priming pass),
+// so a call with first > 0 goes on where the call before it stopped.
 // ------------------------------------------------------------------------------------------
 struct GenCall {
   wn_exec& e;                        // the calling thread's execution state for p
   wn_plan* p; const float* params; const float* cond; int B, length; bool deterministic;
+  int first, end, step0;             // the call's steps are [first, end); step0: the first one that is not the priming pass
   uint64_t seed; WnSampleCtl ctl;    // the sampling controls
   float* out; float* ws; hipStream_t s;
   int RF;
@@ -173,9 +177,10 @@ struct GenCall {
   // arguments that do not change from step to step (build_*)
   WnGenStepArgs ga; WnGen128Args ca; WnGenHeadArgs ha;
 
-  void bind(wn_plan* p_, const float* params_, const float* cond_, int B_, int length_, bool det, uint64_t seed_,
+  void bind(wn_plan* p_, const float* params_, const float* cond_, int B_, int first_, int length_, bool det, uint64_t seed_,
             const WnSampleCtl& ctl_, float* out_, float* workspace, hipStream_t s_, GenLayout&& G_) {
     p = p_; params = params_; cond = cond_; B = B_; length = length_; deterministic = det; seed = seed_; ctl = ctl_;
+    first = first_; end = first_ + length_; step0 = std::max(first_, 1);
     out = out_; ws = workspace; s = s_;
     RF = wn_plan_receptive_field(p);
     G = std::move(G_);
@@ -195,13 +200,13 @@ struct GenCall {
   }
 
   int64_t tau(int step) const { return (int64_t)RF + step - 1; }   // time of the newest known sample at `step`
-  // where sample `step` goes: output column `step`, and the slot of the raw sample ring it enters the network from (it is
-  // x[RF + step], the input at time tau(step) + 1)
-  WnEmit emit(int step) const { return WnEmit{out, length, step, R.xin + (int64_t)((tau(step) + 1) % p->KS) * B}; }
+  // where sample `step` goes: output column `step - first`, and the slot of the raw sample ring it enters the network
+  // from (it is x[RF + step], the input at time tau(step) + 1)
+  WnEmit emit(int step) const { return WnEmit{out, length, step - first, R.xin + (int64_t)((tau(step) + 1) % p->KS) * B}; }
 
-  // the window into the workspace, the guard (and the relay's give-up word behind it) cleared
+  // the window into the workspace (a continuation has none), the guard (and the relay's give-up word behind it) cleared
   int begin(const float* window) {
-    WN_HIP_CHECK(hipMemcpyAsync(win[0], window, (int64_t)B * RF * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (window) WN_HIP_CHECK(hipMemcpyAsync(win[0], window, (int64_t)B * RF * sizeof(float), hipMemcpyDeviceToDevice, s));
     WN_HIP_CHECK(hipMemsetAsync(gguard, 0, 2 * sizeof(float), s));
     return WN_OK;
   }
@@ -218,13 +223,13 @@ struct GenCall {
 
   // ---- naive sliding window: one full forward over the window per sample (src/model.py:296-305) ----
   int sliding_window() {
-    for (int step = 0; step < length; ++step) {
+    for (int step = first; step < end; ++step) {
       int rc = window_forward(win[step & 1], step == 0, nullptr);
       if (rc) return rc;
       rc = sample_rows(p, last, B, deterministic, seed, (uint64_t)step, lastp, samp, s, ctl);
       if (rc) return rc;
       hipLaunchKernelGGL(wn_gen_shift_kernel, dim3((B * RF + 255) / 256), dim3(256), 0, s, win[step & 1], samp, B, RF,
-                         win[(step + 1) & 1], out, length, step);
+                         win[(step + 1) & 1], out, length, step - first);
       WN_HIP_CHECK(hipGetLastError());
     }
     return WN_OK;
@@ -325,7 +330,8 @@ struct GenCall {
     const int64_t tau = this->tau(step);
     if (gp.chain == GEN_CHAIN64) {
       ga.tau = tau;
-      return wn_launch_gen_blocks(ga, p->R, p->KS, (gp.pre_in_head && step > 1) ? 2 : 3, s);
+      // (the pre work of the call's first step rode in no head launch: that step does its own)
+      return wn_launch_gen_blocks(ga, p->R, p->KS, (gp.pre_in_head && step > step0) ? 2 : 3, s);
     }
     int rc;
     // input causal conv on [x[tau-(KS-1)], ..., x[tau]]  ->  block 0's ring slot tau  (128-channel chain: inside its launch)
@@ -401,7 +407,7 @@ struct GenCall {
   int head(int step) {
     if (gp.head != GEN_HEAD_LAYERS) {
       if (ha.tail) { ha.offset = (uint64_t)step; ha.em = emit(step); }
-      if (gp.pre_in_head && step + 1 < length) {
+      if (gp.pre_in_head && step + 1 < end) {
         ga.tau = tau(step) + 1;
         return wn_launch_gen_head_pre(ha, ga, p->R, p->KS, s);
       }
@@ -437,7 +443,7 @@ struct GenCall {
     }
     const int rc = sample_rows(p, last, B, false, seed, (uint64_t)step, lastp, samp, s, ctl);
     if (rc) return rc;
-    hipLaunchKernelGGL(wn_gen_emit_kernel, dim3((B + 255) / 256), dim3(256), 0, s, samp, B, out, length, step, emit(step).xin_slot);
+    hipLaunchKernelGGL(wn_gen_emit_kernel, dim3((B + 255) / 256), dim3(256), 0, s, samp, B, out, length, step - first, emit(step).xin_slot);
     WN_HIP_CHECK(hipGetLastError());
     return WN_OK;
   }
@@ -500,36 +506,75 @@ extern "C" int wn_generate(wn_plan* p, const float* params, const float* window,
   return wn_generate_sampled(p, params, window, cond, B, length, deterministic, queued, &sp, out, workspace, ws_floats, stream);
 }
 
-extern "C" int wn_generate_sampled(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
-                                   int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
-                                   float* out, float* workspace, int64_t ws_floats, void* stream) {
+// wn_generate_sampled (window given, first = 0) and wn_generate_chunk
+static int generate_call(bool chunk, wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                         int64_t first, int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
+                         float* out, float* workspace, int64_t ws_floats, void* stream) {
   WnSampleCtl ctl = WN_SAMPLE_CTL_OFF;
   {
     const int rc = wn_sampling_check("generate", sampling, p ? p->c.head : WN_HEAD_CATEGORICAL, p ? p->Cout : 0x7fffffff, &ctl);
     if (rc) return rc;
   }
-  if (!p || !params || !window || !out || !workspace || B < 1 || length < 0) { wn_set_error("generate: bad arguments"); return WN_E_INVALID; }
+  if (chunk) {
+    if (first < 0) { wn_set_error("generate: first must be >= 0 (got %lld)", (long long)first); return WN_E_INVALID; }
+    if (window && first != 0) {
+      wn_set_error("generate: window begins a sequence and requires first == 0 (got first = %lld)", (long long)first);
+      return WN_E_INVALID;
+    }
+    if (!window && first == 0) { wn_set_error("generate: window is null with first == 0 (a sequence begins from a window)"); return WN_E_INVALID; }
+    // (steps are 32-bit in the launch arguments: the output column, the time tau = RF + step - 1 of the chains)
+    if (length > 0 && first + length > 0x7fffffffLL) {
+      wn_set_error("generate: first + length must not exceed 2147483647 (got first = %lld, length = %d)", (long long)first, (int)length);
+      return WN_E_INVALID;
+    }
+  }
+  if (!p || !params || (!window && first == 0) || !out || !workspace || B < 1 || length < 0) { wn_set_error("generate: bad arguments"); return WN_E_INVALID; }
   GenLayout G = gen_layout(p, B, queued != 0);
   if (ws_floats < G.total) { wn_set_error("generate: workspace too small"); return WN_E_INVALID; }
   if (length == 0) return WN_OK;
   GenCall c{wnp::ex(p)};
-  c.bind(p, params, cond, B, length, deterministic != 0, sampling->seed, ctl, out, workspace, (hipStream_t)stream, std::move(G));
+  c.bind(p, params, cond, B, (int)first, length, deterministic != 0, sampling->seed, ctl, out, workspace, (hipStream_t)stream, std::move(G));
   int rc = c.begin(window);
   if (rc) return rc;
   if (!queued) return c.sliding_window();
-  c.gp = gen_paths(p, B, length, device_cu_count(), c.G.relay >= 0, c.deterministic, ctl);
-  rc = c.prime();
-  if (rc) return rc;
+  c.gp = gen_paths(p, B, c.end, device_cu_count(), c.G.relay >= 0, c.deterministic, ctl);
+  if (window) {
+    rc = c.prime();
+    if (rc) return rc;
+  }
+  // (in every call that reads it: a call at another B may have rebuilt the table in between)
   if (c.gp.table()) {
     rc = ensure_gen_table(p, c.e, c.G, c.L, B, c.gp.chain128());
     if (rc) return rc;
   }
   c.build_args();
-  for (int step = 1; step < length; ++step) {
+  for (int step = c.step0; step < c.end; ++step) {
     if ((rc = c.blocks(step)) != WN_OK) return rc;
     if ((rc = c.skip(step)) != WN_OK) return rc;
     if ((rc = c.head(step)) != WN_OK) return rc;
     if ((rc = c.sample(step)) != WN_OK) return rc;
   }
+  return WN_OK;
+}
+
+extern "C" int wn_generate_sampled(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                                   int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
+                                   float* out, float* workspace, int64_t ws_floats, void* stream) {
+  return generate_call(false, p, params, window, cond, B, 0, length, deterministic, queued, sampling, out, workspace, ws_floats, stream);
+}
+
+extern "C" int wn_generate_chunk(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                                 int64_t first, int32_t length, int32_t deterministic, int32_t queued,
+                                 const wn_sampling* sampling, float* out, float* workspace, int64_t ws_floats, void* stream) {
+  return generate_call(true, p, params, window, cond, B, first, length, deterministic, queued, sampling, out, workspace, ws_floats, stream);
+}
+
+extern "C" int wn_generate_state_range(const wn_plan* p, int32_t B, int32_t queued, int64_t* offset, int64_t* floats) {
+  if (!p || B < 1 || !offset || !floats) { wn_set_error("generate_state_range: bad arguments"); return WN_E_INVALID; }
+  const GenLayout G = gen_layout(p, B, queued != 0);
+  // queued: xin, the rings, the inner rings, the per-step rows, u0, the relay's granule area and the head rows -- everything
+  // behind the guard; sliding window: the two window buffers
+  *offset = queued ? G.xin : G.win0;
+  *floats = queued ? G.total - G.xin : G.win1 + (int64_t)B * wn_plan_receptive_field(p) - G.win0;
   return WN_OK;
 }

@@ -168,6 +168,86 @@ class _NetFn(torch.autograd.Function):
     return g_x, g_c, (model.flat_grads.clone() if need_p else None), None, None, None, None
 
 
+_RELAY_GAVE_UP = ('wn_generate: a workgroup of the generation relay gave up waiting for its predecessor '
+                  '(code {}); the samples of this {} are invalid')
+
+
+class GenerationSession:
+  """One sequence of WaveNet.generation_session(...), continued chunk by chunk (wn_generate_chunk).
+
+  position: samples emitted so far.  exact: the session runs under exact_fp32() from here on (a chunk left the range
+  of the split-precision kernels, or the sequence was begun in exact-fp32 mode, whose priming pass does not prepare
+  what a split-precision step reads).  Otherwise a chunk runs in the math mode of the calling context."""
+
+  def __init__(self, model, sampling, condition, window, batch_size, use_queues, deterministic):
+    L = _lib.lib()
+    self._model, self._sampling, self._cond, self._window = model, sampling, condition, window
+    self._B, self._queued, self._det = int(batch_size), int(bool(use_queues)), int(bool(deterministic))
+    # its own workspace (never model._workspace('gen')): other sessions and one-shot generate calls leave it alone
+    self._ws = torch.zeros(int(L.wn_generate_workspace_floats(model._plan, self._B, self._queued)), dtype=torch.float32,
+                           device=model._device)
+    off, n = C.c_int64(), C.c_int64()
+    _lib.check(L.wn_generate_state_range(model._plan, self._B, self._queued, C.byref(off), C.byref(n)))
+    # what steps write and a continuation reads, and where a chunk's range-guard trip restores it from
+    self._state = self._ws[off.value:off.value + n.value]
+    self._shadow = torch.empty_like(self._state)
+    self._slot = int(L.wn_generate_guard_slot(model._plan, self._B, self._queued))
+    self._weights = (model.flat_params.data_ptr(), model._train_gen)
+    self._failed = False
+    self.position = 0
+    self.exact = False
+
+  def generate(self, n):
+    """The next (B, n, 1) samples, n >= 1.  A chunk that raises leaves position where it was."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+      raise ValueError(f'n must be an int >= 1 (got {n!r})')
+    m, L, first = self._model, _lib.lib(), self.position
+    if self._failed:
+      raise RuntimeError('generation session: an earlier chunk failed; its state is invalid')
+    if (m.flat_params.data_ptr(), m._train_gen) != self._weights:
+      raise RuntimeError('generation session: the weights changed since the session was created (optimizer step, '
+                         'set_weights, finalize_variable_values, or an averaged_weights() boundary); start a new session')
+    n = int(n)
+    out = torch.empty(self._B, n, 1, dtype=torch.float32, device=m._device)
+
+    def run():
+      _lib.check(L.wn_generate_chunk(m._plan, _lib.ptr(m.flat_params), _lib.ptr(self._window) if first == 0 else None,
+                                     _lib.ptr(self._cond), self._B, first, n, self._det, self._queued,
+                                     C.byref(self._sampling), _lib.ptr(out), _lib.ptr(self._ws), self._ws.numel(),
+                                     _lib.stream_ptr()))
+    if self.exact or L.wn_debug_value(1) == 1:
+      # exact fp32 cannot trip: no shadow copy, no host read
+      with m.exact_fp32():
+        run()
+      if first == 0:
+        self.exact = True
+    else:
+      if first > 0:
+        self._shadow.copy_(self._state)              # device to device, on the call's stream
+      run()
+      guard, watchdog = self._ws[self._slot:self._slot + 2].cpu()
+      if int(watchdog.view(torch.int32)) != 0:
+        self._failed = True
+        raise RuntimeError(_RELAY_GAVE_UP.format(int(watchdog.view(torch.int32)), 'chunk'))
+      if not (float(guard) < L.wn_range_limit()):
+        # the tripped run has overwritten the raw-sample slots and ring slots of its steps: back to the state in front
+        # of the chunk, the chunk again and everything after it on the exact-fp32 kernels (same seed: same draws); the
+        # samples already handed out stand
+        if first > 0:
+          self._state.copy_(self._shadow)
+        with m.exact_fp32():
+          run()
+        m.generation_guard_trips += 1
+        self.exact = True
+    self.position = first + n
+    return out
+
+  def reset(self):
+    """Back to the start: the next chunk begins the sequence again from the window, on the same workspace."""
+    self.position = 0
+    self._failed = False
+
+
 class WaveNet(torch.nn.Module):
   """WaveNet model class (src/model.py:11-556)."""
   _TAIL_METRICS = 5      # device-reduced metric slots behind {loss, reg_loss, range_flag} in the gradient bucket
@@ -897,6 +977,33 @@ class WaveNet(torch.nn.Module):
     reproduced).  Returns (B, length, 1).
     temperature / top_k / seed / top_p (additions) as in sample_waveform; an int seed is the Philox key of
     the draws and seeds the initial noise window when `sample` is None.  seed=None is seed=0x0402."""
+    sampling, condition, sample, batch_size = self._generation_args(batch_size, condition, sample, deterministic,
+                                                                    temperature, top_k, seed, top_p)
+    L = _lib.lib()
+    ws = self._workspace('gen', L.wn_generate_workspace_floats(self._plan, batch_size, int(bool(use_queues))))
+    out = torch.empty(batch_size, int(length), 1, dtype=torch.float32, device=self._device)
+    def run():
+      _lib.check(L.wn_generate_sampled(self._plan, _lib.ptr(self.flat_params), _lib.ptr(sample), _lib.ptr(condition),
+                                       batch_size, int(length), int(bool(deterministic)), int(bool(use_queues)),
+                                       C.byref(sampling), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    run()
+    # range guard (one host read; the caller reads the samples anyway): an activation beyond the fp16 range of the
+    # split-precision kernels -> the whole call again on the exact-fp32 kernels (same seed: same draws)
+    if length > 0 and L.wn_debug_value(1) != 1:
+      slot = L.wn_generate_guard_slot(self._plan, batch_size, int(bool(use_queues)))
+      guard, watchdog = ws[slot:slot + 2].cpu()
+      if int(watchdog.view(torch.int32)) != 0:
+        raise RuntimeError(_RELAY_GAVE_UP.format(int(watchdog.view(torch.int32)), 'call'))
+      if not (float(guard) < L.wn_range_limit()):
+        self.generation_guard_trips += 1
+        with self.exact_fp32():
+          run()
+    return out
+
+  def _generation_args(self, batch_size, condition, sample, deterministic, temperature, top_k, seed, top_p):
+    """The argument handling of generate and generation_session: the sampling controls checked, condition and sample on
+    the device, the batch size they imply, the initial window (the last receptive_field samples of `sample`, or zeros /
+    seeded noise), the model built.  Returns (sampling, condition, window, batch_size)."""
     sampling = self._sampling(temperature, top_k, seed, 2 ** self.bits, top_p)
     if self.conditioning is not None and condition is None:
       raise ValueError('Conditioning must be provided.')
@@ -924,27 +1031,30 @@ class WaveNet(torch.nn.Module):
       sample = sample[:, -rf:, :].contiguous()
     if not self.built:
       self.build([tuple(sample.shape), tuple(condition.shape)] if condition is not None else tuple(sample.shape))
-    L = _lib.lib()
-    ws = self._workspace('gen', L.wn_generate_workspace_floats(self._plan, batch_size, int(bool(use_queues))))
-    out = torch.empty(batch_size, int(length), 1, dtype=torch.float32, device=self._device)
-    def run():
-      _lib.check(L.wn_generate_sampled(self._plan, _lib.ptr(self.flat_params), _lib.ptr(sample), _lib.ptr(condition),
-                                       batch_size, int(length), int(bool(deterministic)), int(bool(use_queues)),
-                                       C.byref(sampling), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
-    run()
-    # range guard (one host read; the caller reads the samples anyway): an activation beyond the fp16 range of the
-    # split-precision kernels -> the whole call again on the exact-fp32 kernels (same seed: same draws)
-    if length > 0 and L.wn_debug_value(1) != 1:
-      slot = L.wn_generate_guard_slot(self._plan, batch_size, int(bool(use_queues)))
-      guard, watchdog = ws[slot:slot + 2].cpu()
-      if int(watchdog.view(torch.int32)) != 0:
-        raise RuntimeError(f'wn_generate: a workgroup of the generation relay gave up waiting for its predecessor '
-                           f'(code {int(watchdog.view(torch.int32))}); the samples of this call are invalid')
-      if not (float(guard) < L.wn_range_limit()):
-        self.generation_guard_trips += 1
-        with self.exact_fp32():
-          run()
-    return out
+    return sampling, condition, sample, batch_size
+
+  def generation_session(self, batch_size: int = 1, condition=None, sample=None, use_queues=False, deterministic=False,
+                         temperature=1.0, top_k=0, seed=None, top_p=1.0):
+    """A sequence made in pieces: the arguments of generate without `length`, with the same checks.  The chunks of
+    session.generate(n), concatenated, are bit for bit generate(total, same arguments).  The
+    session owns its workspace and is bound to the weights as they are now: after an optimizer step, set_weights,
+    finalize_variable_values, or entering / leaving averaged_weights() its generate raises RuntimeError."""
+    sampling, condition, window, batch_size = self._generation_args(batch_size, condition, sample, deterministic,
+                                                                    temperature, top_k, seed, top_p)
+    return GenerationSession(self, sampling, condition, window, batch_size, use_queues, deterministic)
+
+  def generate_stream(self, length, chunk, **kwargs):
+    """Generator over a generation_session(**kwargs): yields (B, min(chunk, rest), 1) tensors until `length` samples are
+    out; concatenated they are generate(length, **kwargs).  The arguments are checked here, not at the first next()."""
+    length, chunk = int(length), int(chunk)
+    if chunk < 1:
+      raise ValueError(f'chunk must be >= 1 (got {chunk})')
+    session = self.generation_session(**kwargs)
+
+    def pieces():
+      while session.position < length:
+        yield session.generate(min(chunk, length - session.position))
+    return pieces()
 
   def compute_receptive_field(self, sampling_frequency):
     """src/model.py:553-556."""
