@@ -1,9 +1,9 @@
-"""What every kernel of the block stack's forward and of the backward phase of one training pass should have produced
-FROM ITS OWN INPUTS, in float64.
+"""What every kernel of the block stack's forward, of the head's forward and the loss, and of the backward phase of one
+training pass should have produced FROM ITS OWN INPUTS, in float64.
 
 Not a conftest and not a test: a plain helper (tests/test_bwd_restatement_cpu.py pins it against fp64 autograd of the
-oracle, tests/test_gpu_bwd_tile_walk.py and tests/test_gpu_deep_tile_walk.py compare the HIP kernels with it).  It is
-plain torch float64 on whatever device its inputs live on and never calls into libwn_hip.
+oracle, tests/test_gpu_bwd_tile_walk.py, tests/test_gpu_deep_tile_walk.py and tests/test_gpu_head_tile_walk.py compare
+the HIP kernels with it).  It is plain torch float64 on whatever device its inputs live on and never calls into libwn_hip.
 
 A product is restated from the tensors its kernel read, not from other restated values: `GH[b]` from the stored `GU[b]`
 and `GH[b+1]`, `GU[b]` from the stored `GH[b+1]`, `AG[b]`, `Z[b]` and so on.  An error in one kernel therefore shows in
@@ -11,7 +11,8 @@ that kernel's tensor alone, at the size of the error, and a chain of 7 blocks do
 
 Scope: any `layers_per_block`, with or without dropout, time-invariant (global) conditioning; `restate` is the backward
 phase (DESIGN.md sections 18, 19), `restate_forward` the block stack's forward, the input conv and the skip sum (section
-19).  The head's forward (HA, logits, loss rows) is not restated: HA and GF[nf] are taken as given.
+19), `restate_head` the head's forward, the loss rows, the loss and GF[nf] = d loss / d logits (section 24).  `restate`
+itself still takes HA and GF[nf] as given: they are outputs of `restate_head`, each from the tensors its own kernel read.
 
 Notation: block b has the convs i = 0..L-1 (L = layers_per_block) with dilations d_i = dilation_schedule[b L + i].  Conv 0
 reads X_0 = XD[b] under dropout and H[b] otherwise, conv i > 0 reads X_i = P[b][i-1]; the output gradient of the last conv
@@ -24,7 +25,8 @@ Workspace tensors (`ws`, keyed as below, each `(B, T, channels)`; regions of Wav
   ('AG', b)             region 2   saved sigmoid gate
   ('HA', i) i = 0..nf-1 region 4   head activations (post-activation output of final conv i)
   ('GF', i) i = 0..nf   region 6   d loss / d (output of final conv i, pre-activation); GF[nf] = d loss / d logits is the
-                                   loss epilogue's and is taken as given
+                                   loss epilogue's: `restate` takes it as given, `restate_head` restates it
+  'logits'              region 5   the head's output, where the pass wrote it (not under the fused loss epilogue)
   ('GU', b)             region 8   d loss / d u of block b, [filter half | gate half]
   ('GH', b) b = 0..N    region 9   d loss / d H[b]
   'skipsum', 'g_skipsum' regions 3, 7   unfolded passes with use_skip only
@@ -161,6 +163,82 @@ def restate_forward(cfg, params, x_in, cond, ws, folded, dropout=None):
     conv = 'conv_skip' if cfg.skip_channels is not None else 'conv1'     # (no skip convs: the pre-residual 1x1 output)
     out['skipsum'] = sum(ws['Z', b][..., :D] @ P[f'block{b}/{conv}/kernel'][0] + P[f'block{b}/{conv}/bias']
                          for b in range(N))
+  return out
+
+
+def _loss_rows(cfg, target, pred):
+  """Per-row loss of a (rows, Cout) head output in fp64: the categorical reference is Keras's (clip to [1e-7, 1 - 1e-7] and
+  renormalise) on the soft-max, the logistic one the form that is exact in both tails."""
+  if cfg.sampling_function == 'categorical':
+    return O.loss_categorical(target, torch.softmax(pred, dim=-1))
+  if cfg.sampling_function == 'logistic':
+    return O.loss_logistic_exact(target, pred, cfg.num_mixtures, cfg.bits)
+  if cfg.sampling_function == 'gaussian':
+    return O.loss_gaussian(target, pred, cfg.num_mixtures)
+  raise NotImplementedError(cfg.sampling_function)
+
+
+def restate_head(cfg, params, ws, folded, y_true, global_batch, row_chunk=16384):
+  """The head's forward and the loss of one training pass; cfg, params, ws, folded as for `restate`.  y_true: (B, T, 1) raw
+  next samples (x[:, 1:]).  global_batch: the divisor of the step's loss (compute_average_loss).
+
+  ws needs Z (folded passes), 'skipsum' (unfolded passes with use_skip) or ('H', N) (use_skip False), every ('HA', i) and,
+  where the pass wrote a logits tensor (region 5: standalone loss kernels, exact-fp32 mode, mixture and 512-class heads),
+  'logits'.  Without 'logits' in ws -- the loss was the epilogue of the head's last conv -- the loss is restated from the
+  stored HA[nf-1] through the last conv.
+
+  Returns {key: float64 tensor}:
+    ('HA', 0)    folded: act(sum_b Z_b (W_s(b) W_f0) + b_f0 + (sum_b b_s(b)) W_f0), V(b) = W_s(b) W_f0 formed here in fp64;
+                 unfolded: act(head_in W_f0 + b_f0), head_in the stored skip sum, or H[N] when use_skip is False
+    ('HA', i)    from the stored HA[i-1]
+    'logits'     from the stored HA[nf-1] (from head_in when there is no hidden layer)
+    'loss_rows'  (B, T), from the stored logits where the pass wrote them, else from 'logits' above
+    ('GF', nf)   d (sum of the rows / global_batch) / d logits by fp64 autograd, in chunks of row_chunk rows
+    'loss'       sum of the rows / global_batch
+    'target_prob'  categorical heads: the soft-max probability of each row's target (B, T), the quantity that Keras clips"""
+  N, D = cfg.blocks, cfg.D
+  nf = len(cfg.final_layers_channels)
+  P = params
+  if folded and not (cfg.use_skip and cfg.skip_channels is not None and nf >= 1):
+    raise ValueError('only a skip head with skip_channels and a hidden head layer can fold')
+  conv = lambda x, i: x @ P[f'final{i}/kernel'][0] + P[f'final{i}/bias']
+  out = {}
+  head_in = None
+  if folded:
+    w_f0 = P['final0/kernel'][0]                   # (S, F0)
+    b_s = sum(P[f'block{b}/conv_skip/bias'] for b in range(N))
+    pre = sum(ws['Z', b][..., :D] @ (P[f'block{b}/conv_skip/kernel'][0] @ w_f0) for b in range(N))
+    out['HA', 0] = O.activation(pre + P['final0/bias'] + b_s @ w_f0, cfg.activation)
+  else:
+    head_in = ws['skipsum'] if cfg.use_skip else ws['H', N]
+    if nf:
+      out['HA', 0] = O.activation(conv(head_in, 0), cfg.activation)
+  for i in range(1, nf):
+    out['HA', i] = O.activation(conv(ws['HA', i - 1], i), cfg.activation)
+  out['logits'] = conv(ws['HA', nf - 1] if nf else head_in, nf)
+
+  src = ws['logits'] if 'logits' in ws else out['logits']
+  B, T, Cout = src.shape
+  flat = src.detach().reshape(B * T, Cout)
+  target = O.prepare_target(y_true.detach().cpu(), cfg).to(flat.device)
+  categorical = cfg.sampling_function == 'categorical'
+  target = target.reshape(B * T) if categorical else target.reshape(B * T, 1).to(flat.dtype)
+  rows, grad, tprob = [], [], []
+  for r0 in range(0, B * T, row_chunk):
+    with torch.enable_grad():
+      lg = flat[r0:r0 + row_chunk].clone().requires_grad_(True)
+      lr = _loss_rows(cfg, target[r0:r0 + row_chunk], lg)
+      g, = torch.autograd.grad(lr.sum() / global_batch, lg)
+    rows.append(lr.detach())
+    grad.append(g)
+    if categorical:
+      q = torch.softmax(lg.detach(), dim=-1)
+      tprob.append(torch.gather(q, -1, target[r0:r0 + row_chunk].unsqueeze(-1))[:, 0])
+  out['loss_rows'] = torch.cat(rows).reshape(B, T)
+  out['GF', nf] = torch.cat(grad).reshape(B, T, Cout)
+  out['loss'] = out['loss_rows'].sum() / global_batch
+  if categorical:
+    out['target_prob'] = torch.cat(tprob).reshape(B, T)
   return out
 
 

@@ -12,8 +12,12 @@ end, and nothing may leak from one utterance into the next.
 DEEP holds stacks of 2, 3 and 5 convs per block: the inner activated outputs P, the gradients GP at
 their pre-activation outputs and, under dropout, the dropped block inputs XD join the workspace tensors.  Every deep
 network and two depth-1 networks also run with dropout 0.1, and for every case the forward restatement (H, XD, P, AG, Z,
-skip sum) is pinned against the same pass: XD exactly, everything else to 1e-10 of its max."""
+skip sum) is pinned against the same pass: XD exactly, everything else to 1e-10 of its max.
+
+The head's restatement is pinned on all of these networks, folded and unfolded: HA, the logits of
+O.model_forward, the loss of O.loss_and_grads and the autograd dL/dlogits, to 1e-12 of each tensor's max."""
 import functools
+import math
 
 import pytest
 import torch
@@ -116,6 +120,7 @@ def _autograd(name, rate=0.0):
   fwd.update({('Z', b): inter['z'][b].detach() for b in range(N)})
   fwd.update({k: v for k, v in ws.items() if k[0] in ('AG', 'P', 'XD')})
   fwd['skipsum'] = ws['skipsum']
+  fwd['logits'], fwd['x_full'] = inter['logits'].detach(), x               # (for the head's pin below)
   return cfg, names, params, x[:, :-1], cond, ws, grads, pgrads, dropout, fwd
 
 
@@ -206,6 +211,89 @@ def test_forward_restatement_equals_the_oracle_pass(case):
       else:
         err = (got - ref).abs().max().item()
         assert err <= 1e-10 * scale, (case, k, err, scale)
+
+
+def _can_fold(kw):
+  return bool(kw.get('skip_channels') and kw.get('final_layers_channels') and kw.get('use_skip', True))
+
+
+# (network, folded): every network in the unfolded form, and in the folded form where a head can fold
+HEAD_CASES = [(n, f) for n, (kw, _, _) in list(NETS.items()) + list(DEEP.items())
+              for f in ((False, True) if _can_fold(kw) and kw.get('layers_per_block', 1) == 1 else (False,))]
+
+
+def test_the_head_cases_hold_every_head_form():
+  kws = {n: (NETS.get(n) or DEEP[n])[0] for n, _ in HEAD_CASES}
+  cat = lambda kw: kw.get('sampling_function', 'categorical') == 'categorical'
+  assert any(f and cat(kws[n]) for n, f in HEAD_CASES) and any(not f and cat(kws[n]) and _can_fold(kws[n]) for n, f in HEAD_CASES)
+  assert any(kw.get('skip_channels') is None and kw.get('final_layers_channels') for kw in kws.values())
+  assert any(kw.get('use_skip') is False for kw in kws.values())
+  assert any(not kw.get('final_layers_channels') and kw.get('skip_channels') for kw in kws.values())
+  assert any(not kw.get('final_layers_channels') and kw.get('skip_channels') is None for kw in kws.values())
+  assert {kw.get('sampling_function', 'categorical') for kw in kws.values()} == {'categorical', 'logistic', 'gaussian'}
+
+
+@pytest.mark.parametrize('case', HEAD_CASES, ids=lambda c: f'{c[0]}-{"folded" if c[1] else "unfolded"}')
+def test_head_restatement_equals_the_oracle_and_fp64_autograd(case):
+  """restate_head fed with the oracle's own fp64 intermediates: HA[i], the logits of O.model_forward, the loss of
+  O.loss_and_grads and the dL/dlogits of the one fp64 autograd pass of _autograd, each to 1e-12 of the tensor's max.  Twice:
+  without a stored logits tensor (the fused loss epilogue: the loss from HA[nf-1] through the last conv) and with one (the
+  standalone loss kernels), the second with the stored logits scaled and shifted so that a restatement that ignored them
+  would show.  global_batch is 2 B: the loss and the gradient halve exactly.
+
+  One quantity does not fit 1e-12: dL/dpred of a LOGISTIC head at bits = 16.  A bin mass is the difference of two sigmoids,
+  each off by up to 2^-53, so the likelihood (weights sum to 1) is off by up to 2^-52 ABSOLUTE against a value of e^-row
+  (1e-5 and less), i.e. 2^-52 e^row relative, and the row's gradient with it; the numerators sigmoid'(a) - sigmoid'(b)
+  cancel alike, times e^-ls.  Any two fp64 evaluations that round one sigmoid differently are that far apart:
+  O.loss_logistic (autograd's) against O.loss_logistic_exact (restate_head's) by 1.0e-10 of the tensor's max, and
+  O.loss_logistic_exact against ITSELF over 37-row chunks instead of the whole tensor (another vector lane, another last
+  bit) by 1.5e-11.  That gradient is therefore held to 4 * 2^-52 e^(max row) max(1, e^-min ls) of the tensor's max (1e-9 to
+  1e-8 here) and a single loss row, where the likelihood's relative error is the absolute one, to 4 * 2^-52 e^(max row); the
+  loss, the sum in which those errors average out, stays at 1e-12 like everything else."""
+  name, folded = case
+  cfg, names, params, x_in, cond, ws, grads, _, _, fwd = _autograd(name)
+  nf, N, M = len(cfg.final_layers_channels), cfg.blocks, cfg.num_mixtures
+  Bn = x_in.shape[0]
+  x = fwd['x_full']
+  y_true = x[:, 1:]
+  given = {k: v for k, v in ws.items() if k[0] in ('Z', 'HA')}
+  if not folded:
+    given.update({'skipsum': ws['skipsum']} if cfg.use_skip else {('H', N): ws['H', N]})
+  loss_ref = O.loss_and_grads(x, [params[n] for n in names], cfg, cond, global_batch=2 * Bn)[0]
+  want = {('HA', i): ws['HA', i] for i in range(nf)}
+  want.update({'logits': fwd['logits'], ('GF', nf): grads['GF', nf] * 0.5, 'loss': loss_ref})
+
+  def check(tag, got, ref, rows, stored):
+    for k, r in ref.items():
+      assert got[k].shape == r.shape, (case, tag, k)
+      scale = r.abs().max().item()
+      assert scale > 0, (case, tag, k)
+      tol = 1e-12 * scale
+      if cfg.sampling_function == 'logistic' and k in (('GF', nf), 'loss_rows'):
+        ls = stored[..., 2 * M:].clamp(min=-7.0)
+        bar = 4 * 2.0 ** -52 * math.exp(rows.max().item())
+        assert 1e-12 < bar < 1e-8, (case, tag, bar)
+        # (a row's loss: the likelihood's relative error, absolute; the gradient: relative, with the e^-ls of its numerators)
+        tol = bar if k == 'loss_rows' else bar * max(1.0, math.exp(-ls.min().item())) * scale
+      err = (got[k] - r).abs().max().item()
+      assert err <= tol, (case, tag, k, err, scale, tol)
+
+  got = R.restate_head(cfg, params, given, folded, y_true, 2 * Bn, row_chunk=37)      # chunks that do not divide B T
+  assert sorted((k for k in got if k not in ('loss_rows', 'target_prob')), key=str) == sorted(want, key=str)
+  assert ('target_prob' in got) == (M is None) and got['loss_rows'].shape == x_in.shape[:2]
+  check('from HA', got, want, got['loss_rows'], fwd['logits'])
+  assert abs(got['loss_rows'].sum().item() / (2 * Bn) - loss_ref.item()) <= 1e-12 * abs(loss_ref.item())
+
+  # with a stored logits tensor the loss follows IT, the restated logits still follow HA[nf-1]
+  shifted = fwd['logits'] * 1.25 + 0.01
+  lg = shifted.clone().requires_grad_(True)
+  pred = torch.softmax(lg, -1) if M is None else lg
+  rows = O.loss_fn(O.prepare_target(y_true, cfg), pred, cfg)
+  g_ref, = torch.autograd.grad(rows.sum() / (2 * Bn), lg)
+  rows = rows.detach()
+  got2 = R.restate_head(cfg, params, dict(given, logits=shifted), folded, y_true, 2 * Bn)
+  check('from stored logits', got2, {'logits': fwd['logits'], ('GF', nf): g_ref, 'loss': rows.sum() / (2 * Bn),
+                                     'loss_rows': rows}, rows, shifted)
 
 
 def test_depth_and_dilations_of_the_deep_cases():

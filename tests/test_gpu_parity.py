@@ -1234,6 +1234,12 @@ def test_wide_skip_contraction_matches_oracle():
   assert (out[:2].cpu().double() - inter['logits']).abs().max() < ATOL_ACT      # (oracle on two of the utterances)
   assert (small.cpu().double() - inter['logits']).abs().max() < ATOL_ACT
   assert torch.equal(out[:2], small)                   # same per-element MFMA sequence in both kernels
+  # the streamed kernel's grid holds 2048 row tiles: the 13 tiles of its second pass are the last ones, all in utterance 8
+  assert 9 * 229 - 2048 == 13 and 13 < 229
+  last = model.logits(x[8:9].to(dev())).clone()        # 229 row tiles, one pass
+  lg8 = O.model_forward(x[8:9].double(), [p.double() for p in params], ocfg, None, return_logits=True)
+  assert (out[8:9].cpu().double() - lg8).abs().max() < ATOL_ACT
+  assert torch.equal(out[8:9], last), (out[8] != last[0]).any(dim=-1).nonzero()[:8].flatten().tolist()
 
 
 @pytest.mark.parametrize('name', ['cat_r64', 'mol', 'gauss'])
