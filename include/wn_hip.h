@@ -367,6 +367,33 @@ int wn_plan_set_train_phases(wn_plan* plan, int32_t phases);
  * replicas the metric's mean.  scratch: >= 2048 floats of the caller's. */
 int wn_sum_squared_error(const float* a, const float* b, int64_t n, float scale, float* out, float* scratch,
                          void* stream);
+/* ---- sample_weight of a training / evaluation step (Keras's train_step contract) ----
+ * w: rows = B * T device floats over the target rows, w[b * T + t] belongs to the target x_full[b][t + 1].  Arms the
+ * calling thread's execution state; it stays armed until w == NULL disarms it (the caller owns the buffer: disarm before
+ * freeing it).  While armed, wn_train_fwd_bwd and wn_eval_loss weigh their rows; they return WN_E_INVALID when
+ * rows != B * T of the call, checked before the device is touched, the message naming both numbers.  wn_vjp, wn_forward*,
+ * wn_loss_fn, generation and the optimizer ignore it.  With wn_plan_set_train_phases the weights are read in phase 1 only.
+ *   loss = sum_{b,t} w[b,t] l[b,t] / global_batch (+ the L2 term, unchanged).  The normaliser stays global_batch, as in
+ *     tf.nn.compute_average_loss(per_example_loss, sample_weight): no division by sum w.  A caller who wants the mean over
+ *     the valid samples scales w.  Data parallelism needs nothing new: every replica weighs its own rows.
+ *   gradient: d loss / d logits (or d pred) of a row is that of the unweighted step with gscale = 1 / global_batch replaced
+ *     by gscale * w[row], the product taken once per row in fp32; the stored per-row loss (wn_debug_ws_region what 12) is
+ *     w[row] * l[row].  w == 1 everywhere therefore gives the bits of the call without weights, which also launches the
+ *     kernels it launched before this entry point existed.
+ *   w[row] == 0 is a select, not a product: the row's loss is +0 and every entry of its gradient is 0, even where the row's
+ *     own loss or gradient is inf or NaN (a mixture likelihood that underflows), and the row contributes nothing to the
+ *     published max-abs of the gradient.
+ *   Negative and non-finite weights are not checked: a plain product is taken, non-finite in gives non-finite out.
+ *   The armed step sample is drawn for every row as without weights; the weights do not enter it.
+ * WN_E_INVALID: a null plan; w != NULL with rows < 1. */
+int wn_plan_arm_row_weights(wn_plan* plan, const float* w, int64_t rows);
+/* Keras's weighted MeanSquaredError of one step as a device scalar: out[0] = scale * sum_i w[i] (a[i] - b[i])^2 / sum_i w[i],
+ * and 0 when sum_i w[i] == 0; numerator and denominator in one pass, double accumulation in two stages as
+ * wn_sum_squared_error.  scale = 1 / replicas makes the SUM over the replicas the average of their ratios: the weighted
+ * mean of the global batch when the replicas hold equal sum w, an approximation otherwise.  scratch: >= 2048 floats of the
+ * caller's.  WN_E_INVALID: a null pointer or n < 1. */
+int wn_weighted_squared_error(const float* a, const float* b, const float* w, int64_t n, float scale, float* out,
+                              float* scratch, void* stream);
 /* WaveNet.sample_waveform(pred, deterministic), src/model.py:393-503: (rows,C) -> (rows) */
 int wn_sample_waveform(int32_t head, const float* pred, int64_t rows, int32_t C,
                        int32_t num_mixtures, int32_t bits, int32_t deterministic, uint64_t seed,

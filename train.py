@@ -43,10 +43,13 @@ config = {                       # defaults of the reference, train.py:22-50
     # hold the last n utterances' frames out of training and report val_loss (test_step) after every epoch; the monitored
     # quantity of checkpointing, plateau and early stop stays loss, as in the reference
     'validation_utterances': 0,
+    # not in the reference: keep the tail of every recording as one more frame, zero-padded, and train / validate with a
+    # sample_weight of 0 on the padding (data.frame_padded); false = the reference's framing, which drops the tail
+    'pad_end': False,
 }
 
 
-def validate(model, frames, cond, per_rank, rank, world, scope):
+def validate(model, frames, cond, per_rank, rank, world, scope, weights=None):
   """Mean test_step loss over the held-out frames (whole global batches; a smaller set is one batch of what is there),
   on the averaged weights under use_ema.  Runs after the epoch's training results were read: the metrics are reset per
   pass here and again when the next epoch starts."""
@@ -59,7 +62,8 @@ def validate(model, frames, cond, per_rank, rank, world, scope):
       for m in model.metrics:
         m.reset_state()
       sl = slice(i + rank * per_rank, i + (rank + 1) * per_rank)
-      total += float(model.test_step((frames[sl], cond[sl]) if cond is not None else frames[sl])['loss'])
+      wkw = {} if weights is None else {'sample_weight': weights[sl]}
+      total += float(model.test_step((frames[sl], cond[sl]) if cond is not None else frames[sl], **wkw)['loss'])
       n += 1
   return total / max(n, 1)
 
@@ -112,21 +116,29 @@ def main():
     raw = torch.from_numpy(arr)
     raw = (data.normalise_int16(raw) if arr.dtype == np.int16 else raw.float()).to(dev)
   cond = None
+  pad_end = bool(config['pad_end'])
+  weights = None                                                    # pad_end: sample_weight of every frame, (n, L)
   if conditioned:
     ncls = int(config['condition_classes'])
     labels = np.load(config['labels']).astype(np.int64) if config['labels'] else np.arange(raw.shape[0]) % ncls
     if len(labels) != raw.shape[0]:
       raise SystemExit('labels must hold one class id per utterance')
-    parts = [data.preprocess_with_condition(w, int(l), ncls, L, config['apply_mulaw']) for w, l in zip(raw, labels)]
+    parts = [data.preprocess_with_condition(w, int(l), ncls, L, config['apply_mulaw'], pad_end=pad_end) for w, l in zip(raw, labels)]
     frames = torch.cat([p[0] for p in parts], dim=0)
     cond = torch.cat([p[1] for p in parts], dim=0)
+    per_utterance = [p[0].shape[0] for p in parts]
+  elif pad_end:
+    parts = [data.preprocess_waveform_padded(w, L, config['apply_mulaw']) for w in raw]
+    frames = torch.cat([p[0] for p in parts], dim=0)
     per_utterance = [p[0].shape[0] for p in parts]
   else:
     parts = [data.preprocess_waveform(w, L, config['apply_mulaw']) for w in raw]
     frames = torch.cat(parts, dim=0)
     per_utterance = [p.shape[0] for p in parts]
+  if pad_end:
+    weights = torch.cat([p[-1] for p in parts], dim=0)
   n_val = int(config['validation_utterances'])
-  val_frames = val_cond = None
+  val_frames = val_cond = val_weights = None
   if n_val > 0:                                                     # frames are in utterance order: the tail is held out
     held = sum(per_utterance[-n_val:])
     if n_val >= raw.shape[0] or held < world:
@@ -134,6 +146,8 @@ def main():
     val_frames, frames = frames[-held:], frames[:-held]
     if conditioned:
       val_cond, cond = cond[-held:], cond[:-held]
+    if pad_end:
+      val_weights, weights = weights[-held:], weights[:-held]
   per_rank = config['batch_size'] // world
   if per_rank < 1 or frames.shape[0] < config['batch_size']:
     raise SystemExit('not enough data for one global batch')
@@ -190,7 +204,8 @@ def main():
     for i in range(n_batches):
       idx = perm[i * config['batch_size']:(i + 1) * config['batch_size']][rank * per_rank:(rank + 1) * per_rank]
       idx = idx.to(dev)
-      logs = model.train_step((frames[idx], cond[idx]) if conditioned else frames[idx])
+      wkw = {'sample_weight': weights[idx]} if pad_end else {}
+      logs = model.train_step((frames[idx], cond[idx]) if conditioned else frames[idx], **wkw)
       if nan_guard.on_batch_end(logs['loss']):
         print('loss is not finite: terminating') if rank == 0 else None
         stop = True
@@ -198,7 +213,7 @@ def main():
     loss = model.loss_tracker.result()
     val_loss = None
     if val_frames is not None and not stop:                         # every rank: test_step reduces over the replicas
-      val_loss = validate(model, val_frames, val_cond, per_rank, rank, world, averaged)
+      val_loss = validate(model, val_frames, val_cond, per_rank, rank, world, averaged, val_weights)
     if rank == 0:
       sps = n_batches * config['batch_size'] * L / max(time.time() - t0, 1e-9)
       extra = ''.join(f' - {k}: {v:.4f}' for k, v in logs.items() if k != 'loss')   # the compiled metrics, as Keras logs them

@@ -27,6 +27,17 @@ extern "C" int wn_sum_squared_error(const float* a, const float* b, int64_t n, f
   if (!a || !b || !out || !scratch || n < 1) { wn_set_error("sum_squared_error: bad arguments"); return WN_E_INVALID; }
   return wn_launch_sqdiff_sum(a, b, n, scale, out, scratch, (hipStream_t)stream);
 }
+extern "C" int wn_weighted_squared_error(const float* a, const float* b, const float* w, int64_t n, float scale, float* out,
+                                         float* scratch, void* stream) {
+  if (!a || !b || !w || !out || !scratch || n < 1) { wn_set_error("weighted_squared_error: bad arguments (a null pointer or n < 1)"); return WN_E_INVALID; }
+  return wn_launch_wsqdiff_mean(a, b, w, n, scale, out, scratch, (hipStream_t)stream);
+}
+extern "C" int wn_plan_arm_row_weights(wn_plan* p, const float* w, int64_t rows) {
+  if (!p) { wn_set_error("arm_row_weights: null plan"); return WN_E_INVALID; }
+  if (w && rows < 1) { wn_set_error("arm_row_weights: rows must be >= 1 (got %lld)", (long long)rows); return WN_E_INVALID; }
+  wnp::ex(p).row_weights = w; wnp::ex(p).row_weights_n = w ? rows : 0;
+  return WN_OK;
+}
 extern "C" int wn_plan_arm_step_sample(wn_plan* p, float* sample_out, int32_t deterministic, uint64_t seed, uint64_t offset) {
   if (!p) { wn_set_error("arm_step_sample: null plan"); return WN_E_INVALID; }
   if (sample_out && p->c.head == WN_HEAD_CATEGORICAL && (deterministic || !wn_sample_from_logits_supported(p->Cout))) {

@@ -145,11 +145,20 @@ struct WnCeRow {
     return gscale * q * (g - dot);
   }
 };
+// sample_weight of a row (every loss kernel, the mixture one included, takes the factor from here):
+// the gradient is that of the unweighted row with gscale * w in gscale's place, the product taken once per row; the stored
+// loss is w * l.  w == 0 is a select, not a product: loss +0 and gradient 0 whatever the row holds (inf, NaN), and so nothing
+// of the row reaches the max-abs.  Any other w, negative and non-finite included, is a plain product.  w == 1 changes no bit.
+__device__ __forceinline__ float wn_w_gscale(float gscale, float w) { return gscale * w; }
+__device__ __forceinline__ float wn_w_loss(float w, float l) { return w == 0.f ? 0.f : w * l; }
+__device__ __forceinline__ float wn_w_grad(float w, float g) { return w == 0.f ? 0.f : g; }
 // Loss and (g != null) gradient of one row held as a softmax row (either form): lane 0 stores the loss, every lane
 // stores the gradients of its classes to g[g_off + 0..C) and folds their magnitudes into gmax.
-template <typename Row>
+// WEIGHTED: the row's sample_weight w (wave-uniform) enters as above; false is the row without weights, w unused.
+template <bool WEIGHTED = false, typename Row>
 __device__ __forceinline__ void wn_cat_ce_row(const Row& r, int tgt, float gscale, float* loss, float* g, int64_t g_off,
-                                              float& gmax) {
+                                              float& gmax, float w = 1.0f) {
+  if constexpr (WEIGHTED) gscale = wn_w_gscale(gscale, w);
   float S = 0.f, A = 0.f;
   r.each([&](int, float q) {
     S += wn_ce_clip(q);
@@ -160,11 +169,12 @@ __device__ __forceinline__ void wn_cat_ce_row(const Row& r, int tgt, float gscal
   tgt = wn_ce_target(tgt, r.C);
   const float qt = r.prob(tgt);
   const float pt = wn_ce_clip(qt);
-  if (r.lane == 0) *loss = wn_ce_loss(pt, S);
+  if (r.lane == 0) *loss = WEIGHTED ? wn_w_loss(w, wn_ce_loss(pt, S)) : wn_ce_loss(pt, S);
   if (g) {
     const WnCeRow ce(S, A, qt);
     r.each([&](int j, float q) {
-      const float gl = ce.grad(q, j == tgt, gscale);
+      float gl = ce.grad(q, j == tgt, gscale);
+      if constexpr (WEIGHTED) gl = wn_w_grad(w, gl);
       g[g_off + j] = gl;
       gmax = fmaxf(gmax, fabsf(gl));
     });

@@ -313,6 +313,7 @@ int forward_core(wn_plan* p, const float* params, const float* x, bool prep, con
       ga.y = lf->g_logits; ga.ldy = c.cout; ga.N = c.cout; ga.B = B; ga.T = T; ga.absmax_out = lf->absmax_out;
       ga.cat_loss = 1; ga.target = lf->target; ga.gscale = lf->gscale; ga.loss_rows = lf->loss_rows;
       ga.sample_out = lf->sample_out; ga.inv_lv = lf->inv_lv; ga.seed = lf->seed; ga.offset = lf->offset;
+      ga.row_weight = lf->row_weight;
       rc = wn_launch_gemm_planes16s(ga, s);
       if (rc) return rc;
       lf->done = true;
@@ -358,11 +359,12 @@ bool loss_fusable(const wn_plan* p, int64_t rows) {
 }
 
 int loss_stage(wn_plan* p, int B, int T, int global_batch, bool want_grad, float* ws, const WsLayout& L,
-               float* loss_out, float* absmax_out, hipStream_t s, bool fused_done) {
+               float* loss_out, float* absmax_out, hipStream_t s, bool fused_done, const float* row_weight) {
   const int64_t rows = (int64_t)B * T;
   const float gscale = 1.0f / (float)global_batch;     // compute_average_loss, src/model.py:328-329
   int rc;
-  // (the head's last conv already left the row losses and d loss / d logits: see LossFuse)
+  // (the head's last conv already left the row losses and d loss / d logits: see LossFuse; weighted rows are stored
+  // weighted by every loss kernel, so the sum below is the same launch with and without weights)
   if (fused_done) return wn_launch_sum(ws + L.loss_rows, rows, gscale, loss_out, ws + L.sum_scratch, s);
   // deferred weight gradients read d loss / d logits from GF.back(): written there directly (no 131 MB copy)
   float* g_logits = want_grad ? ws + L.GF.back() : nullptr;
@@ -374,13 +376,20 @@ int loss_stage(wn_plan* p, int B, int T, int global_batch, bool want_grad, float
     if (want_grad && wnp::ex(p).step_sample && !wnp::ex(p).step_sample_det && p->Cout <= 256) { so = wnp::ex(p).step_sample; wnp::ex(p).step_sample = nullptr; }
     rc = wn_launch_cat_loss(ws + L.logits, reinterpret_cast<const int32_t*>(ws + L.target), rows, p->Cout,
                             gscale, ws + L.loss_rows, g_logits, absmax_out, s, so, p->c.bits, wnp::ex(p).step_sample_seed,
-                            wnp::ex(p).step_sample_off);
+                            wnp::ex(p).step_sample_off, row_weight);
   } else {
     rc = wn_launch_mix_loss(ws + L.logits, ws + L.yt, rows, p->c.num_mixtures, p->c.bits,
-                            p->c.head == WN_HEAD_LOGISTIC ? 1 : 2, gscale, ws + L.loss_rows, g_logits, absmax_out, s);
+                            p->c.head == WN_HEAD_LOGISTIC ? 1 : 2, gscale, ws + L.loss_rows, g_logits, absmax_out, s, row_weight);
   }
   if (rc) return rc;
   return wn_launch_sum(ws + L.loss_rows, rows, gscale, loss_out, ws + L.sum_scratch, s);
+}
+
+int row_weights_check(const char* who, const wn_exec& e, int B, int T) {
+  if (!e.row_weights || e.row_weights_n == (int64_t)B * T) return WN_OK;
+  wn_set_error("%s: the armed row weights cover %lld rows, the call has B * T = %lld", who, (long long)e.row_weights_n,
+               (long long)((int64_t)B * T));
+  return WN_E_INVALID;
 }
 
 }  // namespace wnp
@@ -429,6 +438,7 @@ extern "C" int wn_eval_loss(wn_plan* p, const float* params, const float* x_full
                             int32_t B, int32_t T, int32_t global_batch, float* loss_out, float* pred_out,
                             float* workspace, int64_t ws_floats, void* stream) {
   if (!p || !params || !x_full || !workspace || !loss_out || B < 1 || T < 1) { wn_set_error("eval_loss: bad arguments"); return WN_E_INVALID; }
+  if (row_weights_check("eval_loss", wnp::ex(p), B, T)) return WN_E_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const WsLayout L = make_layout(p, B, T, false);
   if (ws_floats < L.total) { wn_set_error("eval_loss: workspace too small"); return WN_E_INVALID; }
@@ -438,7 +448,8 @@ extern "C" int wn_eval_loss(wn_plan* p, const float* params, const float* x_full
   { const int rcs = shift_split(x_full, B, T, inputs, workspace + L.yt, s); if (rcs) return rcs; }
   int rc = forward_core(p, params, inputs, true, cond, B, T, false, workspace, L, s);
   if (rc) return rc;
-  rc = loss_stage(p, B, T, global_batch > 0 ? global_batch : B, false, workspace, L, loss_out, nullptr, s);
+  rc = loss_stage(p, B, T, global_batch > 0 ? global_batch : B, false, workspace, L, loss_out, nullptr, s, false,
+                  wnp::ex(p).row_weights);
   if (rc) return rc;
   rc = wn_launch_guard_flag(workspace + L.fwd_absmax, WN_RANGE_LIMIT, wn_debug_get(1) != 1, loss_out + 2, s);
   if (rc) return rc;

@@ -51,6 +51,8 @@ struct GS {
 // sample_waveform draw are register loops plus a handful of exchanges with the partner lane, for 32 rows at once; the
 // one-row-per-wave loss kernel spends ~300 wave instructions per ROW on the same arithmetic (wn_cat_loss256_kernel: VALU
 // bound at 105 us for 268 MB) and needs the logits written (131 MB) and read back (131 MB).
+// -4: -3 with the rows' sample_weight (a.row_weight): the weight is loaded where the target is and enters
+// through the factor of wn_catrow.h.  An instantiation of its own, so that a step without weights launches -3 as it was.
 template <int RT, int JT_, int ACT, bool SHIFT = false>
 __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesArgs a) {
   using C = GS<RT, JT_>;
@@ -196,13 +198,19 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
 
     // ---- bias, activation, range guard, staged row stores ----
     const unsigned voff = (unsigned)(lane >> 3) * (unsigned)(a.ldy * 4) + (unsigned)(lane & 7) * 16u;
-    if constexpr (ACT == -3) {
-      static_assert(ACT != -3 || (RT == 1 && JT == 8), "the loss epilogue is the 256-class form");
+    if constexpr (ACT == -3 || ACT == -4) {
+      constexpr bool WEIGHTED = ACT == -4;
+      static_assert(RT == 1 && JT == 8, "the loss epilogue is the 256-class form");
       const int rows_valid = live ? max(0, min(32, a.T - t0)) : 0;
       const bool rok = xok[0];
       const int64_t row = row0 + tl;
       int tgt = rok ? a.target[row] : 0;
       tgt = wn_ce_target(tgt, 256);
+      float rw = 1.0f, gscale = a.gscale;
+      if constexpr (WEIGHTED) {
+        rw = rok ? a.row_weight[row] : 0.f;
+        gscale = wn_w_gscale(gscale, rw);
+      }
       auto xch = [](float v) { return __shfl_xor(v, 32); };       // the partner lane holds the row's other 128 classes
       // logits = acc + bias; row maximum
       float m = -INFINITY;
@@ -303,14 +311,15 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
       A += xch(A);
       qt += xch(qt);                                      // (the other half contributes 0)
       const WnCeRow ce(S, A, qt);
-      if (rok && h == 0) a.loss_rows[row] = wn_ce_loss(ce.pt, S);
+      if (rok && h == 0) a.loss_rows[row] = WEIGHTED ? wn_w_loss(rw, wn_ce_loss(ce.pt, S)) : wn_ce_loss(ce.pt, S);
       // ---- gradient w.r.t. the logits, in place ----
 #pragma unroll
       for (int j = 0; j < JT; ++j) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float q = acc[0][j][r];
-          const float gl = ce.grad(q, 32 * j + 8 * (r >> 2) + 4 * h + (r & 3) == tgt, a.gscale);
+          float gl = ce.grad(q, 32 * j + 8 * (r >> 2) + 4 * h + (r & 3) == tgt, gscale);
+          if constexpr (WEIGHTED) gl = wn_w_grad(rw, gl);
           acc[0][j][r] = gl;
           if (rok) wmax = fmaxf(wmax, fabsf(gl));
         }
@@ -363,7 +372,7 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the look-ahead k-steps land before the LDS is given back
   if (a.absmax_out) {
     wmax = wn_wave_absmax_bits(wmax);
-    if (lane == 0) { if (ACT == -2 || ACT == -3) wn_absmax_publish(a.absmax_out, wmax); else wn_absmax_publish_any(a.absmax_out, wmax); }
+    if (lane == 0) { if (ACT == -2 || ACT == -3 || ACT == -4) wn_absmax_publish(a.absmax_out, wmax); else wn_absmax_publish_any(a.absmax_out, wmax); }
   }
 }
 
@@ -405,7 +414,8 @@ int wn_launch_gemm_planes16s(const WnGemmPlanesArgs& a, hipStream_t s) {
     }
   } else if (a.cat_loss) {
     if (a.N != 256 || a.bwd || !a.target || !a.loss_rows || !a.y) { wn_set_error("gemm_planes16s: the loss epilogue is the 256-class forward form"); return WN_E_UNSUPPORTED; }
-    WN_GS_LAUNCH(1, 8, -3);
+    if (a.row_weight) WN_GS_LAUNCH(1, 8, -4);
+    else WN_GS_LAUNCH(1, 8, -3);
   } else if (a.bwd) {
     if (a.N == 256) WN_GS_LAUNCH(1, 8, -2);
     else WN_GS_LAUNCH(2, 4, -2);

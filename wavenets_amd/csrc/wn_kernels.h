@@ -103,6 +103,9 @@ struct WnGemmPlanesArgs {
   float* sample_out;       // [rows] or null
   float inv_lv;            // 2 / levels
   uint64_t seed, offset;   // Philox key / counter word of the draw
+  // sample_weight of the rows (cat_loss only; wn_catrow.h) or null.  Non-null selects the weighted
+  // instantiation of the epilogue; null launches the instantiation that has no such load
+  const float* row_weight; // [rows]
 };
 int wn_gemm_planes16s_supported(int N, int plane_k, int nplanes, int ld, int ldy);
 int wn_gemm_taps16s_supported(int N, int plane_k, int ntaps, int ld, int ldy);
@@ -387,9 +390,12 @@ int wn_launch_inv_mulaw(const float* y, float* x, int64_t n, hipStream_t s);
 // ---------------------------------------------------------------- softmax / loss / reductions (wn_loss.hip)
 int wn_launch_softmax(const float* logits, float* probs, int64_t rows, int C, hipStream_t s);
 // categorical: Keras sparse CE on clipped probabilities; g_logits may be null (loss only)
+// weight ([rows] or null, here and in wn_launch_mix_loss): the rows' sample_weight (wn_catrow.h); non-null launches the
+// weighted twin of the kernel, null the kernel as it is without weights
 int wn_launch_cat_loss(const float* logits, const int32_t* target, int64_t rows, int C,
                        float gscale, float* loss_rows, float* g_logits, float* absmax_out, hipStream_t s,
-                       float* sample_out = nullptr, int bits = 8, uint64_t seed = 0, uint64_t offset = 0);
+                       float* sample_out = nullptr, int bits = 8, uint64_t seed = 0, uint64_t offset = 0,
+                       const float* weight = nullptr);
 // seed of a backward pass from a caller's gradient g (rows, C): dl = g (through_softmax 0) or the softmax vector-Jacobian
 // product q (g - <g, q>), q = softmax(logits); max-abs of dl published to absmax_out
 int wn_launch_vjp_seed(const float* logits, const float* g, int64_t rows, int C, int through_softmax, float* dl,
@@ -399,9 +405,13 @@ int wn_launch_cat_loss_probs(const float* probs, const int32_t* target, int64_t 
                              float* loss_rows, hipStream_t s);
 // kind 1 = logistic, 2 = gaussian
 int wn_launch_mix_loss(const float* pred, const float* y, int64_t rows, int M, int bits, int kind,
-                       float gscale, float* loss_rows, float* g_pred, float* absmax_out, hipStream_t s);
+                       float gscale, float* loss_rows, float* g_pred, float* absmax_out, hipStream_t s,
+                       const float* weight = nullptr);
 int wn_launch_sum(const float* v, int64_t n, float scale, float* out, float* scratch, hipStream_t s);
 int wn_launch_sqdiff_sum(const float* a, const float* b, int64_t n, float scale, float* out, float* scratch, hipStream_t s);
+// out[0] = scale * sum(w (a - b)^2) / sum(w), 0 when sum(w) == 0; scratch as for wn_launch_sum
+int wn_launch_wsqdiff_mean(const float* a, const float* b, const float* w, int64_t n, float scale, float* out, float* scratch,
+                           hipStream_t s);
 
 // ---------------------------------------------------------------- samplers (wn_sample.hip)
 // em: queued generation, the sample also goes to the output rows and the network's input slot in the same launch.

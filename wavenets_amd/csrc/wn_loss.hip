@@ -28,19 +28,23 @@ int wn_launch_softmax(const float* logits, float* probs, int64_t rows, int C, hi
 // C <= 256, the shape of every BASELINE categorical head: persistent waves, one row at a time per wave with the NEXT row's
 // logits and target already requested (a one-row-per-wave launch spends most of a row waiting for its loads: 172 us for
 // 268 MB); the row lives in registers, and the max-abs of the gradients is published once per wave.
-__global__ __launch_bounds__(256) void wn_cat_loss256_kernel(const float* logits, const int32_t* target,
-                                                             int64_t rows, int C, float gscale,
-                                                             float* loss_rows, float* g_logits, float* absmax_out,
-                                                             float* sample_out, float inv_lv, uint64_t seed, uint64_t offset) {
+// WEIGHTED (sample_weight): weight[row] goes through wn_cat_ce_row; the next row's weight travels with
+// its prefetch.  The two __global__ functions below are the instantiations: the one without weights keeps its arguments.
+template <bool WEIGHTED>
+__device__ __forceinline__ void wn_cat_loss256_body(const float* logits, const int32_t* target, int64_t rows, int C, float gscale,
+                                                    float* loss_rows, float* g_logits, float* absmax_out, float* sample_out,
+                                                    float inv_lv, uint64_t seed, uint64_t offset, const float* weight) {
   __shared__ float qs[4][256];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t stride = (int64_t)gridDim.x * 4;
   int64_t row = (int64_t)blockIdx.x * 4 + w;
   float vn[4];
   int tn = 0;
+  float wnx = 1.0f;
   auto fetch = [&](int64_t r) {
     wn_cat_load4(logits + r * C, C, lane, vn);
     tn = target[r];
+    if constexpr (WEIGHTED) wnx = weight[r];
   };
   if (row < rows) fetch(row);
   float gmax = 0.f;
@@ -49,6 +53,7 @@ __global__ __launch_bounds__(256) void wn_cat_loss256_kernel(const float* logits
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = vn[k];
     const int tgt = tn;
+    const float rw = wnx;
     if (row + stride < rows) fetch(row + stride);     // in flight while this row is worked on
     const WnSoftmaxRegs r(v, C, lane);
     if (sample_out) {
@@ -60,38 +65,69 @@ __global__ __launch_bounds__(256) void wn_cat_loss256_kernel(const float* logits
       if (lane == 0) sample_out[row] = (float)drawn * inv_lv - 1.0f;
       __builtin_amdgcn_wave_barrier();                // the next row rewrites qw
     }
-    wn_cat_ce_row(r, tgt, gscale, loss_rows + row, g_logits, row * C, gmax);
+    wn_cat_ce_row<WEIGHTED>(r, tgt, gscale, loss_rows + row, g_logits, row * C, gmax, rw);
   }
   if (g_logits && absmax_out) {
     gmax = wn_wave_max(gmax);
     if (lane == 0) wn_absmax_publish(absmax_out, gmax);
   }
 }
+__global__ __launch_bounds__(256) void wn_cat_loss256_kernel(const float* logits, const int32_t* target,
+                                                             int64_t rows, int C, float gscale,
+                                                             float* loss_rows, float* g_logits, float* absmax_out,
+                                                             float* sample_out, float inv_lv, uint64_t seed, uint64_t offset) {
+  wn_cat_loss256_body<false>(logits, target, rows, C, gscale, loss_rows, g_logits, absmax_out, sample_out, inv_lv, seed, offset, nullptr);
+}
+__global__ __launch_bounds__(256) void wn_cat_loss256_weighted_kernel(const float* logits, const int32_t* target,
+                                                                      int64_t rows, int C, float gscale,
+                                                                      float* loss_rows, float* g_logits, float* absmax_out,
+                                                                      float* sample_out, float inv_lv, uint64_t seed, uint64_t offset,
+                                                                      const float* weight) {
+  wn_cat_loss256_body<true>(logits, target, rows, C, gscale, loss_rows, g_logits, absmax_out, sample_out, inv_lv, seed, offset, weight);
+}
 
 // more than 256 classes: one row per wave, the row re-read from memory on every pass
-__global__ __launch_bounds__(256) void wn_cat_loss_kernel(const float* logits, const int32_t* target,
-                                                          int64_t rows, int C, float gscale,
-                                                          float* loss_rows, float* g_logits, float* absmax_out) {
+template <bool WEIGHTED>
+__device__ __forceinline__ void wn_cat_loss_body(const float* logits, const int32_t* target, int64_t rows, int C, float gscale,
+                                                 float* loss_rows, float* g_logits, float* absmax_out, const float* weight) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   float gmax = 0.f;
-  wn_cat_ce_row(WnSoftmaxLoop(logits + row * C, C, lane), target[row], gscale, loss_rows + row, g_logits, row * C, gmax);
+  float rw = 1.0f;
+  if constexpr (WEIGHTED) rw = weight[row];
+  wn_cat_ce_row<WEIGHTED>(WnSoftmaxLoop(logits + row * C, C, lane), target[row], gscale, loss_rows + row, g_logits, row * C, gmax, rw);
   if (g_logits && absmax_out) {
     gmax = wn_wave_max(gmax);
     if (lane == 0) wn_absmax_publish(absmax_out, gmax);
   }
 }
+__global__ __launch_bounds__(256) void wn_cat_loss_kernel(const float* logits, const int32_t* target,
+                                                          int64_t rows, int C, float gscale,
+                                                          float* loss_rows, float* g_logits, float* absmax_out) {
+  wn_cat_loss_body<false>(logits, target, rows, C, gscale, loss_rows, g_logits, absmax_out, nullptr);
+}
+__global__ __launch_bounds__(256) void wn_cat_loss_weighted_kernel(const float* logits, const int32_t* target,
+                                                                   int64_t rows, int C, float gscale,
+                                                                   float* loss_rows, float* g_logits, float* absmax_out,
+                                                                   const float* weight) {
+  wn_cat_loss_body<true>(logits, target, rows, C, gscale, loss_rows, g_logits, absmax_out, weight);
+}
 int wn_launch_cat_loss(const float* logits, const int32_t* target, int64_t rows, int C,
                        float gscale, float* loss_rows, float* g_logits, float* absmax_out, hipStream_t s,
-                       float* sample_out, int bits, uint64_t seed, uint64_t offset) {
+                       float* sample_out, int bits, uint64_t seed, uint64_t offset, const float* weight) {
   if (rows <= 0) return WN_OK;
   if (sample_out && C > 256) { wn_set_error("cat_loss: the in-kernel sample draw needs <= 256 classes"); return WN_E_UNSUPPORTED; }
   const float inv_lv = sample_out ? 1.0f / (float)(1 << (bits - 1)) : 0.f;
   if (C <= 256) {
     const int64_t wgs = std::min<int64_t>((rows + 3) / 4, 256 * 8);
-    hipLaunchKernelGGL(wn_cat_loss256_kernel, dim3((unsigned)wgs), dim3(256), 0, s, logits, target, rows, C, gscale,
-                       loss_rows, g_logits, absmax_out, sample_out, inv_lv, seed, offset);
+    if (weight) hipLaunchKernelGGL(wn_cat_loss256_weighted_kernel, dim3((unsigned)wgs), dim3(256), 0, s, logits, target, rows, C,
+                                   gscale, loss_rows, g_logits, absmax_out, sample_out, inv_lv, seed, offset, weight);
+    else hipLaunchKernelGGL(wn_cat_loss256_kernel, dim3((unsigned)wgs), dim3(256), 0, s, logits, target, rows, C, gscale,
+                            loss_rows, g_logits, absmax_out, sample_out, inv_lv, seed, offset);
+  } else if (weight) {
+    hipLaunchKernelGGL(wn_cat_loss_weighted_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits,
+                       target, rows, C, gscale, loss_rows, g_logits, absmax_out, weight);
   } else {
     hipLaunchKernelGGL(wn_cat_loss_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits,
                        target, rows, C, gscale, loss_rows, g_logits, absmax_out);
@@ -206,10 +242,26 @@ __device__ __forceinline__ bool wn_logistic_bin(double a, double b, double& hi, 
   lo = up ? -a : b;
   return up;
 }
-__global__ void wn_mix_loss_kernel(const float* pred, const float* y, int64_t rows, int M, int bits,
-                                   int kind, float gscale, float* loss_rows, float* g_pred, float* absmax_out) {
+// WEIGHTED (sample_weight; the factor of wn_catrow.h): dl = -(double)(gscale * w) / lik, the stored loss
+// is w * (float)(-log lik); a row with w == 0 writes its zeros and returns before anything of it is evaluated, so a
+// likelihood that underflows there (section 17's open case) reaches neither the loss, the gradient nor the max-abs.
+template <bool WEIGHTED>
+__device__ __forceinline__ void wn_mix_loss_body(const float* pred, const float* y, int64_t rows, int M, int bits, int kind,
+                                                 float gscale, float* loss_rows, float* g_pred, float* absmax_out,
+                                                 const float* weight) {
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= rows) return;
+  float rw = 1.0f;
+  if constexpr (WEIGHTED) {
+    rw = weight[row];
+    if (rw == 0.f) {
+      loss_rows[row] = 0.f;
+      if (g_pred)
+        for (int k = 0; k < 3 * M; ++k) g_pred[row * 3 * M + k] = 0.f;
+      return;
+    }
+    gscale = wn_w_gscale(gscale, rw);
+  }
   const float* p = pred + row * 3 * M;
   const double yy = (double)y[row];
   double w[WN_MAXMIX], comp[WN_MAXMIX];
@@ -237,7 +289,7 @@ __global__ void wn_mix_loss_kernel(const float* pred, const float* y, int64_t ro
     }
     lik += w[k] * comp[k];
   }
-  loss_rows[row] = (float)(-log(lik));
+  loss_rows[row] = WEIGHTED ? rw * (float)(-log(lik)) : (float)(-log(lik));
   if (!g_pred) return;
   float* g = g_pred + row * 3 * M;
   const double dl = -(double)gscale / lik;                               // dL/dlik
@@ -272,12 +324,23 @@ __global__ void wn_mix_loss_kernel(const float* pred, const float* y, int64_t ro
     wn_absmax_publish(absmax_out, gmax);
   }
 }
+__global__ void wn_mix_loss_kernel(const float* pred, const float* y, int64_t rows, int M, int bits,
+                                   int kind, float gscale, float* loss_rows, float* g_pred, float* absmax_out) {
+  wn_mix_loss_body<false>(pred, y, rows, M, bits, kind, gscale, loss_rows, g_pred, absmax_out, nullptr);
+}
+__global__ void wn_mix_loss_weighted_kernel(const float* pred, const float* y, int64_t rows, int M, int bits,
+                                            int kind, float gscale, float* loss_rows, float* g_pred, float* absmax_out,
+                                            const float* weight) {
+  wn_mix_loss_body<true>(pred, y, rows, M, bits, kind, gscale, loss_rows, g_pred, absmax_out, weight);
+}
 int wn_launch_mix_loss(const float* pred, const float* y, int64_t rows, int M, int bits, int kind,
-                       float gscale, float* loss_rows, float* g_pred, float* absmax_out, hipStream_t s) {
+                       float gscale, float* loss_rows, float* g_pred, float* absmax_out, hipStream_t s, const float* weight) {
   if (rows <= 0) return WN_OK;
   if (M < 1 || M > WN_MAXMIX) { wn_set_error("mix_loss: num_mixtures %d unsupported (max %d)", M, WN_MAXMIX); return WN_E_UNSUPPORTED; }
-  hipLaunchKernelGGL(wn_mix_loss_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, pred,
-                     y, rows, M, bits, kind, gscale, loss_rows, g_pred, absmax_out);
+  if (weight) hipLaunchKernelGGL(wn_mix_loss_weighted_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, pred,
+                                 y, rows, M, bits, kind, gscale, loss_rows, g_pred, absmax_out, weight);
+  else hipLaunchKernelGGL(wn_mix_loss_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, pred,
+                          y, rows, M, bits, kind, gscale, loss_rows, g_pred, absmax_out);
   WN_HIP_CHECK(hipGetLastError());
   return WN_OK;
 }
@@ -341,6 +404,51 @@ int wn_launch_sqdiff_sum(const float* a, const float* b, int64_t n, float scale,
   int nb = wn_blocks(n, 256, 1024);
   hipLaunchKernelGGL(wn_sqdiff_stage1, dim3(nb), dim3(256), 0, s, a, b, n, reinterpret_cast<double*>(scratch));
   hipLaunchKernelGGL(wn_sum_stage2, dim3(1), dim3(256), 0, s, reinterpret_cast<const double*>(scratch), nb, scale, out);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
+// out[0] = scale * sum(w (a - b)^2) / sum(w), 0 when sum(w) == 0: Keras's weighted MeanSquaredError of one step (DESIGN.md
+// section 25).  Numerator and denominator in one pass, the same two-stage double accumulation as above: block i leaves its
+// two partial sums at scratch[i] and scratch[512 + i] (at most 512 blocks: the 1024 doubles of the other reductions' scratch).
+__global__ void wn_wsqdiff_stage1(const float* a, const float* b, const float* w, int64_t n, double* scratch) {
+  __shared__ double sn[256], sd[256];
+  double num = 0.0, den = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float d = a[i] - b[i];
+    const double wi = (double)w[i];
+    num += wi * (double)(d * d);
+    den += wi;
+  }
+  sn[threadIdx.x] = num;
+  sd[threadIdx.x] = den;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) { sn[threadIdx.x] += sn[threadIdx.x + o]; sd[threadIdx.x] += sd[threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { scratch[blockIdx.x] = sn[0]; scratch[512 + blockIdx.x] = sd[0]; }
+}
+__global__ void wn_wsqdiff_stage2(const double* scratch, int nb, float scale, float* out) {
+  __shared__ double sn[256], sd[256];
+  double num = 0.0, den = 0.0;
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) { num += scratch[i]; den += scratch[512 + i]; }
+  sn[threadIdx.x] = num;
+  sd[threadIdx.x] = den;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) { sn[threadIdx.x] += sn[threadIdx.x + o]; sd[threadIdx.x] += sd[threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = sd[0] == 0.0 ? 0.f : (float)((double)scale * sn[0] / sd[0]);
+}
+// scratch: >= 1024 doubles (8 KiB)
+int wn_launch_wsqdiff_mean(const float* a, const float* b, const float* w, int64_t n, float scale, float* out, float* scratch,
+                           hipStream_t s) {
+  int nb = wn_blocks(n, 256, 512);
+  hipLaunchKernelGGL(wn_wsqdiff_stage1, dim3(nb), dim3(256), 0, s, a, b, w, n, reinterpret_cast<double*>(scratch));
+  hipLaunchKernelGGL(wn_wsqdiff_stage2, dim3(1), dim3(256), 0, s, reinterpret_cast<const double*>(scratch), nb, scale, out);
   WN_HIP_CHECK(hipGetLastError());
   return WN_OK;
 }

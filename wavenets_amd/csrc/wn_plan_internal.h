@@ -193,6 +193,9 @@ struct wn_exec {
   uint64_t drop_seed = 0, drop_step = 0;
   // armed by wn_plan_arm_step_sample: the next training step also draws sample_waveform(pred)
   float* step_sample = nullptr; int step_sample_det = 0; uint64_t step_sample_seed = 0, step_sample_off = 0;
+  // armed by wn_plan_arm_row_weights: sample_weight of the (B, T) target rows for wn_train_fwd_bwd / wn_eval_loss; it stays
+  // armed until the caller disarms it
+  const float* row_weights = nullptr; int64_t row_weights_n = 0;
   wnp::WgSchedule wg;           // the cached weight-gradient schedule of the last (B, T) layout it trained
   wnp::GenTable gen;            // the cached block table of the generation chains, for the last batch size it generated
   // side stream: the side spans of the weight-gradient schedule run beside the per-block / skip kernels
@@ -464,6 +467,7 @@ int block_backward(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, 
 struct LossFuse {
   const int32_t* target; float gscale; float* loss_rows; float* g_logits; float* absmax_out;
   float* sample_out; float inv_lv; uint64_t seed, offset;
+  const float* row_weight;     // [rows] sample_weight of the rows, or null (the unweighted instantiation)
   bool done;
 };
 bool loss_fusable(const wn_plan* p, int64_t rows);
@@ -475,7 +479,9 @@ int forward_core(wn_plan* p, const float* params, const float* x, bool prep, con
 // inputs = x[:, :-1], y_true = x[:, 1:]  (src/model.py:319-321)
 int shift_split(const float* x_full, int B, int T, float* inputs, float* y_true, hipStream_t s);
 int loss_stage(wn_plan* p, int B, int T, int global_batch, bool want_grad, float* ws, const WsLayout& L,
-               float* loss_out, float* absmax_out, hipStream_t s, bool fused_done = false);
+               float* loss_out, float* absmax_out, hipStream_t s, bool fused_done = false, const float* row_weight = nullptr);
+// the armed row weights against the rows of a call: WN_E_INVALID with both numbers, before the device is touched
+int row_weights_check(const char* who, const wn_exec& e, int B, int T);
 
 }  // namespace wnp
 

@@ -280,12 +280,13 @@ struct TrainCall {
         lf.sample_out = e.step_sample; lf.inv_lv = 1.0f / (float)(1 << (p->c.bits - 1));
         lf.seed = e.step_sample_seed; lf.offset = e.step_sample_off;
       }
+      lf.row_weight = e.row_weights;                   // armed sample_weight: the weighted instantiation of the epilogue
     }
     rc = forward_core(p, params, inputs, true, cond, B, T, true, ws, L, s, nullptr, fuse ? &lf : nullptr);
     if (rc) return rc;
     if (lf.done && lf.sample_out) e.step_sample = nullptr;     // drawn
     if (e.phase_on) (void)hipEventRecord(e.phase_ev[1], s);
-    rc = loss_stage(p, B, T, global_batch, true, ws, L, loss_out, am_GF(nf - 1), s, lf.done);
+    rc = loss_stage(p, B, T, global_batch, true, ws, L, loss_out, am_GF(nf - 1), s, lf.done, e.row_weights);
     if (rc) return rc;
     if (pred_out) {
       if (p->c.head == WN_HEAD_CATEGORICAL) rc = wn_launch_softmax(ws + L.logits, pred_out, rows, p->Cout, s);
@@ -708,6 +709,7 @@ extern "C" int wn_train_fwd_bwd(wn_plan* p, const float* params, const float* x_
                                 float* loss_out, float* pred_out, float* workspace, int64_t ws_floats,
                                 void* stream) {
   if (!p || !params || !x_full || !workspace || !loss_out || !grads || B < 1 || T < 1) { wn_set_error("train_fwd_bwd: bad arguments"); return WN_E_INVALID; }
+  if (wnp::row_weights_check("train_fwd_bwd", wnp::ex(p), B, T)) return WN_E_INVALID;
   TrainCall c{wnp::ex(p)};
   c.bind(p, params, cond, B, T, grads, workspace, (hipStream_t)stream);
   c.x_full = x_full;

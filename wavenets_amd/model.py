@@ -50,20 +50,33 @@ class MeanSquaredError:
   def reset_state(self):
     self.total, self.count = 0.0, 0
 
-  def update_state(self, y_true, y_pred):
-    self.total += float(self.update_state_device(y_true, y_pred))
+  def update_state(self, y_true, y_pred, sample_weight=None):
+    self.total += float(self.update_state_device(y_true, y_pred, sample_weight=sample_weight))
     self.count += 1
 
   # two-phase form used by train_step / test_step: the reduction is queued behind the step's kernels (one library launch
   # pair, no torch arithmetic) and its value comes back in the step's single device-to-host read.  ``out``: a one-float
   # device view to write into (the gradient bucket's tail in a training step); ``scale`` = 1 / replicas makes the SUM
-  # over the replicas the mean Keras reports.
-  def update_state_device(self, y_true, y_pred, out=None, scale=1.0):
+  # over the replicas the mean Keras reports.  ``sample_weight`` (one weight per element of y_true, or per utterance):
+  # Keras's weighted mean sum(w d^2) / sum(w) of the step, 0 when sum(w) == 0, both sums in the same pass on the device;
+  # the replicas' ratios are then averaged, which is the global weighted mean only when they hold equal sum(w).
+  def update_state_device(self, y_true, y_pred, out=None, scale=1.0, sample_weight=None):
     n = y_true.numel()
     if out is None:
       out = torch.empty(1, dtype=torch.float32, device=y_true.device)
     if self._scratch is None or self._scratch.device != y_true.device:
       self._scratch = torch.empty(2048, dtype=torch.float32, device=y_true.device)
+    if sample_weight is not None:
+      w = torch.as_tensor(sample_weight, dtype=torch.float32, device=y_true.device)
+      if w.numel() != n:
+        if w.dim() != 1 or w.shape[0] != y_true.shape[0]:
+          raise ValueError(f'sample_weight must hold one weight per element of y_true {tuple(y_true.shape)} or one per '
+                           f'utterance (got {tuple(w.shape)})')
+        w = w.reshape(-1, *([1] * (y_true.dim() - 1))).expand(y_true.shape)
+      _lib.check(_lib.lib().wn_weighted_squared_error(_lib.ptr(y_true.contiguous()), _lib.ptr(y_pred.contiguous()),
+                                                      _lib.ptr(w.contiguous()), n, float(scale), _lib.ptr(out),
+                                                      _lib.ptr(self._scratch), _lib.stream_ptr()))
+      return out
     _lib.check(_lib.lib().wn_sum_squared_error(_lib.ptr(y_true.contiguous()), _lib.ptr(y_pred.contiguous()), n,
                                                float(scale) / n, _lib.ptr(out), _lib.ptr(self._scratch),
                                                _lib.stream_ptr()))
@@ -658,8 +671,32 @@ class WaveNet(torch.nn.Module):
       self._drop_armed_step = step
       self._drop_step += 1
 
+  @staticmethod
+  def _check_sample_weight(data, sample_weight):
+    """The shape check of ``sample_weight`` against the batch, on shapes alone: before the model is built and before
+    anything is queued.  Returns the weight as given (None: no weights)."""
+    if sample_weight is None:
+      return None
+    x = data[0] if isinstance(data, (tuple, list)) else data
+    xs, ws = tuple(getattr(x, 'shape', ())), tuple(getattr(sample_weight, 'shape', np.shape(sample_weight)))
+    if len(xs) >= 2:
+      B, T = int(xs[0]), int(xs[1]) - 1
+      if ws not in ((B, T), (B, T, 1), (B,)):
+        raise ValueError(f'sample_weight must have shape ({B}, {T}), ({B}, {T}, 1) or ({B},): one weight per target '
+                         f'x[b, t + 1], or one per utterance (got {ws})')
+    return sample_weight
+
+  def _row_weights(self, sample_weight, B, T):
+    """(B, T) fp32 on the device; a per-utterance (B,) weight is expanded there."""
+    if sample_weight is None:
+      return None
+    w = torch.as_tensor(sample_weight, dtype=torch.float32, device=self._device)
+    if w.dim() == 1:
+      w = w[:, None].expand(B, T)
+    return w.reshape(B, T).contiguous()
+
   def loss_and_grads(self, data, global_batch=None, n_replicas=None, want_pred=False, want_sample=False,
-                     _loss_in_bucket=False, _between=None):
+                     _loss_in_bucket=False, _between=None, sample_weight=None):
     """Forward + loss + backward of this replica's rows (src/model.py:319-335).
 
     Fills ``self.flat_grads`` with d(sum_local l / B_global)/d(theta); returns
@@ -668,7 +705,15 @@ class WaveNet(torch.nn.Module):
     exact-fp32 kernels; a direct caller checks loss[2] and does the same through ``exact_fp32()``).  ``want_sample``: the step also draws
     ``sample_waveform(pred)`` (src/model.py:338) from the logits inside the library -- same draw, no (B,T,C)
     probability tensor -- and returns it in place of pred; when the library cannot (deterministic / more than
-    1024 classes) pred is returned and the caller samples from it."""
+    1024 classes) pred is returned and the caller samples from it.
+
+    ``sample_weight``: fp32 ``(B, T)``, ``(B, T, 1)`` or per utterance ``(B,)``; ``w[b, t]`` weighs the
+    target ``x[b, t + 1]``.  loss = sum w l / global_batch: the normaliser stays the global batch as in
+    ``tf.nn.compute_average_loss``, there is no division by sum w -- scale ``w`` yourself for a mean over the valid samples.
+    A weight of 0 removes the row whatever it holds (inf and NaN included); all ones give the bits of the call without
+    weights.  Negative and non-finite weights are not checked (a plain product).  The draw of ``want_sample`` is made for
+    every row and does not see the weights."""
+    sample_weight = self._check_sample_weight(data, sample_weight)
     self._not_averaged('loss_and_grads')
     x, cond = self._split_inputs(data)
     B, T = x.shape[0], x.shape[1] - 1
@@ -696,12 +741,15 @@ class WaveNet(torch.nn.Module):
     want_pred = want_pred or (want_sample and sample is None)
     pred = torch.empty(B, T, self.spec.out_channels, dtype=torch.float32, device=self._device) if want_pred else None
     self._arm_dropout()
+    weights = self._row_weights(sample_weight, B, T)
 
     def run():
       _lib.check(L.wn_train_fwd_bwd(self._plan, _lib.ptr(self.flat_params), _lib.ptr(x), _lib.ptr(cond), B, T,
                                     int(global_batch), int(n_replicas), _lib.ptr(self.flat_grads),
                                     _lib.ptr(loss), _lib.ptr(pred), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
     try:
+      if weights is not None:
+        _lib.check(L.wn_plan_arm_row_weights(self._plan, _lib.ptr(weights), B * T))
       if _between is None:
         run()
         out = (sample if sample is not None else self.sample_waveform(pred)) if want_sample else pred
@@ -719,26 +767,34 @@ class WaveNet(torch.nn.Module):
     finally:
       if sample is not None:
         L.wn_plan_arm_step_sample(self._plan, None, 0, 0, 0)      # never leave a stale pointer armed
+      if weights is not None:
+        L.wn_plan_arm_row_weights(self._plan, None, 0)
     return loss, out, x[:, 1:, :]
 
-  def train_step(self, data):
+  def train_step(self, data, sample_weight=None):
     """src/model.py:309-348.  Data-parallel: the flat gradient (and the step's scalars) are
     SUM-all-reduced over RCCL before the (replicated, deterministic) optimizer step.
 
     Range guard: the split-precision kernels need |activation| < 65504.  The step's range flag rides in the bucket's
     tail through the all-reduce, the optimizer kernel skips the update on every replica when it is set, and the step is
     then repeated here with the exact-fp32 kernels (same dropout mask, same optimizer iteration); ``train_guard_trips``
-    counts those repeats (a tripped step costs a second, ~2.7x slower one)."""
+    counts those repeats (a tripped step costs a second, ~2.7x slower one).
+
+    ``sample_weight``: Keras's third element of the step's data, semantics as in ``loss_and_grads``.  The step keeps its
+    launches (the loss kernels take the factor per row).  A compiled ``MeanSquaredError`` becomes Keras's weighted mean
+    sum w (y - sample)^2 / sum w (0 when sum w == 0); under data parallelism the replicas' ratios are averaged."""
+    sample_weight = self._check_sample_weight(data, sample_weight)
     if self.optimizer is None:
       raise RuntimeError('compile(optimizer=...) first')
     self._not_averaged('train_step')
-    lv, pending, y_true, sample = self._train_step_once(data)
+    wkw = {} if sample_weight is None else {'sample_weight': sample_weight}
+    lv, pending, y_true, sample = self._train_step_once(data, sample_weight)
     if lv[2] > 0:                                    # tripped on some replica -> on all of them after the SUM
       self.train_guard_trips += 1
       self.optimizer.iterations -= 1
       self._drop_step -= 1 if self.dropout > 0 else 0
       with self.exact_fp32():
-        lv, pending, y_true, sample = self._train_step_once(data)
+        lv, pending, y_true, sample = self._train_step_once(data, sample_weight)
     for m, v in zip(pending, lv[3:]):
       m.commit(v)
     for metric in self.metrics:
@@ -747,7 +803,7 @@ class WaveNet(torch.nn.Module):
       elif metric.name == 'reg_loss':
         metric.update_state(lv[1])
       elif not hasattr(metric, 'update_state_device'):
-        metric.update_state(y_true, sample)
+        metric.update_state(y_true, sample, **wkw)
     return {m.name: m.result() for m in self.metrics}
 
   def _mirror(self, vec):
@@ -758,7 +814,7 @@ class WaveNet(torch.nn.Module):
     self._log_mirror.copy_(vec, non_blocking=True)
     self._log_event.record()
 
-  def _train_step_once(self, data):
+  def _train_step_once(self, data, sample_weight=None):
     """One pass of the step.  The scalars a step reports -- {loss, reg_loss, range flag, device-reduced metrics} -- live in
     the gradient bucket's tail, each already scaled so that the SUM over the replicas is the reported value.
 
@@ -781,10 +837,11 @@ class WaveNet(torch.nn.Module):
     n = self.flat_params.numel()
     tail = self._grad_bucket[n:]
     nt = 3 + len(dev_metrics)
+    wkw = {} if sample_weight is None else {'sample_weight': sample_weight}      # a metric gets the keyword only with weights
 
     def queue_metrics(sample, y_true):
       for i, m in enumerate(dev_metrics):
-        m.update_state_device(y_true, sample, out=tail[3 + i:4 + i], scale=1.0 / world)
+        m.update_state_device(y_true, sample, out=tail[3 + i:4 + i], scale=1.0 / world, **wkw)
 
     if early:
       def between(loss, sample, y_true):
@@ -794,12 +851,12 @@ class WaveNet(torch.nn.Module):
           vec = vec.clone()
           dp.allreduce_bucket(vec)
         self._mirror(vec)
-      loss, sample, y_true = self.loss_and_grads(data, want_sample=want_metric, _loss_in_bucket=True, _between=between)
+      loss, sample, y_true = self.loss_and_grads(data, want_sample=want_metric, _loss_in_bucket=True, _between=between, **wkw)
       self.optimizer.clip_local_gradients(self)         # clip_before_reduce only; in place, see the note below
       dp.allreduce_bucket(self._grad_bucket)            # gradients + tail; no-op without a process group
       self.optimizer.apply_gradients(self, skip_flag=tail[2:3])
     else:
-      loss, sample, y_true = self.loss_and_grads(data, want_sample=want_metric, _loss_in_bucket=True)
+      loss, sample, y_true = self.loss_and_grads(data, want_sample=want_metric, _loss_in_bucket=True, **wkw)
       queue_metrics(sample, y_true)
       # Adam(clip_before_reduce=True) clips THIS replica's gradient in place ahead of the SUM (one path, with or without a
       # process group; the tail behind the gradient is not touched).  In place is safe under the range guard: a tripped
@@ -811,12 +868,16 @@ class WaveNet(torch.nn.Module):
     self._log_event.synchronize()
     return self._log_mirror.tolist(), dev_metrics, y_true, sample
 
-  def test_step(self, data):
+  def test_step(self, data, sample_weight=None):
     """src/model.py:362-391 (range guard as in train_step: a tripped pass is repeated with the exact-fp32 kernels and
-    counted in ``test_guard_trips``)."""
+    counted in ``test_guard_trips``).  ``sample_weight``: as in ``train_step`` -- loss = sum w l / global_batch, a compiled
+    ``MeanSquaredError`` the weighted mean."""
     from . import dp
+    sample_weight = self._check_sample_weight(data, sample_weight)
     x, cond = self._split_inputs(data)
     B, T = x.shape[0], x.shape[1] - 1
+    weights = self._row_weights(sample_weight, B, T)
+    wkw = {} if weights is None else {'sample_weight': weights}
     world = self._world()
     L = _lib.lib()
     ws = self._workspace('fwd', L.wn_plan_workspace_floats(self._plan, B, T, 0))
@@ -827,14 +888,20 @@ class WaveNet(torch.nn.Module):
     pred = torch.empty(B, T, self.spec.out_channels, dtype=torch.float32, device=self._device) if want_metric else None
 
     def once():
-      _lib.check(L.wn_eval_loss(self._plan, _lib.ptr(self.flat_params), _lib.ptr(x), _lib.ptr(cond), B, T,
-                                B * world, _lib.ptr(vec), _lib.ptr(pred), _lib.ptr(ws), ws.numel(),
-                                _lib.stream_ptr()))
+      try:
+        if weights is not None:
+          _lib.check(L.wn_plan_arm_row_weights(self._plan, _lib.ptr(weights), B * T))
+        _lib.check(L.wn_eval_loss(self._plan, _lib.ptr(self.flat_params), _lib.ptr(x), _lib.ptr(cond), B, T,
+                                  B * world, _lib.ptr(vec), _lib.ptr(pred), _lib.ptr(ws), ws.numel(),
+                                  _lib.stream_ptr()))
+      finally:
+        if weights is not None:
+          L.wn_plan_arm_row_weights(self._plan, None, 0)
       sample = self.sample_waveform(pred) if want_metric else None
       # as in train_step: device-side metric reductions into the same vector, ONE collective (loss sums over the replicas;
       # reg_loss unused; flag: any replica; metrics: replica means), ONE device-to-host read
       for i, m in enumerate(dev_metrics):
-        m.update_state_device(x[:, 1:, :], sample, out=vec[3 + i:4 + i], scale=1.0 / world)
+        m.update_state_device(x[:, 1:, :], sample, out=vec[3 + i:4 + i], scale=1.0 / world, **wkw)
       dp.allreduce_bucket(vec)
       return vec.tolist(), sample
     lv, sample = once()
@@ -850,14 +917,15 @@ class WaveNet(torch.nn.Module):
       elif metric.name == 'reg_loss':
         continue
       elif not hasattr(metric, 'update_state_device'):
-        metric.update_state(x[:, 1:, :], sample)
+        metric.update_state(x[:, 1:, :], sample, **wkw)
     return {m.name: m.result() for m in self.metrics if m.name != 'reg_loss'}
 
   # ------------------------------------------------------------------ autograd
   def differentiable(self, inputs, training=False, output='probs'):
     """The network as one ``torch.autograd`` node: returns ``(B, T, C_out)`` with a ``grad_fn``, for losses the training
-    step does not have built in (masks, weights, label smoothing, distillation, a loss on the expected sample, a gradient
-    at the input waveform or the condition).  DESIGN.md section 20.
+    step does not have built in (label smoothing, distillation, a loss on the expected sample, a gradient
+    at the input waveform or the condition).  DESIGN.md section 20.  Masks and per-sample weights do not need it: ``train_step``,
+    ``test_step`` and ``loss_and_grads`` take ``sample_weight`` inside the fused step.
 
     ``output='probs'`` is what ``call()`` returns, ``'logits'`` the pre-softmax head output; for the mixture heads both
     are the same linear parameters.  A loss of the form ``-log p[target]`` on ``'probs'`` meets ``0 * inf`` where a
