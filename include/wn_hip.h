@@ -142,6 +142,10 @@ int wn_prof_read(wn_plan* p, int32_t* launches, float* avg_ms);
  *          dropout rate is above 0; with dropout off it is WN_E_INVALID, like every other absent region */
 int wn_debug_ws_region(const wn_plan* p, int32_t B, int32_t T, int32_t what, int32_t idx, int64_t* off,
                        int64_t* len);
+/* the same for the INFERENCE workspace of (B, T) (wn_forward, wn_eval_loss, wn_score): what = 5 the logits (B * T * C_out;
+ * untouched by a wn_score pass that formed the loss in the last conv's epilogue) | 12 the per-row losses (B * T).
+ * Any other `what` is WN_E_INVALID. */
+int wn_debug_eval_region(const wn_plan* p, int32_t B, int32_t T, int32_t what, int64_t* off, int64_t* len);
 /* the whole residual-block stack of a forward pass: one event pair per pass from the first block launch to
  * the end of the folded skip contraction = t_stack_fwd of SURVEY.md 8(d); read returns passes and the average */
 int wn_stack_prof_enable(wn_plan* p, int32_t max_passes);
@@ -200,6 +204,28 @@ int wn_vjp(wn_plan* p, const float* params, const float* x, const float* cond, i
 int wn_eval_loss(wn_plan* p, const float* params, const float* x_full, const float* cond,
                  int32_t B, int32_t T, int32_t global_batch, float* loss_out, float* pred_out,
                  float* workspace, int64_t ws_floats, void* stream);
+
+/* ---- per-utterance negative log-likelihoods in one evaluation pass (WaveNet.score) ----
+ * Inputs and targets as wn_eval_loss: inputs = x[:, :-1], targets = prepare_target(x[:, 1:]); the inference forward (no
+ * dropout) on the INFERENCE workspace, wn_plan_workspace_floats(p, B, T, 0).  l[b,t] is the per-row loss exactly as loss_fn
+ * defines it for the head (the clipped cross entropy, or the mixture negative log-likelihood), in nats: no 1 / global_batch,
+ * no L2 term.
+ *   nll_out    B floats:   sum_t w[b,t] l[b,t]
+ *   weight_out B floats:   sum_t w[b,t], exactly T when no weights are armed; NULL = not wanted
+ *   rows_out   B*T floats: w[b,t] l[b,t] as the loss kernel stored it; NULL = not wanted
+ *   flag_out   1 float:    the range flag, as loss_out[2] of wn_eval_loss (1: repeat the call with the exact-fp32 kernels)
+ * Armed row weights (wn_plan_arm_row_weights) apply as they do to wn_eval_loss: rows are stored weighted, w == 0 is a select
+ * (a row whose own loss is inf or NaN contributes +0), a row count other than B * T is WN_E_INVALID naming both numbers.
+ * Each utterance is summed by one workgroup in double, without atomics, in an order that depends on T alone: nll_out[b] is
+ * a function of utterance b's rows only, bit for bit, whatever B is and whatever the other rows hold.
+ * A 256-class categorical head whose last conv the streamed kernel takes forms the rows in that conv's epilogue
+ * (evaluation form: no logits and no d loss / d logits are written); every other head and shape, and the exact-fp32 mode,
+ * run the standalone loss kernels on the logits.
+ * WN_E_INVALID (checked before the device is touched): a null plan / params / x_full / nll_out / flag_out / workspace,
+ * cond null on a conditioned plan, B < 1 or T < 1, a workspace smaller than the inference size (message: both sizes). */
+int wn_score(wn_plan* p, const float* params, const float* x_full, const float* cond, int32_t B, int32_t T,
+             float* nll_out, float* weight_out, float* rows_out, float* flag_out,
+             float* workspace, int64_t ws_floats, void* stream);
 
 /* ---- optimizer.apply_gradients with Adam(lr, clipnorm), train.py:225-226, model.py:336 ----
  * Keras Adam: alpha = lr*sqrt(1-b2^t)/(1-b1^t); p -= alpha*m/(sqrt(v)+eps); per-tensor
@@ -370,7 +396,7 @@ int wn_sum_squared_error(const float* a, const float* b, int64_t n, float scale,
 /* ---- sample_weight of a training / evaluation step (Keras's train_step contract) ----
  * w: rows = B * T device floats over the target rows, w[b * T + t] belongs to the target x_full[b][t + 1].  Arms the
  * calling thread's execution state; it stays armed until w == NULL disarms it (the caller owns the buffer: disarm before
- * freeing it).  While armed, wn_train_fwd_bwd and wn_eval_loss weigh their rows; they return WN_E_INVALID when
+ * freeing it).  While armed, wn_train_fwd_bwd, wn_eval_loss and wn_score weigh their rows; they return WN_E_INVALID when
  * rows != B * T of the call, checked before the device is touched, the message naming both numbers.  wn_vjp, wn_forward*,
  * wn_loss_fn, generation and the optimizer ignore it.  With wn_plan_set_train_phases the weights are read in phase 1 only.
  *   loss = sum_{b,t} w[b,t] l[b,t] / global_batch (+ the L2 term, unchanged).  The normaliser stays global_batch, as in

@@ -87,6 +87,7 @@ _SIGS = {
     'wn_prof_read': (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     'wn_debug_ws_region': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64)]),
+    'wn_debug_eval_region': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'wn_stack_prof_enable': (C.c_int, [_P, C.c_int32]),
     'wn_stack_prof_read': (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     'wn_stack_prof_read_foldprep': (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
@@ -98,6 +99,7 @@ _SIGS = {
                                    _P, C.c_int64, _P]),
     'wn_vjp': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P]),
     'wn_eval_loss': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P]),
+    'wn_score': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
     'wn_adam_step': (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                C.c_float, _P, _P]),
     'wn_adam_step_guarded': (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,

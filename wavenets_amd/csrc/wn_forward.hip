@@ -303,7 +303,8 @@ int forward_core(wn_plan* p, const float* params, const float* x, bool prep, con
     const ConvInfo& c = p->finals[i];
     const bool last = (i + 1 == p->finals.size());
     float* dst = last ? ws + L.logits : ws + L.HA[i];
-    // training pass of a 256-class categorical head: the loss is this conv's epilogue (no logits tensor)
+    // training pass of a 256-class categorical head: the loss is this conv's epilogue (no logits tensor); a scoring pass
+    // (lf->eval) takes the evaluation form of it: the loss rows and nothing else
     if (last && lf && loss_fusable(p, rows) && wn_gemm_planes16s_supported(c.cout, hc, 1, hc, c.cout) &&
         (int64_t)rows * hc * 4 < ((int64_t)1 << 32)) {
       WnGemmPlanesArgs ga;
@@ -311,7 +312,7 @@ int forward_core(wn_plan* p, const float* params, const float* x, bool prep, con
       ga.z = hin; ga.plane_stride = 0; ga.ld = hc; ga.plane_k = hc; ga.nplanes = 1;
       ga.w16 = fragbase + c.frag16; ga.bias = params + p->tensors[c.bias_t].off; ga.act = WN_ACT_LINEAR;
       ga.y = lf->g_logits; ga.ldy = c.cout; ga.N = c.cout; ga.B = B; ga.T = T; ga.absmax_out = lf->absmax_out;
-      ga.cat_loss = 1; ga.target = lf->target; ga.gscale = lf->gscale; ga.loss_rows = lf->loss_rows;
+      ga.cat_loss = lf->eval ? 2 : 1; ga.target = lf->target; ga.gscale = lf->gscale; ga.loss_rows = lf->loss_rows;
       ga.sample_out = lf->sample_out; ga.inv_lv = lf->inv_lv; ga.seed = lf->seed; ga.offset = lf->offset;
       ga.row_weight = lf->row_weight;
       rc = wn_launch_gemm_planes16s(ga, s);
@@ -368,6 +369,14 @@ int loss_stage(wn_plan* p, int B, int T, int global_batch, bool want_grad, float
   if (fused_done) return wn_launch_sum(ws + L.loss_rows, rows, gscale, loss_out, ws + L.sum_scratch, s);
   // deferred weight gradients read d loss / d logits from GF.back(): written there directly (no 131 MB copy)
   float* g_logits = want_grad ? ws + L.GF.back() : nullptr;
+  rc = loss_rows_stage(p, rows, gscale, g_logits, want_grad, ws, L, absmax_out, s, row_weight);
+  if (rc) return rc;
+  return wn_launch_sum(ws + L.loss_rows, rows, gscale, loss_out, ws + L.sum_scratch, s);
+}
+
+int loss_rows_stage(wn_plan* p, int64_t rows, float gscale, float* g_logits, bool want_grad, float* ws, const WsLayout& L,
+                    float* absmax_out, hipStream_t s, const float* row_weight) {
+  int rc;
   if (p->c.head == WN_HEAD_CATEGORICAL) {
     rc = wn_launch_quantize(ws + L.yt, reinterpret_cast<int32_t*>(ws + L.target), rows, p->c.bits, s);
     if (rc) return rc;
@@ -381,8 +390,7 @@ int loss_stage(wn_plan* p, int B, int T, int global_batch, bool want_grad, float
     rc = wn_launch_mix_loss(ws + L.logits, ws + L.yt, rows, p->c.num_mixtures, p->c.bits,
                             p->c.head == WN_HEAD_LOGISTIC ? 1 : 2, gscale, ws + L.loss_rows, g_logits, absmax_out, s, row_weight);
   }
-  if (rc) return rc;
-  return wn_launch_sum(ws + L.loss_rows, rows, gscale, loss_out, ws + L.sum_scratch, s);
+  return rc;
 }
 
 int row_weights_check(const char* who, const wn_exec& e, int B, int T) {
@@ -458,4 +466,52 @@ extern "C" int wn_eval_loss(wn_plan* p, const float* params, const float* x_full
     WN_HIP_CHECK(hipMemcpyAsync(pred_out, workspace + L.logits, rows * p->Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
   return WN_OK;
+}
+
+// WaveNet.score: the evaluation pass of wn_eval_loss up to the row losses, then one workgroup per utterance.  A 256-class
+// head the streamed kernel takes forms the rows in the last conv's epilogue (evaluation form: LossFuse.eval); everything
+// else runs the standalone loss kernel on the logits, without a gradient, as wn_eval_loss does.
+extern "C" int wn_score(wn_plan* p, const float* params, const float* x_full, const float* cond, int32_t B, int32_t T,
+                        float* nll_out, float* weight_out, float* rows_out, float* flag_out,
+                        float* workspace, int64_t ws_floats, void* stream) {
+  if (!p) { wn_set_error("score: null plan"); return WN_E_INVALID; }
+  if (!params || !x_full || !nll_out || !flag_out || !workspace) {
+    wn_set_error("score: null %s", !params ? "params" : !x_full ? "x_full" : !nll_out ? "nll_out" : !flag_out ? "flag_out" : "workspace");
+    return WN_E_INVALID;
+  }
+  if (p->c.cond_inputs > 0 && !cond) { wn_set_error("score: the plan is conditioned (%d inputs) and cond is null", p->c.cond_inputs); return WN_E_INVALID; }
+  if (B < 1 || T < 1) { wn_set_error("score: B = %d, T = %d: both must be at least 1", (int)B, (int)T); return WN_E_INVALID; }
+  if (row_weights_check("score", wnp::ex(p), B, T)) return WN_E_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  const WsLayout L = make_layout(p, B, T, false);
+  if (ws_floats < L.total) {
+    wn_set_error("score: workspace too small (%lld < %lld floats)", (long long)ws_floats, (long long)L.total);
+    return WN_E_INVALID;
+  }
+  const int64_t rows = (int64_t)B * T;
+  const float* rw = wnp::ex(p).row_weights;
+  float* inputs = workspace + L.probs;                   // (as wn_eval_loss: the probs region is free in this pass)
+  int rc = shift_split(x_full, B, T, inputs, workspace + L.yt, s);
+  if (rc) return rc;
+  LossFuse lf;
+  memset(&lf, 0, sizeof(lf));
+  const bool fuse = loss_fusable(p, rows);
+  if (fuse) {
+    rc = wn_launch_quantize(workspace + L.yt, reinterpret_cast<int32_t*>(workspace + L.target), rows, p->c.bits, s);
+    if (rc) return rc;
+    lf.target = reinterpret_cast<const int32_t*>(workspace + L.target);
+    lf.loss_rows = workspace + L.loss_rows;
+    lf.row_weight = rw;
+    lf.eval = true;
+  }
+  rc = forward_core(p, params, inputs, true, cond, B, T, false, workspace, L, s, nullptr, fuse ? &lf : nullptr);
+  if (rc) return rc;
+  if (!lf.done) {
+    rc = loss_rows_stage(p, rows, 1.0f, nullptr, false, workspace, L, nullptr, s, rw);
+    if (rc) return rc;
+  }
+  rc = wn_launch_score_reduce(workspace + L.loss_rows, rw, B, T, nll_out, weight_out, s);
+  if (rc) return rc;
+  if (rows_out) WN_HIP_CHECK(hipMemcpyAsync(rows_out, workspace + L.loss_rows, rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return wn_launch_guard_flag(workspace + L.fwd_absmax, WN_RANGE_LIMIT, wn_debug_get(1) != 1, flag_out, s);
 }

@@ -53,6 +53,9 @@ struct GS {
 // bound at 105 us for 268 MB) and needs the logits written (131 MB) and read back (131 MB).
 // -4: -3 with the rows' sample_weight (a.row_weight): the weight is loaded where the target is and enters
 // through the factor of wn_catrow.h.  An instantiation of its own, so that a step without weights launches -3 as it was.
+// -5 / -6: the evaluation form of -3 / -4 (wn_score): soft-max, the clip sum and the loss row, the
+// same expressions in the same order, and nothing else -- no softmax - onehot, no store_tile of the accumulators, no max-abs
+// publication, no draw; a.y, a.absmax_out, a.gscale and a.sample_out are not looked at.
 template <int RT, int JT_, int ACT, bool SHIFT = false>
 __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesArgs a) {
   using C = GS<RT, JT_>;
@@ -198,18 +201,20 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
 
     // ---- bias, activation, range guard, staged row stores ----
     const unsigned voff = (unsigned)(lane >> 3) * (unsigned)(a.ldy * 4) + (unsigned)(lane & 7) * 16u;
-    if constexpr (ACT == -3 || ACT == -4) {
-      constexpr bool WEIGHTED = ACT == -4;
+    if constexpr (ACT <= -3) {
+      constexpr bool WEIGHTED = ACT == -4 || ACT == -6;
+      constexpr bool EVAL = ACT <= -5;
       static_assert(RT == 1 && JT == 8, "the loss epilogue is the 256-class form");
       const int rows_valid = live ? max(0, min(32, a.T - t0)) : 0;
       const bool rok = xok[0];
       const int64_t row = row0 + tl;
       int tgt = rok ? a.target[row] : 0;
       tgt = wn_ce_target(tgt, 256);
-      float rw = 1.0f, gscale = a.gscale;
+      float rw = 1.0f;
+      [[maybe_unused]] float gscale = EVAL ? 0.f : a.gscale;
       if constexpr (WEIGHTED) {
         rw = rok ? a.row_weight[row] : 0.f;
-        gscale = wn_w_gscale(gscale, rw);
+        if constexpr (!EVAL) gscale = wn_w_gscale(gscale, rw);
       }
       auto xch = [](float v) { return __shfl_xor(v, 32); };       // the partner lane holds the row's other 128 classes
       // logits = acc + bias; row maximum
@@ -239,7 +244,7 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
       const float inv = 1.0f / z;
       // ---- sample_waveform(pred) of the row: inverse CDF over the classes in order (src/model.py:405-411), the draw
       // wn_draw_cat_row makes from these probabilities up to the rounding of its running sums ----
-      if (a.sample_out) {
+      if (!EVAL && a.sample_out) {
         uint32_t rnd[4];
         wn_philox((uint64_t)row, a.offset, a.seed, rnd);
         const float thr = wn_u01(rnd[0]) * (z * inv);     // target mass in probability units (total = sum of q)
@@ -302,14 +307,20 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float q = acc[0][j][r] * inv;
-          acc[0][j][r] = q;
+          if constexpr (!EVAL) acc[0][j][r] = q;
           S += wn_ce_clip(q);
-          if (wn_ce_inside(q)) A += q;
+          if constexpr (!EVAL) { if (wn_ce_inside(q)) A += q; }
           if (32 * j + 8 * (r >> 2) + 4 * h + (r & 3) == tgt) qt = q;
         }
       S += xch(S);
-      A += xch(A);
+      if constexpr (!EVAL) A += xch(A);
       qt += xch(qt);                                      // (the other half contributes 0)
+      if constexpr (EVAL) {
+        // the evaluation form ends here: pt as WnCeRow takes it, the row as the training form stores it
+        const float pt = wn_ce_clip(qt);
+        if (rok && h == 0) a.loss_rows[row] = WEIGHTED ? wn_w_loss(rw, wn_ce_loss(pt, S)) : wn_ce_loss(pt, S);
+        continue;
+      }
       const WnCeRow ce(S, A, qt);
       if (rok && h == 0) a.loss_rows[row] = WEIGHTED ? wn_w_loss(rw, wn_ce_loss(ce.pt, S)) : wn_ce_loss(ce.pt, S);
       // ---- gradient w.r.t. the logits, in place ----
@@ -370,7 +381,7 @@ __global__ __launch_bounds__(256, 2) void wn_gemm_planes16s_kernel(WnGemmPlanesA
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the look-ahead k-steps land before the LDS is given back
-  if (a.absmax_out) {
+  if (ACT > -5 && a.absmax_out) {
     wmax = wn_wave_absmax_bits(wmax);
     if (lane == 0) { if (ACT == -2 || ACT == -3 || ACT == -4) wn_absmax_publish(a.absmax_out, wmax); else wn_absmax_publish_any(a.absmax_out, wmax); }
   }
@@ -413,8 +424,10 @@ int wn_launch_gemm_planes16s(const WnGemmPlanesArgs& a, hipStream_t s) {
       default: WN_GS_LAUNCH_S(-1); break;
     }
   } else if (a.cat_loss) {
-    if (a.N != 256 || a.bwd || !a.target || !a.loss_rows || !a.y) { wn_set_error("gemm_planes16s: the loss epilogue is the 256-class forward form"); return WN_E_UNSUPPORTED; }
-    if (a.row_weight) WN_GS_LAUNCH(1, 8, -4);
+    const bool eval = a.cat_loss == 2;                   // wn_score: the rows only, nothing is written through a.y
+    if (a.N != 256 || a.bwd || !a.target || !a.loss_rows || (!eval && !a.y)) { wn_set_error("gemm_planes16s: the loss epilogue is the 256-class forward form"); return WN_E_UNSUPPORTED; }
+    if (eval) { if (a.row_weight) WN_GS_LAUNCH(1, 8, -6); else WN_GS_LAUNCH(1, 8, -5); }
+    else if (a.row_weight) WN_GS_LAUNCH(1, 8, -4);
     else WN_GS_LAUNCH(1, 8, -3);
   } else if (a.bwd) {
     if (a.N == 256) WN_GS_LAUNCH(1, 8, -2);

@@ -95,7 +95,9 @@ struct WnGemmPlanesArgs {
   // cat_loss != 0 (N == 256 == classes, forward form): the epilogue is the categorical loss instead of a store of the
   // logits -- Keras sparse CE on clipped probabilities per row (src/model.py:515-516) into loss_rows, d loss / d logits
   // (* gscale) into y, its running max-abs into absmax_out (a gradient slot), and optionally the step's
-  // sample_waveform(pred) draw (src/model.py:338,405-411) into sample_out: the (rows, 256) logits never reach HBM
+  // sample_waveform(pred) draw (src/model.py:338,405-411) into sample_out: the (rows, 256) logits never reach HBM.
+  // cat_loss == 2: the evaluation form (wn_score): soft-max, clip sum and the loss row only -- y, absmax_out, gscale and
+  // sample_out are not looked at, nothing but loss_rows is written
   int32_t cat_loss;
   const int32_t* target;   // [rows] class indices
   float gscale;
@@ -408,6 +410,10 @@ int wn_launch_mix_loss(const float* pred, const float* y, int64_t rows, int M, i
                        float gscale, float* loss_rows, float* g_pred, float* absmax_out, hipStream_t s,
                        const float* weight = nullptr);
 int wn_launch_sum(const float* v, int64_t n, float scale, float* out, float* scratch, hipStream_t s);
+// per-utterance sums of the (B, T) row losses as the loss kernels stored them (weighted rows are stored weighted):
+// nll[b] = sum_t rows[b][t], wsum[b] = sum_t weight[b][t] (or (float)T without weights; wsum may be null).  One workgroup per
+// utterance, double accumulation, no atomics: the order of summation depends on T alone (wn_score)
+int wn_launch_score_reduce(const float* rows, const float* weight, int B, int T, float* nll, float* wsum, hipStream_t s);
 int wn_launch_sqdiff_sum(const float* a, const float* b, int64_t n, float scale, float* out, float* scratch, hipStream_t s);
 // out[0] = scale * sum(w (a - b)^2) / sum(w), 0 when sum(w) == 0; scratch as for wn_launch_sum
 int wn_launch_wsqdiff_mean(const float* a, const float* b, const float* w, int64_t n, float scale, float* out, float* scratch,

@@ -382,6 +382,55 @@ int wn_launch_sum(const float* v, int64_t n, float scale, float* out, float* scr
   return WN_OK;
 }
 
+// Per-utterance sums of a scoring pass (wn_score): workgroup b owns utterance b.  Thread i adds the rows
+// t = i, i + 256, ... of its utterance in that order, in double -- the rows as the loss kernels stored them, weighted rows
+// already weighted, so the first sum is sum_t w l; the second is sum_t w from the weight buffer when one is armed -- then the
+// tree of wn_sum_stage1 over the 256 partial sums, and one store as float.  No atomics, nothing shared between
+// workgroups: the order of summation depends on T alone, so nll[b] is a function of utterance b's rows only, bit for bit.
+__global__ __launch_bounds__(256) void wn_score_reduce_kernel(const float* rows, const float* weight, int T, float* nll,
+                                                              float* wsum) {
+  __shared__ double sl[256], sw[256];
+  const int64_t base = (int64_t)blockIdx.x * T;
+  double l = 0.0, w = 0.0;
+  int t = threadIdx.x;
+  // eight of a thread's rows requested before the first is added (8 workgroups at the configs[1] batch: one load per
+  // trip would leave the kernel waiting for memory 63 times in a row); the adds keep the order t, t + 256, ...
+  for (; t + 7 * 256 < T; t += 8 * 256) {
+    float r[8], q[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      r[k] = rows[base + t + 256 * k];
+      q[k] = weight ? weight[base + t + 256 * k] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      l += (double)r[k];
+      w += (double)q[k];
+    }
+  }
+  for (; t < T; t += 256) {
+    l += (double)rows[base + t];
+    if (weight) w += (double)weight[base + t];
+  }
+  sl[threadIdx.x] = l;
+  sw[threadIdx.x] = w;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) { sl[threadIdx.x] += sl[threadIdx.x + o]; sw[threadIdx.x] += sw[threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    nll[blockIdx.x] = (float)sl[0];
+    if (wsum) wsum[blockIdx.x] = weight ? (float)sw[0] : (float)T;
+  }
+}
+int wn_launch_score_reduce(const float* rows, const float* weight, int B, int T, float* nll, float* wsum, hipStream_t s) {
+  if (B <= 0 || T <= 0) return WN_OK;
+  hipLaunchKernelGGL(wn_score_reduce_kernel, dim3((unsigned)B), dim3(256), 0, s, rows, weight, T, nll, wsum);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
 // out[0] = scale * sum((a - b)^2): tf.keras.metrics.MeanSquaredError(y_true, sample) of a step (src/model.py:346,
 // train.py:227) with scale = 1 / (n * replicas); same two-stage double accumulation as wn_launch_sum
 __global__ void wn_sqdiff_stage1(const float* a, const float* b, int64_t n, double* scratch) {

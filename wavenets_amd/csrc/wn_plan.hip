@@ -967,6 +967,21 @@ extern "C" int wn_debug_ws_region(const wn_plan* p, int32_t B, int32_t T, int32_
   return WN_OK;
 }
 
+// the inference layout (wn_forward, wn_eval_loss, wn_score): the two regions that tell which loss path a pass took
+extern "C" int wn_debug_eval_region(const wn_plan* p, int32_t B, int32_t T, int32_t what, int64_t* off, int64_t* len) {
+  if (!p || !off || !len || B < 1 || T < 1) return WN_E_INVALID;
+  const WsLayout L = make_layout(p, B, T, false);
+  const int64_t rows = (int64_t)B * T;
+  switch (what) {
+    case 5: *off = L.logits; *len = rows * p->Cout; return WN_OK;
+    case 12: *off = L.loss_rows; *len = rows; return WN_OK;
+    default: break;
+  }
+  *off = -1; *len = 0;
+  wn_set_error("eval_region: no such region (%d)", what);
+  return WN_E_INVALID;
+}
+
 // forward range guard of an inference call: reads nothing back, only tells where the slot is
 extern "C" int64_t wn_plan_range_slot(const wn_plan* p, int32_t B, int32_t T, int32_t training) {
   if (!p || B < 1 || T < 1) return -1;

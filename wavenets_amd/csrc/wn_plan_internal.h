@@ -193,7 +193,7 @@ struct wn_exec {
   uint64_t drop_seed = 0, drop_step = 0;
   // armed by wn_plan_arm_step_sample: the next training step also draws sample_waveform(pred)
   float* step_sample = nullptr; int step_sample_det = 0; uint64_t step_sample_seed = 0, step_sample_off = 0;
-  // armed by wn_plan_arm_row_weights: sample_weight of the (B, T) target rows for wn_train_fwd_bwd / wn_eval_loss; it stays
+  // armed by wn_plan_arm_row_weights: sample_weight of the (B, T) target rows for wn_train_fwd_bwd / wn_eval_loss / wn_score; it stays
   // armed until the caller disarms it
   const float* row_weights = nullptr; int64_t row_weights_n = 0;
   wnp::WgSchedule wg;           // the cached weight-gradient schedule of the last (B, T) layout it trained
@@ -469,6 +469,9 @@ struct LossFuse {
   float* sample_out; float inv_lv; uint64_t seed, offset;
   const float* row_weight;     // [rows] sample_weight of the rows, or null (the unweighted instantiation)
   bool done;
+  // wn_score: the evaluation form of the epilogue (<1, 8, -5> / <1, 8, -6>): the loss rows and nothing else -- g_logits,
+  // absmax_out, gscale and the draw are not used
+  bool eval;
 };
 bool loss_fusable(const wn_plan* p, int64_t rows);
 BlockPtrs block_ptrs(const wn_plan* p, int b, const float* params, const float* fragbase, int B, int T);
@@ -480,6 +483,10 @@ int forward_core(wn_plan* p, const float* params, const float* x, bool prep, con
 int shift_split(const float* x_full, int B, int T, float* inputs, float* y_true, hipStream_t s);
 int loss_stage(wn_plan* p, int B, int T, int global_batch, bool want_grad, float* ws, const WsLayout& L,
                float* loss_out, float* absmax_out, hipStream_t s, bool fused_done = false, const float* row_weight = nullptr);
+// the standalone loss kernel of the head on the logits in the workspace: the row losses (and d loss / d logits when
+// g_logits is given).  loss_stage is this plus the sum of the rows; wn_score takes the rows as they are
+int loss_rows_stage(wn_plan* p, int64_t rows, float gscale, float* g_logits, bool want_grad, float* ws, const WsLayout& L,
+                    float* absmax_out, hipStream_t s, const float* row_weight);
 // the armed row weights against the rows of a call: WN_E_INVALID with both numbers, before the device is touched
 int row_weights_check(const char* who, const wn_exec& e, int B, int T);
 

@@ -318,6 +318,7 @@ class WaveNet(torch.nn.Module):
     # in exact fp32 (each costs a second, slower pass; train.py logs them per epoch)
     self.train_guard_trips = 0
     self.test_guard_trips = 0
+    self.score_guard_trips = 0
     self.generation_guard_trips = 0
     # None = automatic: a single replica reads its step scalars back between forward and backward; data-parallel replicas
     # take them from the gradient bucket's tail after the ONE all-reduce of the step (no second collective per step)
@@ -919,6 +920,68 @@ class WaveNet(torch.nn.Module):
       elif not hasattr(metric, 'update_state_device'):
         metric.update_state(x[:, 1:, :], sample, **wkw)
     return {m.name: m.result() for m in self.metrics if m.name != 'reg_loss'}
+
+  def score(self, data, sample_weight=None, per_sample=False):
+    """Per-utterance negative log-likelihoods of ``data`` in one evaluation pass.
+
+    ``data`` is what ``test_step`` takes: ``x (B, T + 1, 1)`` or ``(x, cond)``; the pass is the inference forward (no
+    dropout) and works inside ``averaged_weights()``.  Returns a dict of device tensors::
+
+      'nll'             (B,)  sum_t w[b, t] l[b, t], in nats
+      'weight'          (B,)  sum_t w[b, t]; exactly T without sample_weight
+      'nll_per_sample'  (B,)  nll / weight
+      'bits_per_sample' (B,)  nll / (weight ln 2)
+      'rows'            (B, T)  w[b, t] l[b, t] as the loss kernel stored it -- only with per_sample=True
+
+    ``l`` is the per-row loss exactly as ``loss_fn`` defines it for the head: Keras's clipped cross entropy of a categorical
+    head; for a mixture head the negative log of the bin mass (logistic) or of the density (gaussian), so "bits per sample"
+    of a mixture head is that NLL divided by ln 2 and nothing more (a density's is not bounded below by 0).  There is no
+    1 / global_batch factor and no L2 term; no metric is updated and nothing is all-reduced: a replica scores its own rows.
+
+    ``sample_weight``: the shapes of ``train_step`` (``(B, T)``, ``(B, T, 1)`` or ``(B,)``), the semantics of DESIGN.md
+    section 25 -- a weight of 0 removes the row whatever it holds, so ``data.length_weights(lengths, T)`` scores padded
+    utterances of different lengths.  Where ``weight == 0`` the two ratios are NaN (0 / 0); they are not special-cased.
+
+    Range guard as in ``test_step``: a tripped pass is repeated under ``exact_fp32()`` and counted in
+    ``score_guard_trips`` (one host read of the flag per call)."""
+    sample_weight = self._check_sample_weight(data, sample_weight)
+    x, cond = self._split_inputs(data)
+    B, T = x.shape[0], x.shape[1] - 1
+    if T < 1:
+      raise ValueError('score needs at least 2 samples per utterance')
+    weights = self._row_weights(sample_weight, B, T)
+    L = _lib.lib()
+    ws = self._workspace('fwd', L.wn_plan_workspace_floats(self._plan, B, T, 0))
+    out = torch.empty(2 * B + 1, dtype=torch.float32, device=self._device)
+    nll, weight, flag = out[:B], out[B:2 * B], out[2 * B:]
+    rows = torch.empty(B, T, dtype=torch.float32, device=self._device) if per_sample else None
+
+    def once():
+      try:
+        if weights is not None:
+          _lib.check(L.wn_plan_arm_row_weights(self._plan, _lib.ptr(weights), B * T))
+        _lib.check(L.wn_score(self._plan, _lib.ptr(self.flat_params), _lib.ptr(x), _lib.ptr(cond), B, T, _lib.ptr(nll),
+                              _lib.ptr(weight), _lib.ptr(rows), _lib.ptr(flag), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+      finally:
+        if weights is not None:
+          L.wn_plan_arm_row_weights(self._plan, None, 0)
+      return float(flag) > 0
+    if once():
+      self.score_guard_trips += 1
+      with self.exact_fp32():
+        once()
+    nll, weight = nll.clone(), weight.clone()
+    res = {'nll': nll, 'weight': weight, 'nll_per_sample': nll / weight, 'bits_per_sample': nll / (weight * math.log(2.0))}
+    if per_sample:
+      res['rows'] = rows
+    return res
+
+  def eval_intermediate(self, what: int, B: int, T: int):
+    """View on a region of the inference workspace as the last ``test_step`` / ``score`` / ``call`` over (B, T) left it
+    (wn_debug_eval_region: 5 the logits, 12 the per-row losses; tests tell from them which loss path a pass took)."""
+    off, ln = C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().wn_debug_eval_region(self._plan, B, T, what, C.byref(off), C.byref(ln)))
+    return self._ws['fwd'][off.value:off.value + ln.value]
 
   # ------------------------------------------------------------------ autograd
   def differentiable(self, inputs, training=False, output='probs'):
