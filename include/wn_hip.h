@@ -146,6 +146,13 @@ int wn_debug_ws_region(const wn_plan* p, int32_t B, int32_t T, int32_t what, int
  * untouched by a wn_score pass that formed the loss in the last conv's epilogue) | 12 the per-row losses (B * T).
  * Any other `what` is WN_E_INVALID. */
 int wn_debug_eval_region(const wn_plan* p, int32_t B, int32_t T, int32_t what, int64_t* off, int64_t* len);
+/* test / diagnosis hook, host only: which kernels a forward pass over (B, T) takes under the calling thread's switches,
+ * for a call without dropout and without ring capture.  loss: 0 none | 1 the training loss epilogue wanted | 2 the
+ * evaluation epilogue wanted.  One `name=value` token per decision, separated by blanks:
+ *   cond=none|small|rows  conv_cond=none|batched|per_block  inconv=elementwise|rows  zfill=0|1  fold=0|1
+ *   prep=none|inline|side  drop=0|1  deep16=0|1  skip=none|folded/planes|folded/rows|sum  first_final=<i>  hc0=<width>
+ *   head=<epilogue|planes|rows of every head layer from first_final on, in order, comma separated> */
+int wn_debug_fwd_paths(const wn_plan* p, int32_t B, int32_t T, int32_t training, int32_t loss, char* buf, int32_t len);
 /* the whole residual-block stack of a forward pass: one event pair per pass from the first block launch to
  * the end of the folded skip contraction = t_stack_fwd of SURVEY.md 8(d); read returns passes and the average */
 int wn_stack_prof_enable(wn_plan* p, int32_t max_passes);

@@ -1188,6 +1188,64 @@ def test_generation_paths_follow_every_key_change(channels, finals):
     _lib.lib().wn_debug_set(2, 0)
 
 
+FWD_PATH_NETS = {
+    # folded contraction on the planes kernel, a planes head layer, the loss epilogue
+    'folded_planes_epilogue': dict(blocks=3, channels=64, skip_channels=256, dilation_bound=4, final_layers_channels=[128, 256],
+                                   bits=8, activation='leaky_relu'),
+    'rows_everywhere': MODEL_CASES['cat_small_fused'],
+}
+
+
+@pytest.mark.parametrize('net', list(FWD_PATH_NETS))
+def test_forward_paths_follow_every_key_change(net):
+  """The kernel paths of a forward pass are decided per call (wnp::fwd_paths) from the math mode, training or inference
+  and what the caller wants of the loss: ONE model through logits in split precision -> logits in exact fp32 ->
+  loss_and_grads (the loss epilogue where the head takes it) -> loss_and_grads(want_pred=True) (the logits written, the
+  standalone loss kernel) -> score (the evaluation epilogue) -> the first state again.  B = 2, T = 97: four 32-row tiles
+  per utterance, the last one ragged.  Every revisit gives the bits of the first visit, and every first visit those of a
+  fresh model built directly in that state; where the head fuses the loss, the two loss_and_grads forms agree on loss and
+  gradients to the bars of test_loss_and_gradients_parity.  Correctness against the oracle is the parity tests' job."""
+  import contextlib
+  kw = dict(FWD_PATH_NETS[net])
+  B, T = 2, 97
+  x = O.synthetic_waveform(B, T + 1, seed=31).to(dev())
+  xin = x[:, :-1].contiguous()
+
+  def run(m, state):
+    what, exact = state
+    with (m.exact_fp32() if exact else contextlib.nullcontext()):
+      if what == 'logits':
+        return [m.logits(xin).clone()]
+      if what == 'score':
+        sc = m.score(x, per_sample=True)
+        return [sc['nll'].clone(), sc['weight'].clone(), sc['rows'].clone()]
+      loss, pred, _ = m.loss_and_grads(x, want_pred=(what == 'grads_pred'))
+      return [loss.clone()] + ([pred.clone()] if pred is not None else []) + [g.clone() for g in m.gradients()]
+  _, _, model = make_pair(seed=23, bias_range=0.2, **kw)
+  states = [('logits', False), ('logits', True), ('grads', False), ('grads_pred', False), ('score', False), ('logits', False)]
+  first = {}
+  for state in states:
+    got = run(model, state)
+    assert all(bool(torch.isfinite(t).all()) for t in got), state
+    if state not in first:
+      first[state] = got
+      fresh = run(make_pair(seed=23, bias_range=0.2, **kw)[2], state)
+      assert len(got) == len(fresh) and all(torch.equal(a, b) for a, b in zip(got, fresh)), ('fresh', state)
+    assert len(got) == len(first[state]) and all(torch.equal(a, b) for a, b in zip(got, first[state])), ('revisit', state)
+  assert not torch.equal(first[('logits', False)][0], first[('logits', True)][0])      # two math modes really ran
+  fused, plain = first[('grads', False)], first[('grads_pred', False)]
+  assert float(fused[0][2]) == 0.0 and float(plain[0][2]) == 0.0                         # range flags
+  assert len(plain) == len(fused) + 1 and plain[1].shape == (B, T, 256)
+  if net == 'folded_planes_epilogue':
+    # the loss in the last conv's epilogue against the standalone kernel on the written logits
+    ref = plain[0][0].item()
+    assert abs(fused[0][0].item() - ref) < 2e-5 * max(1.0, abs(ref))
+    for n, g, r in zip(model.variable_names, fused[1:], plain[2:]):
+      scale = max(r.abs().max().item(), 1e-6)
+      err = (g.double() - r.double()).abs().max().item()
+      assert err < 1e-4 * scale + 1e-7, (n, err, scale)
+
+
 @pytest.mark.parametrize('B,T', [(1, 20), (3, 97)])
 def test_wide_blocks_gradients_ragged(B, T, math_mode):
   """128-channel blocks (BASELINE configs[3] width): the forward is two split-precision contractions with the

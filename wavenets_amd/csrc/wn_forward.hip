@@ -76,29 +76,53 @@ int ring_capture(const float* src, int B, int T, int C, int nslots, float* ring,
   return WN_OK;
 }
 
-int forward_core(wn_plan* p, const float* params, const float* x, bool prep, const float* cond, int B,
-                 int T, bool training, float* ws, const WsLayout& L, hipStream_t s, const GenRings* rings, LossFuse* lf) {
-  int rc = ensure_device_tables(p);
-  if (rc) return rc;
-  const int64_t rows = (int64_t)B * T;
-  float* fragbase = ws + L.frag;
-  if (prep) {
-    rc = wn_launch_prep_table(p->d_prep, (int)p->prep.size(), params, fragbase, s);
-    if (rc) return rc;
+// ------------------------------------------------------------------------------------------
+// One forward pass: the calling thread's execution state, the caller's buffers, the workspace layout and the kernel paths
+// of the call (fwd_paths, wn_plan.hip); its phases are the member functions, in launch order.
+// ------------------------------------------------------------------------------------------
+struct FwdCall {
+  wn_exec& e;
+  wn_plan* p; const float* params; const float* x; const float* cond; int B, T; bool training, prep;
+  float* ws; const WsLayout& L; hipStream_t s; const GenRings* rings; LossFuse* lf;
+  int64_t rows; float* fragbase;
+  // Forward range guard.  The split-precision kernels cast fp32 activations to fp16 hi|lo unscaled: beyond 65504 the
+  // hi part is inf.  Every kernel that produces an input of such a kernel -- the residual stream H[b], the skip sum,
+  // the head activations (z is bounded by 1) -- publishes its running max-abs here; the callers turn it into a flag
+  // (WN_RANGE_LIMIT) and redo the pass with the exact-fp32 kernels when it tripped.
+  float* fam;
+  FwdPaths fp;
+  bool stack_prof = false;           // an event pair around the stack is open (blocks() -> skip())
+  const float* hin = nullptr;        // the head's input rows (skip() -> head())
+
+  FwdCall(wn_plan* p_, const float* params_, const float* x_, bool prep_, const float* cond_, int B_, int T_, bool training_,
+          float* ws_, const WsLayout& L_, hipStream_t s_, const GenRings* rings_, LossFuse* lf_)
+      : e(wnp::ex(p_)), p(p_), params(params_), x(x_), cond(cond_), B(B_), T(T_), training(training_), prep(prep_), ws(ws_),
+        L(L_), s(s_), rings(rings_), lf(lf_), rows((int64_t)B_ * T_), fragbase(ws_ + L_.frag), fam(ws_ + L_.fwd_absmax),
+        fp(fwd_paths(p_, e, B_, T_, training_, prep_, rings_ != nullptr, !lf_ ? FWD_LOSS_NONE : lf_->eval ? FWD_LOSS_EVAL : FWD_LOSS_TRAIN)) {}
+
+  const float* par(int tensor) const { return params + p->tensors[tensor].off; }
+
+  // The timing hooks bench.py reads: (start, stop) event pairs out of the calling state's pools, recorded on `sp` at the
+  // points they always were.  A stop takes the pair.
+  static bool pair_free(const std::vector<hipEvent_t>& ev, int used) { return used + 2 <= (int)ev.size(); }
+  static void mark(const std::vector<hipEvent_t>& ev, int& used, bool stop, hipStream_t sp) {
+    (void)hipEventRecord(ev[used + (stop ? 1 : 0)], sp);
+    if (stop) used += 2;
   }
+
+  int weight_images() {
+    return prep ? wn_launch_prep_table(p->d_prep, (int)p->prep.size(), params, fragbase, s) : WN_OK;
+  }
+
   // The weight-space preparation of the skip path (bias sum, V = W_s W_f0, its fp16 images: ~45 us of small launches) is
   // only needed by the folded contraction at the END of the block chain.  With the side stream allowed (knob 9 = 0) it is
-  // forked off right where the stack begins (the stack's start event below) and runs beside the first blocks; the
-  // contraction waits for it.  Otherwise it runs here, on the caller's stream.
-  wn_exec& exs = wnp::ex(p);
-  const bool fold = fold_ok(p);
-  const bool fork_prep = prep && fold && p->c.use_skip && wn_debug_get(9) == 0;
-  bool prep_forked = false;
-  auto fold_prep = [&](hipStream_t sp) -> int {
-    const bool fp_prof = prep && fold && exs.foldprep_used + 2 <= (int)exs.foldprep_ev.size();
-    if (fp_prof) (void)hipEventRecord(exs.foldprep_ev[exs.foldprep_used], sp);
+  // forked off right where the stack begins (the stack's start event in blocks()) and runs beside the first blocks; the
+  // contraction waits for it.  Otherwise it runs on the caller's stream, ahead of the conditioning.
+  int fold_prep(hipStream_t sp) {
+    const bool fp_prof = fp.fold && pair_free(e.foldprep_ev, e.foldprep_used);
+    if (fp_prof) mark(e.foldprep_ev, e.foldprep_used, false, sp);
     // bias of the folded skip sum = sum over blocks of conv_skip (or conv1) biases
-    if (prep && p->c.use_skip) {
+    if (p->c.use_skip) {
       const ConvInfo& c0 = p->blocks[0].has_skip ? p->blocks[0].conv_skip : p->blocks[0].conv1;
       WnVecSumArgs v;
       v.base = params; v.off0 = p->tensors[c0.bias_t].off;
@@ -109,7 +133,7 @@ int forward_core(wn_plan* p, const float* params, const float* x, bool prep, con
     }
     // (inference and the generation priming pass fold too: the queued sampler carries the folded contraction in its chain
     // kernel and must reproduce the sliding window bit for bit)
-    if (fold && prep) {
+    if (fp.fold) {
       const BlockInfo& b0 = p->blocks[0];
       const int64_t wst = p->N > 1 ? p->tensors[p->blocks[1].conv_skip.kernel_t].off - p->tensors[b0.conv_skip.kernel_t].off : 0;
       int r = wn_launch_skip_fold(params, p->tensors[b0.conv_skip.kernel_t].off, wst, p->tensors[p->finals[0].kernel_t].off,
@@ -119,228 +143,243 @@ int forward_core(wn_plan* p, const float* params, const float* x, bool prep, con
       r = wn_launch_prep_table(p->d_prep2, (int)p->prep2.size(), ws, fragbase, sp, 64);  // sources relative to the workspace
       if (r) return r;
     }
-    if (fp_prof) { (void)hipEventRecord(exs.foldprep_ev[exs.foldprep_used + 1], sp); exs.foldprep_used += 2; }
+    if (fp_prof) mark(e.foldprep_ev, e.foldprep_used, true, sp);
     return WN_OK;
-  };
-  if (!fork_prep) {
-    rc = fold_prep(s);
-    if (rc) return rc;
   }
+
+  // ... on the side stream, behind whatever wrote the parameters
+  int fold_prep_fork() {
+    if (!e.side) {
+      WN_HIP_CHECK(hipStreamCreateWithFlags(&e.side, hipStreamNonBlocking));
+      WN_HIP_CHECK(hipEventCreateWithFlags(&e.ev_fork, hipEventDisableTiming));
+      WN_HIP_CHECK(hipEventCreateWithFlags(&e.ev_join, hipEventDisableTiming));
+    }
+    if (!e.ev_ffork) {
+      WN_HIP_CHECK(hipEventCreateWithFlags(&e.ev_ffork, hipEventDisableTiming));
+      WN_HIP_CHECK(hipEventCreateWithFlags(&e.ev_fjoin, hipEventDisableTiming));
+    }
+    WN_HIP_CHECK(hipEventRecord(e.ev_ffork, s));
+    WN_HIP_CHECK(hipStreamWaitEvent(e.side, e.ev_ffork, 0));
+    const int rc = fold_prep(e.side);
+    if (rc) return rc;
+    WN_HIP_CHECK(hipEventRecord(e.ev_fjoin, e.side));
+    return WN_OK;
+  }
+
   // conditioning: mapping Dense stack + per-block time-invariant bias  (src/model.py:221-225,
   // src/layers.py:203-204: conv_cond(repeat(m)) == per-utterance bias)
-  const float* m = cond;
-  if (p->c.cond_inputs > 0) {
+  int condition() {
+    if (fp.cond == FWD_COND_NONE) return WN_OK;
     if (!cond) { wn_set_error("Conditioning must be provided."); return WN_E_INVALID; }
-    int mc = p->c.cond_inputs;
+    const bool small = fp.cond == FWD_COND_SMALL;
+    const float* m = cond;
+    int mc = p->c.cond_inputs, rc;
     for (size_t j = 0; j < p->mapping.size(); ++j) {
       const ConvInfo& c = p->mapping[j];
-      if (cond_small(p))      // Dense: M[j] = act(m W + b), W = kernel (cin, cout)
-        rc = wn_launch_sgemm_small_batched(m, mc, 1, 0, params + p->tensors[c.kernel_t].off, c.cout, 1, 0, ws + L.M[j], c.cout, 0,
-                                           B, c.cout, mc, 1, params + p->tensors[c.bias_t].off, p->c.mapping_activation, s);
+      if (small)              // Dense: M[j] = act(m W + b), W = kernel (cin, cout)
+        rc = wn_launch_sgemm_small_batched(m, mc, 1, 0, par(c.kernel_t), c.cout, 1, 0, ws + L.M[j], c.cout, 0,
+                                           B, c.cout, mc, 1, par(c.bias_t), p->c.mapping_activation, s);
       else
-      rc = Gemm(1, B, c.cout, ceil32(c.cout)).seg(m, mc, mc, 0, fragbase + c.fragF)
-               .bias(params + p->tensors[c.bias_t].off).act(p->c.mapping_activation).run(ws + L.M[j], c.cout, s);
+        rc = Gemm(1, B, c.cout, ceil32(c.cout)).seg(m, mc, mc, 0, fragbase + c.fragF)
+                 .bias(par(c.bias_t)).act(p->c.mapping_activation).run(ws + L.M[j], c.cout, s);
       if (rc) return rc;
       m = ws + L.M[j]; mc = c.cout;
     }
-    if (p->frag_condF >= 0) {
-      // all blocks in one contraction, then [B][N*2D] -> [N][B][2D] with the biases added
-      const int D2 = 2 * p->D;
-      const ConvInfo& c0 = p->blocks[0].conv_cond;
-      const int64_t bst = p->N > 1 ? p->tensors[p->blocks[1].conv_cond.bias_t].off - p->tensors[c0.bias_t].off : 0;
-      if (cond_small(p)) {    // block z: cbt[:, z * 2D ..] = m W_c(z), W_c = kernel (1, Cc, 2D)
-        const int64_t wst = p->N > 1 ? p->tensors[p->blocks[1].conv_cond.kernel_t].off - p->tensors[c0.kernel_t].off : 0;
-        rc = wn_launch_sgemm_small_batched(m, p->Cc, 1, 0, params + p->tensors[c0.kernel_t].off, D2, 1, wst, ws + L.cbt, p->N * D2, D2,
-                                           B, D2, p->Cc, p->N, nullptr, 0, s);
-      } else
-      rc = Gemm(1, B, p->N * D2, ceil32(p->N * D2)).seg(m, p->Cc, p->Cc, 0, fragbase + p->frag_condF).run(ws + L.cbt, p->N * D2, s);
-      if (rc) return rc;
-      rc = wn_launch_cond_scatter(ws + L.cbt, params, p->tensors[c0.bias_t].off, bst, B, p->N, D2, ws + L.cb, s);
-      if (rc) return rc;
+    const int D2 = 2 * p->D;
+    if (!fp.cond_batched) {
+      for (int b = 0; b < p->N; ++b) {
+        const ConvInfo& c = p->blocks[b].conv_cond;
+        rc = Gemm(1, B, D2, ceil32(D2)).seg(m, p->Cc, p->Cc, 0, fragbase + c.fragF)
+                 .bias(par(c.bias_t)).run(ws + L.cb + (int64_t)b * B * D2, D2, s);
+        if (rc) return rc;
+      }
+      return WN_OK;
+    }
+    // all blocks in one contraction, then [B][N*2D] -> [N][B][2D] with the biases added
+    const ConvInfo& c0 = p->blocks[0].conv_cond;
+    const int64_t bst = p->N > 1 ? p->tensors[p->blocks[1].conv_cond.bias_t].off - p->tensors[c0.bias_t].off : 0;
+    if (small) {              // block z: cbt[:, z * 2D ..] = m W_c(z), W_c = kernel (1, Cc, 2D)
+      const int64_t wst = p->N > 1 ? p->tensors[p->blocks[1].conv_cond.kernel_t].off - p->tensors[c0.kernel_t].off : 0;
+      rc = wn_launch_sgemm_small_batched(m, p->Cc, 1, 0, par(c0.kernel_t), D2, 1, wst, ws + L.cbt, p->N * D2, D2,
+                                         B, D2, p->Cc, p->N, nullptr, 0, s);
     } else {
-    for (int b = 0; b < p->N; ++b) {
-      const ConvInfo& c = p->blocks[b].conv_cond;
-      rc = Gemm(1, B, 2 * p->D, ceil32(2 * p->D)).seg(m, p->Cc, p->Cc, 0, fragbase + c.fragF)
-               .bias(params + p->tensors[c.bias_t].off).run(ws + L.cb + (int64_t)b * B * 2 * p->D, 2 * p->D, s);
-      if (rc) return rc;
+      rc = Gemm(1, B, p->N * D2, ceil32(p->N * D2)).seg(m, p->Cc, p->Cc, 0, fragbase + p->frag_condF).run(ws + L.cbt, p->N * D2, s);
     }
-    }
+    if (rc) return rc;
+    return wn_launch_cond_scatter(ws + L.cbt, params, p->tensors[c0.bias_t].off, bst, B, p->N, D2, ws + L.cb, s);
   }
-  // Forward range guard.  The split-precision kernels cast fp32 activations to fp16 hi|lo unscaled: beyond 65504 the
-  // hi part is inf.  Every kernel that produces an input of such a kernel -- the residual stream H[b], the skip sum,
-  // the head activations (z is bounded by 1) -- publishes its running max-abs here; the callers turn it into a flag
-  // (WN_RANGE_LIMIT) and redo the pass with the exact-fp32 kernels when it tripped.
-  float* const fam = ws + L.fwd_absmax;
-  WN_HIP_CHECK(hipMemsetAsync(fam, 0, sizeof(float), s));
-  // input causal conv, src/model.py:84-88,228 : KS taps with C_in = 1
-  {
-    if (p->R % 4 == 0 && wn_debug_get(1) != 1) {
-      // elementwise kernel, same fma chain as the matrix product below computes for a K = 1 operand
-      rc = wn_launch_inconv_fwd(x, params + p->tensors[p->causal.kernel_t].off, params + p->tensors[p->causal.bias_t].off, B, T,
-                                p->R, p->KS, ws + L.H[0], fam, s);
+
+  // input causal conv, src/model.py:84-88,228 : KS taps with C_in = 1 (behind the cleared range-guard slot)
+  int input_conv() {
+    WN_HIP_CHECK(hipMemsetAsync(fam, 0, sizeof(float), s));
+    int rc;
+    if (fp.inconv_elem) {
+      rc = wn_launch_inconv_fwd(x, par(p->causal.kernel_t), par(p->causal.bias_t), B, T, p->R, p->KS, ws + L.H[0], fam, s);
     } else {
       Gemm g(B, T, p->R, ceil32(p->R));
       for (int t = 0; t < p->KS; ++t)
         g.seg(x, 1, 1, (p->KS - 1 - t), fragbase + p->causal.fragF + t * p->causal.fragF_stride);
-      rc = g.bias(params + p->tensors[p->causal.bias_t].off).run(ws + L.H[0], p->R, s);
+      rc = g.bias(par(p->causal.bias_t)).run(ws + L.H[0], p->R, s);
     }
     if (rc) return rc;
     if (rings) {
       rc = ring_capture(x, B, T, 1, p->KS, rings->xin, s);
       if (!rc) rc = ring_capture(ws + L.H[0], B, T, p->R, rings->nslots[0], rings->h[0], s);
-      if (rc) return rc;
     }
+    return rc;
   }
-  if (p->Dp != p->D) {
-    rc = wn_launch_fill(ws + L.Z, 0.f, rows * p->N * p->Dp, s);
-    if (rc) return rc;
-  }
+
   // residual blocks, src/model.py:230-234
-  // profiling: is the chain N back-to-back launches of the fused block kernel?
-  const bool prof_chain = wnp::ex(p).prof_on && !rings && p->LPB == 1 && p->c.cond_inputs == 0 && p->R == p->D &&
-                          !(training && wnp::ex(p).drop_rate > 0.f) && block_ptrs(p, 0, params, fragbase, B, T).fused;
-  const bool stack_prof = !rings && wnp::ex(p).stack_used + 2 <= (int)wnp::ex(p).stack_ev.size();
-  if (stack_prof) (void)hipEventRecord(wnp::ex(p).stack_ev[wnp::ex(p).stack_used], s);
-  if (fork_prep) {
+  int blocks() {
+    int rc;
+    if (fp.zfill) {
+      rc = wn_launch_fill(ws + L.Z, 0.f, rows * p->N * p->Dp, s);
+      if (rc) return rc;
+    }
+    // profiling: is the chain N back-to-back launches of the fused block kernel?
+    const bool prof_chain = e.prof_on && !rings && p->LPB == 1 && p->c.cond_inputs == 0 && p->R == p->D && !fp.drop && p->fused_ok;
+    stack_prof = !rings && pair_free(e.stack_ev, e.stack_used);
+    if (stack_prof) mark(e.stack_ev, e.stack_used, false, s);
     // the stack's start event (above) is the fork point: whatever the preparation costs the chain shows inside the pair
-    if (!exs.side) {
-      WN_HIP_CHECK(hipStreamCreateWithFlags(&exs.side, hipStreamNonBlocking));
-      WN_HIP_CHECK(hipEventCreateWithFlags(&exs.ev_fork, hipEventDisableTiming));
-      WN_HIP_CHECK(hipEventCreateWithFlags(&exs.ev_join, hipEventDisableTiming));
-    }
-    if (!exs.ev_ffork) {
-      WN_HIP_CHECK(hipEventCreateWithFlags(&exs.ev_ffork, hipEventDisableTiming));
-      WN_HIP_CHECK(hipEventCreateWithFlags(&exs.ev_fjoin, hipEventDisableTiming));
-    }
-    WN_HIP_CHECK(hipEventRecord(exs.ev_ffork, s));     // behind whatever wrote the parameters
-    WN_HIP_CHECK(hipStreamWaitEvent(exs.side, exs.ev_ffork, 0));
-    rc = fold_prep(exs.side);
-    if (rc) return rc;
-    WN_HIP_CHECK(hipEventRecord(exs.ev_fjoin, exs.side));
-    prep_forked = true;
-  }
-  for (int b = 0; b < p->N; ++b) {
-    BlockPtrs k = block_ptrs(p, b, params, fragbase, B, T);
-    if (training && !rings) deep16_ptrs(p, b, fragbase, k);
-    if (p->c.cond_inputs > 0) k.cb = ws + L.cb + (int64_t)b * B * 2 * p->D;
-    BlockBufs f;
-    memset(&f, 0, sizeof(f));
-    const int hi = training ? b : (b & 1), ho = training ? b + 1 : ((b + 1) & 1);
-    f.x = ws + L.H[hi];
-    if (training && wnp::ex(p).drop_rate > 0.f) {
-      // x = dropout(x) feeds the dilated stack; the residual keeps the original (src/layers.py:192-196)
-      rc = wn_launch_dropout(ws + L.H[hi], nullptr, ws + L.XD[b], rows * p->R, wnp::ex(p).drop_rate,
-                             wn_dropout_key(wnp::ex(p).drop_seed, b, wnp::ex(p).drop_step), nullptr, s);
-      if (rc) return rc;
-      f.x = ws + L.XD[b];
-      f.res = ws + L.H[hi];
-    }
-    for (int i = 0; i + 1 < p->LPB; ++i) f.P[i] = ws + L.P[b][i];
-    f.U = ws + L.U;
-    f.AG = training ? ws + L.AG[b] : nullptr;
-    f.Z = ws + L.Z + (int64_t)b * rows * p->Dp; f.ldz = p->Dp;      // block-major [N][rows][Dp]
-    f.O = nullptr;
-    f.x_out = ws + L.H[ho];
-    f.fwd_absmax = fam;
-    const bool prof = wnp::ex(p).prof_on && wnp::ex(p).prof_used + 2 <= (int)wnp::ex(p).prof_ev.size();
-    const bool ev0 = prof && (!prof_chain || b == 0), ev1 = prof && (!prof_chain || b == p->N - 1);
-    if (ev0) (void)hipEventRecord(wnp::ex(p).prof_ev[wnp::ex(p).prof_used], s);
-    rc = block_forward(k, f, s);
-    if (rc) return rc;
-    if (ev1) {
-      (void)hipEventRecord(wnp::ex(p).prof_ev[wnp::ex(p).prof_used + 1], s);
-      wnp::ex(p).prof_cnt[wnp::ex(p).prof_used / 2] = prof_chain ? p->N : 1;
-      wnp::ex(p).prof_used += 2;
-    }
-    if (rings && b + 1 < p->N) {
-      rc = ring_capture(f.x_out, B, T, p->R, rings->nslots[b + 1], rings->h[b + 1], s);
+    if (fp.prep == FWD_PREP_SIDE) {
+      rc = fold_prep_fork();
       if (rc) return rc;
     }
-    if (rings)
-      for (int i = 0; i + 1 < p->LPB; ++i) {
-        rc = ring_capture(f.P[i], B, T, p->D, rings->nslots_p[b][i], rings->hp[b][i], s);
+    for (int b = 0; b < p->N; ++b) {
+      BlockPtrs k = block_ptrs(p, b, params, fragbase, B, T);
+      if (fp.deep16) deep16_ptrs(p, b, fragbase, k);
+      if (fp.cond != FWD_COND_NONE) k.cb = ws + L.cb + (int64_t)b * B * 2 * p->D;
+      BlockBufs f;
+      memset(&f, 0, sizeof(f));
+      const int hi = training ? b : (b & 1), ho = training ? b + 1 : ((b + 1) & 1);
+      f.x = ws + L.H[hi];
+      if (fp.drop) {
+        // x = dropout(x) feeds the dilated stack; the residual keeps the original (src/layers.py:192-196)
+        rc = wn_launch_dropout(ws + L.H[hi], nullptr, ws + L.XD[b], rows * p->R, e.drop_rate,
+                               wn_dropout_key(e.drop_seed, b, e.drop_step), nullptr, s);
+        if (rc) return rc;
+        f.x = ws + L.XD[b];
+        f.res = ws + L.H[hi];
+      }
+      for (int i = 0; i + 1 < p->LPB; ++i) f.P[i] = ws + L.P[b][i];
+      f.U = ws + L.U;
+      f.AG = training ? ws + L.AG[b] : nullptr;
+      f.Z = ws + L.Z + (int64_t)b * rows * p->Dp; f.ldz = p->Dp;      // block-major [N][rows][Dp]
+      f.O = nullptr;
+      f.x_out = ws + L.H[ho];
+      f.fwd_absmax = fam;
+      // one event pair per block launch, or one around the whole chain
+      const bool prof = e.prof_on && pair_free(e.prof_ev, e.prof_used);
+      if (prof && (!prof_chain || b == 0)) mark(e.prof_ev, e.prof_used, false, s);
+      rc = block_forward(k, f, s);
+      if (rc) return rc;
+      if (prof && (!prof_chain || b == p->N - 1)) {
+        e.prof_cnt[e.prof_used / 2] = prof_chain ? p->N : 1;
+        mark(e.prof_ev, e.prof_used, true, s);
+      }
+      if (rings && b + 1 < p->N) {
+        rc = ring_capture(f.x_out, B, T, p->R, rings->nslots[b + 1], rings->h[b + 1], s);
         if (rc) return rc;
       }
+      if (rings)
+        for (int i = 0; i + 1 < p->LPB; ++i) {
+          rc = ring_capture(f.P[i], B, T, p->D, rings->nslots_p[b][i], rings->hp[b][i], s);
+          if (rc) return rc;
+        }
+    }
+    if (fp.prep == FWD_PREP_SIDE) WN_HIP_CHECK(hipStreamWaitEvent(s, e.ev_fjoin, 0));   // the fold's images and biases are ready
+    return WN_OK;
   }
-  if (prep_forked) WN_HIP_CHECK(hipStreamWaitEvent(s, exs.ev_fjoin, 0));   // the fold's images and biases are ready
+
   // skip sum folded into one contraction over all blocks' gated activations (src/model.py:235-236
   // with src/layers.py:216-219), or the last block output when use_skip is False
-  const float* hin;
-  size_t first_final = 0;
-  if (fold) {
-    // a = act(sum_b V(b)^T z_b + b'): the skip sum and the head's first conv in ONE contraction with F0 output columns
-    const ConvInfo& c0 = p->finals[0];
-    // streamed kernel, second form (wn_gemm16s.hip; other shapes: wn_gemm_rows16_kernel, the same products in the same order)
-    // (the streamed form indexes rows with 32-bit byte offsets: beyond 4 GiB per plane the rows GEMM takes over)
-    if (p->Dp == p->D && wn_gemm_planes16s_supported(c0.cout, p->D, p->N, p->Dp, c0.cout) &&
-        (int64_t)rows * p->Dp * 4 < ((int64_t)1 << 32) && (int64_t)rows * c0.cout * 4 < ((int64_t)1 << 32)) {
-      WnGemmPlanesArgs ga;
-      memset(&ga, 0, sizeof(ga));
-      ga.z = ws + L.Z; ga.plane_stride = rows * p->Dp; ga.ld = p->Dp; ga.plane_k = p->D; ga.nplanes = p->N;
-      ga.w16 = fragbase + p->frag16_foldF; ga.bias = ws + L.bfold; ga.act = p->c.activation;
-      ga.y = ws + L.HA[0]; ga.ldy = c0.cout; ga.N = c0.cout; ga.B = B; ga.T = T; ga.absmax_out = fam;
-      rc = wn_launch_gemm_planes16s(ga, s);
-    } else
-    rc = Gemm(B, T, c0.cout, ceil32(c0.cout)).seg_planes(ws + L.Z, p->Dp, rows * p->Dp, p->N * p->Dp, nullptr)
-             .w16(fragbase + p->frag16_foldF).bias(ws + L.bfold).act(p->c.activation).absmax_fwd(fam)
-             .run(ws + L.HA[0], c0.cout, s);
-    if (rc) return rc;
-    hin = ws + L.HA[0];
-    first_final = 1;
-  } else if (p->c.use_skip) {
-    rc = Gemm(B, T, p->Sh, ceil32(p->Sh)).seg_planes(ws + L.Z, p->Dp, rows * p->Dp, p->N * p->Dp, fragbase + p->frag_skipF)
-             .w16(p->frag16_skipF >= 0 ? fragbase + p->frag16_skipF : nullptr)
-             .bias(ws + L.bias_sum).absmax_fwd(fam).run(ws + L.skipsum, p->Sh, s);
-    if (rc) return rc;
-    hin = ws + L.skipsum;
-  } else {
-    hin = ws + L.H[training ? p->N : (p->N & 1)];
-  }
-  if (stack_prof) { (void)hipEventRecord(wnp::ex(p).stack_ev[wnp::ex(p).stack_used + 1], s); wnp::ex(p).stack_used += 2; }
-  // head, src/model.py:105-119,237-238: conv -> activation, last conv linear (softmax applied later)
-  int hc = fold ? p->finals[0].cout : p->Hin;
-  for (size_t i = first_final; i < p->finals.size(); ++i) {
-    const ConvInfo& c = p->finals[i];
-    const bool last = (i + 1 == p->finals.size());
-    float* dst = last ? ws + L.logits : ws + L.HA[i];
-    // training pass of a 256-class categorical head: the loss is this conv's epilogue (no logits tensor); a scoring pass
-    // (lf->eval) takes the evaluation form of it: the loss rows and nothing else
-    if (last && lf && loss_fusable(p, rows) && wn_gemm_planes16s_supported(c.cout, hc, 1, hc, c.cout) &&
-        (int64_t)rows * hc * 4 < ((int64_t)1 << 32)) {
-      WnGemmPlanesArgs ga;
-      memset(&ga, 0, sizeof(ga));
-      ga.z = hin; ga.plane_stride = 0; ga.ld = hc; ga.plane_k = hc; ga.nplanes = 1;
-      ga.w16 = fragbase + c.frag16; ga.bias = params + p->tensors[c.bias_t].off; ga.act = WN_ACT_LINEAR;
-      ga.y = lf->g_logits; ga.ldy = c.cout; ga.N = c.cout; ga.B = B; ga.T = T; ga.absmax_out = lf->absmax_out;
-      ga.cat_loss = lf->eval ? 2 : 1; ga.target = lf->target; ga.gscale = lf->gscale; ga.loss_rows = lf->loss_rows;
-      ga.sample_out = lf->sample_out; ga.inv_lv = lf->inv_lv; ga.seed = lf->seed; ga.offset = lf->offset;
-      ga.row_weight = lf->row_weight;
-      rc = wn_launch_gemm_planes16s(ga, s);
-      if (rc) return rc;
-      lf->done = true;
-      break;
+  int skip() {
+    int rc = WN_OK;
+    switch (fp.skip) {
+      // a = act(sum_b V(b)^T z_b + b'): the skip sum and the head's first conv in ONE contraction with F0 output columns
+      case FWD_SKIP_FOLD_PLANES:   // streamed kernel, second form (wn_gemm16s.hip)
+        rc = Planes(B, T, fp.hc0).operand(ws + L.Z, p->Dp, p->D, p->N, rows * p->Dp).w16(fragbase + p->frag16_foldF)
+                 .bias(ws + L.bfold).act(p->c.activation).absmax_fwd(fam).run(ws + L.HA[0], fp.hc0, s);
+        hin = ws + L.HA[0];
+        break;
+      case FWD_SKIP_FOLD_ROWS:     // other shapes: wn_gemm_rows16_kernel, the same products in the same order
+        rc = Gemm(B, T, fp.hc0, ceil32(fp.hc0)).seg_planes(ws + L.Z, p->Dp, rows * p->Dp, p->N * p->Dp, nullptr)
+                 .w16(fragbase + p->frag16_foldF).bias(ws + L.bfold).act(p->c.activation).absmax_fwd(fam)
+                 .run(ws + L.HA[0], fp.hc0, s);
+        hin = ws + L.HA[0];
+        break;
+      case FWD_SKIP_SUM:
+        rc = Gemm(B, T, p->Sh, ceil32(p->Sh)).seg_planes(ws + L.Z, p->Dp, rows * p->Dp, p->N * p->Dp, fragbase + p->frag_skipF)
+                 .w16(p->frag16_skipF >= 0 ? fragbase + p->frag16_skipF : nullptr)
+                 .bias(ws + L.bias_sum).absmax_fwd(fam).run(ws + L.skipsum, p->Sh, s);
+        hin = ws + L.skipsum;
+        break;
+      case FWD_SKIP_NONE:
+        hin = ws + L.H[training ? p->N : (p->N & 1)];
+        break;
     }
-    // 128 / 256 output columns: the streamed kernel's second form (wn_gemm16s.hip; the operand is one "plane"); same
-    // products in the same order as the rows GEMM below
-    if (c.frag16 >= 0 && wn_debug_get(1) != 1 && wn_gemm_planes16s_supported(c.cout, hc, 1, hc, c.cout) &&
-        (int64_t)rows * hc * 4 < ((int64_t)1 << 32)) {
-      WnGemmPlanesArgs ga;
-      memset(&ga, 0, sizeof(ga));
-      ga.z = hin; ga.plane_stride = 0; ga.ld = hc; ga.plane_k = hc; ga.nplanes = 1;
-      ga.w16 = fragbase + c.frag16; ga.bias = params + p->tensors[c.bias_t].off; ga.act = last ? WN_ACT_LINEAR : p->c.activation;
-      ga.y = dst; ga.ldy = c.cout; ga.N = c.cout; ga.B = B; ga.T = T; ga.absmax_out = last ? nullptr : fam;
-      rc = wn_launch_gemm_planes16s(ga, s);
+    if (rc) return rc;
+    if (stack_prof) mark(e.stack_ev, e.stack_used, true, s);
+    return WN_OK;
+  }
+
+  // head, src/model.py:105-119,237-238: conv -> activation, last conv linear (softmax applied later)
+  int head() {
+    int hc = fp.hc0;
+    for (int i = fp.first_final; i < fp.nhead; ++i) {
+      const ConvInfo& c = p->finals[i];
+      const bool last = (i + 1 == fp.nhead);
+      float* dst = last ? ws + L.logits : ws + L.HA[i];
+      int rc;
+      switch (fp.head[i]) {
+        // training pass of a 256-class categorical head: the loss is this conv's epilogue (no logits tensor); a scoring
+        // pass (lf->eval) takes the evaluation form of it: the loss rows and nothing else
+        case FWD_HEAD_EPILOGUE:
+          rc = Planes(B, T, c.cout).operand(hin, hc, hc).w16(fragbase + c.frag16).bias(par(c.bias_t)).act(WN_ACT_LINEAR)
+                   .loss(*lf).run(lf->g_logits, c.cout, s);
+          if (rc) return rc;
+          lf->done = true;
+          return WN_OK;
+        // 128 / 256 output columns: the streamed kernel's second form (wn_gemm16s.hip; the operand is one "plane"); same
+        // products in the same order as the rows GEMM below
+        case FWD_HEAD_PLANES:
+          rc = Planes(B, T, c.cout).operand(hin, hc, hc).w16(fragbase + c.frag16).bias(par(c.bias_t))
+                   .act(last ? WN_ACT_LINEAR : p->c.activation).absmax_fwd(last ? nullptr : fam).run(dst, c.cout, s);
+          break;
+        default:
+          rc = Gemm(B, T, c.cout, ceil32(c.cout)).seg(hin, hc, hc, 0, fragbase + c.fragF)
+                   .w16(c.frag16 >= 0 ? fragbase + c.frag16 : nullptr)
+                   .bias(par(c.bias_t)).act(last ? WN_ACT_LINEAR : p->c.activation)
+                   .absmax_fwd(last ? nullptr : fam).run(dst, c.cout, s);
+          break;
+      }
       if (rc) return rc;
       hin = dst; hc = c.cout;
-      continue;
     }
-    rc = Gemm(B, T, c.cout, ceil32(c.cout)).seg(hin, hc, hc, 0, fragbase + c.fragF)
-             .w16(c.frag16 >= 0 ? fragbase + c.frag16 : nullptr)
-             .bias(params + p->tensors[c.bias_t].off).act(last ? WN_ACT_LINEAR : p->c.activation)
-             .absmax_fwd(last ? nullptr : fam).run(dst, c.cout, s);
-    if (rc) return rc;
-    hin = dst; hc = c.cout;
+    return WN_OK;
   }
+};
+
+int forward_core(wn_plan* p, const float* params, const float* x, bool prep, const float* cond, int B,
+                 int T, bool training, float* ws, const WsLayout& L, hipStream_t s, const GenRings* rings, LossFuse* lf) {
+  int rc = ensure_device_tables(p);
+  if (rc) return rc;
+  FwdCall c(p, params, x, prep, cond, B, T, training, ws, L, s, rings, lf);
+  if ((rc = c.weight_images())) return rc;
+  if (c.fp.prep == FWD_PREP_INLINE && (rc = c.fold_prep(s))) return rc;
+  if ((rc = c.condition())) return rc;
+  if ((rc = c.input_conv())) return rc;
+  if ((rc = c.blocks())) return rc;      // (FWD_PREP_SIDE: fold_prep() forked off at their start, joined at their end)
+  if ((rc = c.skip())) return rc;
+  return c.head();
+}
+
+int emit_outputs(const wn_plan* p, const float* ws, const WsLayout& L, int64_t rows, float* logits_out, float* out, hipStream_t s) {
+  const size_t bytes = rows * p->Cout * sizeof(float);
+  if (logits_out) WN_HIP_CHECK(hipMemcpyAsync(logits_out, ws + L.logits, bytes, hipMemcpyDeviceToDevice, s));
+  if (!out) return WN_OK;
+  if (p->c.head == WN_HEAD_CATEGORICAL) return wn_launch_softmax(ws + L.logits, out, rows, p->Cout, s);
+  WN_HIP_CHECK(hipMemcpyAsync(out, ws + L.logits, bytes, hipMemcpyDeviceToDevice, s));
   return WN_OK;
 }
 
@@ -404,22 +443,22 @@ int row_weights_check(const char* who, const wn_exec& e, int B, int T) {
 
 using namespace wnp;
 
+// wn_forward / wn_forward_training: one body; `who` is the prefix of its error texts
+static int forward_entry(const char* who, bool training, wn_plan* p, const float* params, const float* x, const float* cond,
+                         int32_t B, int32_t T, float* out, float* logits_out, float* workspace, int64_t ws_floats, void* stream) {
+  if (!p || !params || !x || !workspace || B < 1 || T < 1) { wn_set_error("%s: bad arguments", who); return WN_E_INVALID; }
+  hipStream_t s = (hipStream_t)stream;
+  const WsLayout L = make_layout(p, B, T, training);
+  if (ws_floats < L.total) { wn_set_error("%s: workspace too small (%lld < %lld floats)", who, (long long)ws_floats, (long long)L.total); return WN_E_INVALID; }
+  const int rc = forward_core(p, params, x, true, cond, B, T, training, workspace, L, s);
+  if (rc) return rc;
+  return emit_outputs(p, workspace, L, (int64_t)B * T, logits_out, out, s);
+}
+
 extern "C" int wn_forward(wn_plan* p, const float* params, const float* x, const float* cond, int32_t B,
                           int32_t T, float* out, float* logits_out, float* workspace, int64_t ws_floats,
                           void* stream) {
-  if (!p || !params || !x || !workspace || B < 1 || T < 1) { wn_set_error("forward: bad arguments"); return WN_E_INVALID; }
-  hipStream_t s = (hipStream_t)stream;
-  const WsLayout L = make_layout(p, B, T, false);
-  if (ws_floats < L.total) { wn_set_error("forward: workspace too small (%lld < %lld floats)", (long long)ws_floats, (long long)L.total); return WN_E_INVALID; }
-  int rc = forward_core(p, params, x, true, cond, B, T, false, workspace, L, s);
-  if (rc) return rc;
-  const int64_t rows = (int64_t)B * T;
-  if (logits_out) WN_HIP_CHECK(hipMemcpyAsync(logits_out, workspace + L.logits, rows * p->Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (out) {
-    if (p->c.head == WN_HEAD_CATEGORICAL) return wn_launch_softmax(workspace + L.logits, out, rows, p->Cout, s);
-    WN_HIP_CHECK(hipMemcpyAsync(out, workspace + L.logits, rows * p->Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-  }
-  return WN_OK;
+  return forward_entry("forward", false, p, params, x, cond, B, T, out, logits_out, workspace, ws_floats, stream);
 }
 
 // WaveNet.call(inputs, training=True), src/model.py:213-239 with src/layers.py:195-196: the forward pass with the
@@ -427,19 +466,7 @@ extern "C" int wn_forward(wn_plan* p, const float* params, const float* x, const
 extern "C" int wn_forward_training(wn_plan* p, const float* params, const float* x, const float* cond, int32_t B,
                                    int32_t T, float* out, float* logits_out, float* workspace, int64_t ws_floats,
                                    void* stream) {
-  if (!p || !params || !x || !workspace || B < 1 || T < 1) { wn_set_error("forward_training: bad arguments"); return WN_E_INVALID; }
-  hipStream_t s = (hipStream_t)stream;
-  const WsLayout L = make_layout(p, B, T, true);
-  if (ws_floats < L.total) { wn_set_error("forward_training: workspace too small (%lld < %lld floats)", (long long)ws_floats, (long long)L.total); return WN_E_INVALID; }
-  int rc = forward_core(p, params, x, true, cond, B, T, true, workspace, L, s);
-  if (rc) return rc;
-  const int64_t rows = (int64_t)B * T;
-  if (logits_out) WN_HIP_CHECK(hipMemcpyAsync(logits_out, workspace + L.logits, rows * p->Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (out) {
-    if (p->c.head == WN_HEAD_CATEGORICAL) return wn_launch_softmax(workspace + L.logits, out, rows, p->Cout, s);
-    WN_HIP_CHECK(hipMemcpyAsync(out, workspace + L.logits, rows * p->Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-  }
-  return WN_OK;
+  return forward_entry("forward_training", true, p, params, x, cond, B, T, out, logits_out, workspace, ws_floats, stream);
 }
 
 extern "C" int wn_eval_loss(wn_plan* p, const float* params, const float* x_full, const float* cond,
@@ -461,11 +488,7 @@ extern "C" int wn_eval_loss(wn_plan* p, const float* params, const float* x_full
   if (rc) return rc;
   rc = wn_launch_guard_flag(workspace + L.fwd_absmax, WN_RANGE_LIMIT, wn_debug_get(1) != 1, loss_out + 2, s);
   if (rc) return rc;
-  if (pred_out) {
-    if (p->c.head == WN_HEAD_CATEGORICAL) return wn_launch_softmax(workspace + L.logits, pred_out, rows, p->Cout, s);
-    WN_HIP_CHECK(hipMemcpyAsync(pred_out, workspace + L.logits, rows * p->Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-  }
-  return WN_OK;
+  return emit_outputs(p, workspace, L, rows, nullptr, pred_out, s);
 }
 
 // WaveNet.score: the evaluation pass of wn_eval_loss up to the row losses, then one workgroup per utterance.  A 256-class

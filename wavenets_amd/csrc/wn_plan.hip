@@ -9,6 +9,8 @@
 // (prep descriptors, tensor table) are immutable launch metadata uploaded on first use.
 #include "wn_plan_internal.h"
 
+#include <string>
+
 namespace {
 using namespace wnp;
 
@@ -317,6 +319,53 @@ GenPaths gen_paths(const wn_plan* p, int B, int length, int cu_count, bool relay
   g.sampler = (g.head_tail || head_mix) ? GEN_SAMPLE_IN_HEAD : deterministic ? GEN_SAMPLE_DET
               : (!cat || wn_sample_from_logits_supported(p->Cout)) ? GEN_SAMPLE_RAND : GEN_SAMPLE_ROWS;
   return g;
+}
+
+// Which kernels a forward pass over B x T rows takes under knobs 1 and 9 (the one decision: the phases of FwdCall and
+// wn_debug_fwd_paths read it).  The 32-bit row limits are each site's own, as they were where the launches stood (DESIGN.md
+// section 27 lists where they differ).
+FwdPaths fwd_paths(const wn_plan* p, const wn_exec& e, int B, int T, bool training, bool prep, bool rings, FwdLoss loss) {
+  FwdPaths f;
+  const bool split = wn_debug_get(1) != 1;
+  const int64_t rows = (int64_t)B * T;
+  if (p->c.cond_inputs > 0) {
+    f.cond = cond_small(p) ? FWD_COND_SMALL : FWD_COND_ROWS;
+    f.cond_batched = p->frag_condF >= 0;
+  }
+  // elementwise kernel: the same fma chain as the matrix product computes for a K = 1 operand
+  f.inconv_elem = p->R % 4 == 0 && split;
+  f.zfill = p->Dp != p->D;
+  f.fold = fold_ok(p);
+  // the bias sum of the skip convs (any skip path) and V = W_s W_f0 with its images (folded): beside the first blocks when
+  // the side stream is allowed (knob 9 = 0) and the folded contraction at the end of the chain is what waits for it
+  f.prep = (prep && f.fold && p->c.use_skip && wn_debug_get(9) == 0) ? FWD_PREP_SIDE
+           : (prep && (f.fold || p->c.use_skip)) ? FWD_PREP_INLINE : FWD_PREP_NONE;
+  f.drop = training && e.drop_rate > 0.f;
+  f.deep16 = training && !rings && deep16(p);
+  const size_t nf = p->finals.size();
+  if (f.fold) {
+    // (the streamed form indexes rows with 32-bit byte offsets: beyond 4 GiB per plane the rows GEMM takes over)
+    const ConvInfo& c0 = p->finals[0];
+    f.skip = (p->Dp == p->D && Planes::takes(false, c0.cout, p->D, p->N, p->Dp, c0.cout, rows, {p->Dp, c0.cout}))
+             ? FWD_SKIP_FOLD_PLANES : FWD_SKIP_FOLD_ROWS;
+    f.first_final = 1;
+  } else if (p->c.use_skip) {
+    f.skip = FWD_SKIP_SUM;
+  }
+  f.hc0 = f.fold ? p->finals[0].cout : p->Hin;
+  f.nhead = (int)nf;
+  int hc = f.hc0;
+  for (size_t i = (size_t)f.first_final; i < nf; ++i) {
+    const ConvInfo& c = p->finals[i];
+    // 128 / 256 output columns: the streamed kernel's second form (the operand is one "plane")
+    const bool planes = Planes::takes(false, c.cout, hc, 1, hc, c.cout, rows, {hc});
+    // the last conv of a 256-class categorical head with the loss as its epilogue, when the caller set one up (LossFuse)
+    if (i + 1 == nf && loss != FWD_LOSS_NONE && loss_fusable(p, rows) && planes) f.head[i] = FWD_HEAD_EPILOGUE;
+    else if (c.frag16 >= 0 && split && planes) f.head[i] = FWD_HEAD_PLANES;
+    else f.head[i] = FWD_HEAD_ROWS;
+    hc = c.cout;
+  }
+  return f;
 }
 
 WsLayout make_layout(const wn_plan* p, int B, int T, bool training) {
@@ -925,6 +974,25 @@ extern "C" int wn_plan_describe(const wn_plan* p, char* buf, int32_t len) {
            fold ? "folded into the head's first conv (V = W_s W_f0, training / inference / generation)"
                 : (p->c.use_skip ? "one contraction over all blocks' gated activations, then the head" : "none (use_skip False)"),
            bwd, wg);
+  return WN_OK;
+}
+
+// fwd_paths() of a call over B x T rows under the calling thread's knobs, without dropout or rings, weight images
+// prepared: one `name=value` token per decision, the head layers in order (host only)
+extern "C" int wn_debug_fwd_paths(const wn_plan* p, int32_t B, int32_t T, int32_t training, int32_t loss, char* buf, int32_t len) {
+  if (!p || !buf || len < 1 || B < 1 || T < 1 || loss < 0 || loss > 2) return WN_E_INVALID;
+  wn_exec none;                       // (a state of its own: no dropout)
+  const FwdPaths f = fwd_paths(p, none, B, T, training != 0, true, false, (FwdLoss)loss);
+  static const char* const cond[] = {"none", "small", "rows"};
+  static const char* const prep[] = {"none", "inline", "side"};
+  static const char* const skip[] = {"none", "folded/planes", "folded/rows", "sum"};
+  static const char* const head[] = {"rows", "planes", "epilogue"};
+  std::string h;
+  for (int i = f.first_final; i < f.nhead; ++i) h += std::string(h.empty() ? "" : ",") + head[f.head[i]];
+  snprintf(buf, (size_t)len, "cond=%s conv_cond=%s inconv=%s zfill=%d fold=%d prep=%s drop=%d deep16=%d skip=%s first_final=%d hc0=%d head=%s",
+           cond[f.cond], f.cond == FWD_COND_NONE ? "none" : f.cond_batched ? "batched" : "per_block",
+           f.inconv_elem ? "elementwise" : "rows", (int)f.zfill, (int)f.fold, prep[f.prep], (int)f.drop, (int)f.deep16, skip[f.skip],
+           f.first_final, f.hc0, h.c_str());
   return WN_OK;
 }
 

@@ -126,6 +126,35 @@ struct GenPaths {
   }
 };
 
+// Which kernels one forward pass takes: decided once per call (fwd_paths, wn_plan.hip), read by the phases of FwdCall
+// (wn_forward.hip) and written out by wn_debug_fwd_paths.
+enum FwdCond { FWD_COND_NONE, FWD_COND_SMALL, FWD_COND_ROWS };   // unconditioned | wn_sgemm_small32_kernel | rows GEMMs
+enum FwdPrep { FWD_PREP_NONE, FWD_PREP_INLINE, FWD_PREP_SIDE };  // the skip path's weight-space preparation: none | caller's stream | side stream
+// the skip stage: the last block output feeds the head | folded with the head's first conv on the planes kernel | ... on the
+// rows GEMM | the reference's skip sum
+enum FwdSkip { FWD_SKIP_NONE, FWD_SKIP_FOLD_PLANES, FWD_SKIP_FOLD_ROWS, FWD_SKIP_SUM };
+enum FwdHead : uint8_t { FWD_HEAD_ROWS, FWD_HEAD_PLANES, FWD_HEAD_EPILOGUE };   // rows GEMM | planes kernel | ... with the loss as its epilogue
+enum FwdLoss { FWD_LOSS_NONE, FWD_LOSS_TRAIN, FWD_LOSS_EVAL };   // what the caller wants of the loss epilogue (LossFuse)
+struct FwdPaths {
+  FwdCond cond = FWD_COND_NONE;
+  bool cond_batched = false;      // all blocks' conv_cond as one contraction + scatter (else one rows GEMM per block)
+  bool inconv_elem = false;       // the input conv on the elementwise kernel (else a rows GEMM over KS one-channel taps)
+  bool zfill = false;             // Z has padding columns (Dp != D): zero-filled before the blocks
+  bool fold = false;
+  FwdPrep prep = FWD_PREP_NONE;
+  bool drop = false;              // dropped copies of the block inputs
+  bool deep16 = false;            // the deep-stack split-precision images are bound (training, no rings)
+  FwdSkip skip = FWD_SKIP_NONE;
+  int first_final = 0, hc0 = 0;   // the first head layer behind the skip stage and its input width
+  int nhead = 0;                  // = finals.size(); head[i] for i >= first_final
+  FwdHead head[WN_MAX_FINAL + 1] = {};
+  bool operator==(const FwdPaths& o) const {
+    return cond == o.cond && cond_batched == o.cond_batched && inconv_elem == o.inconv_elem && zfill == o.zfill && fold == o.fold &&
+           prep == o.prep && drop == o.drop && deep16 == o.deep16 && skip == o.skip && first_final == o.first_final &&
+           hc0 == o.hc0 && nhead == o.nhead && std::equal(head, head + WN_MAX_FINAL + 1, o.head);
+  }
+};
+
 // owning device copy of a host table
 template <class T> struct DevTable {
   T* d = nullptr;
@@ -368,6 +397,71 @@ struct Gemm {
   }
 };
 
+// Training passes of a 256-class categorical head: the loss runs as the epilogue of the head's last conv
+// (wn_gemm_planes16s_kernel<1, 8, -3>): where that launch puts its results.  forward_core sets `done` when it took the
+// fused path (the logits are then never written); loss_stage only sums the row losses.
+struct LossFuse {
+  const int32_t* target; float gscale; float* loss_rows; float* g_logits; float* absmax_out;
+  float* sample_out; float inv_lv; uint64_t seed, offset;
+  const float* row_weight;     // [rows] sample_weight of the rows, or null (the unweighted instantiation)
+  bool done;
+  // wn_score: the evaluation form of the epilogue (<1, 8, -5> / <1, 8, -6>): the loss rows and nothing else -- g_logits,
+  // absmax_out, gscale and the draw are not used
+  bool eval;
+};
+
+// The streamed kernel's second form (wn_gemm_planes16s_kernel): one builder for its arguments, one test for "does it take
+// this contraction".
+struct Planes {
+  WnGemmPlanesArgs a;
+  // The shape rule (with `taps`: of the shifted-planes form) and the kernel's 32-bit byte offsets: rows * w * 4 < 2^32 for
+  // every row width w the calling site lists (the sites do not list the same ones: DESIGN.md section 27)
+  static bool takes(bool taps, int N, int plane_k, int nplanes, int ld, int ldy, int64_t rows, std::initializer_list<int> widths) {
+    if (!(taps ? wn_gemm_taps16s_supported(N, plane_k, nplanes, ld, ldy) : wn_gemm_planes16s_supported(N, plane_k, nplanes, ld, ldy)))
+      return false;
+    for (int w : widths)
+      if (!((int64_t)rows * w * 4 < ((int64_t)1 << 32))) return false;
+    return true;
+  }
+  Planes(int B, int T, int N) {
+    memset(&a, 0, sizeof(a));
+    a.B = B; a.T = T; a.N = N;
+  }
+  // plane q, row r: z + q * plane_stride + r * ld, plane_k columns of it
+  Planes& operand(const float* z, int ld, int plane_k, int nplanes = 1, int64_t plane_stride = 0) {
+    a.z = z; a.ld = ld; a.plane_k = plane_k; a.nplanes = nplanes; a.plane_stride = plane_stride;
+    return *this;
+  }
+  // the n taps of a dilated conv as shifted planes of the one operand: tap t reads row time - (n - 1 - t) * step (backward
+  // data: step = -dilation)
+  Planes& taps(int n, int step) {
+    a.nplanes = n; a.nshift = n;
+    for (int t = 0; t < n; ++t) a.shift[t] = (n - 1 - t) * step;
+    return *this;
+  }
+  Planes& w16(const float* img) { a.w16 = img; return *this; }
+  Planes& bias(const float* b) { a.bias = b; return *this; }
+  Planes& act(int act) { a.act = act; return *this; }
+  Planes& absmax_fwd(float* out) { a.absmax_out = out; return *this; }     // forward range-guard slot
+  // backward-data form: operand scaled by *am_in, the result's max-abs into am_out, * act'(aux) when aux is given
+  Planes& bwd(const float* am_in, float* am_out, const float* aux = nullptr, int ld_aux = 0) {
+    a.bwd = 1; a.absmax_in = am_in; a.absmax_out = am_out; a.aux = aux; a.ld_aux = ld_aux;
+    return *this;
+  }
+  // the categorical loss as the epilogue (training or evaluation form); run() then takes lf.g_logits as y
+  Planes& loss(const LossFuse& lf) {
+    a.absmax_out = lf.absmax_out;
+    a.cat_loss = lf.eval ? 2 : 1; a.target = lf.target; a.gscale = lf.gscale; a.loss_rows = lf.loss_rows;
+    a.sample_out = lf.sample_out; a.inv_lv = lf.inv_lv; a.seed = lf.seed; a.offset = lf.offset;
+    a.row_weight = lf.row_weight;
+    return *this;
+  }
+  int run(float* y, int ldy, hipStream_t s) {
+    a.y = y; a.ldy = ldy;
+    return wn_launch_gemm_planes16s(a, s);
+  }
+};
+
 struct BlockPtrs {
   // geometry
   int B, T, KS, R, D, S, Cin, depth, act, residual;
@@ -454,6 +548,8 @@ TrainPaths train_paths(const wn_plan* p);   // the plan-level part; the per-call
 TrainPaths train_paths(const wn_plan* p, const wn_exec& e, const WsLayout& L, int64_t rows);
 // (cu_count: the device's compute units; relay_area: the generation workspace carries the relay's granule areas)
 GenPaths gen_paths(const wn_plan* p, int B, int length, int cu_count, bool relay_area, bool deterministic, const WnSampleCtl& ctl);
+// (e: the calling state, for its dropout rate; rings: the generation priming pass captures the rings)
+FwdPaths fwd_paths(const wn_plan* p, const wn_exec& e, int B, int T, bool training, bool prep, bool rings, FwdLoss loss);
 int64_t slab_need(int B, int T, int K, int N);
 // ---- wn_block.hip ----
 int wgrad(const float* x, int ldx, int K, int shift, const float* g, int ldg, int N, int B, int T,
@@ -461,24 +557,15 @@ int wgrad(const float* x, int ldx, int K, int shift, const float* g, int ldg, in
 int block_forward(const BlockPtrs& k, const BlockBufs& f, hipStream_t s);
 int block_backward(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, hipStream_t s);
 // ---- wn_forward.hip ----
-// Training passes of a 256-class categorical head: the loss runs as the epilogue of the head's last conv
-// (wn_gemm_planes16s_kernel<1, 8, -3>): where that launch puts its results.  forward_core sets `done` when it took the
-// fused path (the logits are then never written); loss_stage only sums the row losses.
-struct LossFuse {
-  const int32_t* target; float gscale; float* loss_rows; float* g_logits; float* absmax_out;
-  float* sample_out; float inv_lv; uint64_t seed, offset;
-  const float* row_weight;     // [rows] sample_weight of the rows, or null (the unweighted instantiation)
-  bool done;
-  // wn_score: the evaluation form of the epilogue (<1, 8, -5> / <1, 8, -6>): the loss rows and nothing else -- g_logits,
-  // absmax_out, gscale and the draw are not used
-  bool eval;
-};
 bool loss_fusable(const wn_plan* p, int64_t rows);
 BlockPtrs block_ptrs(const wn_plan* p, int b, const float* params, const float* fragbase, int B, int T);
 void deep16_ptrs(const wn_plan* p, int b, const float* fragbase, BlockPtrs& k);
 int forward_core(wn_plan* p, const float* params, const float* x, bool prep, const float* cond, int B,
                  int T, bool training, float* ws, const WsLayout& L, hipStream_t s, const GenRings* rings = nullptr,
                  LossFuse* lf = nullptr);
+// what a pass hands back from the logits in the workspace: a copy of them, and the model output (their softmax for a
+// categorical head, the logits themselves for a mixture head); either may be null
+int emit_outputs(const wn_plan* p, const float* ws, const WsLayout& L, int64_t rows, float* logits_out, float* out, hipStream_t s);
 // inputs = x[:, :-1], y_true = x[:, 1:]  (src/model.py:319-321)
 int shift_split(const float* x_full, int B, int T, float* inputs, float* y_true, hipStream_t s);
 int loss_stage(wn_plan* p, int B, int T, int global_batch, bool want_grad, float* ws, const WsLayout& L,

@@ -288,11 +288,8 @@ struct TrainCall {
     if (e.phase_on) (void)hipEventRecord(e.phase_ev[1], s);
     rc = loss_stage(p, B, T, global_batch, true, ws, L, loss_out, am_GF(nf - 1), s, lf.done, e.row_weights);
     if (rc) return rc;
-    if (pred_out) {
-      if (p->c.head == WN_HEAD_CATEGORICAL) rc = wn_launch_softmax(ws + L.logits, pred_out, rows, p->Cout, s);
-      else rc = hipMemcpyAsync(pred_out, ws + L.logits, rows * p->Cout * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess ? WN_OK : WN_E_HIP;
-      if (rc) return rc;
-    }
+    rc = emit_outputs(p, ws, L, rows, nullptr, pred_out, s);
+    if (rc) return rc;
     if (e.step_sample) {
       // sample_waveform(pred) of this step (src/model.py:338) drawn from the logits while they are still hot:
       // no (rows, C) probability tensor is written or re-read
@@ -349,17 +346,11 @@ struct TrainCall {
       const ConvInfo& c = p->finals[i];
       float* dst = (i == 0) ? head_out : ws + L.GF[i - 1];
       // 128 / 256 input channels: the streamed kernel's second form in its backward-data instantiation
-      if (c.frag16B >= 0 && wn_debug_get(1) != 1 && wn_gemm_planes16s_supported(c.cin, c.cout, 1, c.cout, c.cin) &&
-          (int64_t)rows * c.cout * 4 < ((int64_t)1 << 32)) {
-        WnGemmPlanesArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.z = ws + L.GF[i]; ga.ld = c.cout; ga.plane_k = c.cout; ga.nplanes = 1;
-        ga.w16 = fragbase + c.frag16B; ga.act = p->c.activation;
-        ga.y = dst; ga.ldy = c.cin; ga.N = c.cin; ga.B = B; ga.T = T;
-        ga.bwd = 1; ga.absmax_in = am_GF(i);
-        ga.absmax_out = i > 0 ? am_GF(i - 1) : (p->c.use_skip ? am_gskip : am_GH(p->N));
-        if (i > 0) { ga.aux = ws + L.HA[i - 1]; ga.ld_aux = c.cin; }
-        rc = wn_launch_gemm_planes16s(ga, s);
+      if (c.frag16B >= 0 && wn_debug_get(1) != 1 && Planes::takes(false, c.cin, c.cout, 1, c.cout, c.cin, rows, {c.cout})) {
+        rc = Planes(B, T, c.cin).operand(ws + L.GF[i], c.cout, c.cout).w16(fragbase + c.frag16B).act(p->c.activation)
+                 .bwd(am_GF(i), i > 0 ? am_GF(i - 1) : (p->c.use_skip ? am_gskip : am_GH(p->N)),
+                      i > 0 ? ws + L.HA[i - 1] : nullptr, i > 0 ? c.cin : 0)
+                 .run(dst, c.cin, s);
         if (rc) return rc;
         continue;
       }
