@@ -16,6 +16,13 @@
 // 128-byte row segments.  Operand scaling: the first product uses the running max-abs of g_u(b+1) like the unfused
 // kernel (bit-identical g_x); the second one cannot know the max-abs of the tensor it is producing, so every tile is
 // scaled by the exact power of two of max(its own max |g_x|, running max-abs of dL/da).
+//
+// Waits: every load and store is compiler-visible and the code is shaped so that hipcc's own vmcnt counts come out right
+// (no hand-written s_waitcnt vmcnt).  The tile body is instantiated once per position in a wave's
+// walk (only tile, first of several, later with a successor, last): the ring refills that belong to the next tile are
+// unconditional where there is one and absent where there is none, and no copy joins a state it is not entered with.
+// Rows leave as buffer stores on a descriptor that ends behind the tile's last valid row, so no store sits in a branch.
+// The tile index and all that follows from it (utterance, first row, valid rows, tensor bases) are scalar.
 #include "wn_split16.h"
 
 using namespace wn_split16;
@@ -32,24 +39,17 @@ constexpr int BP_STAGE = 32 * BP_PITCH * 4;      // 4608
 constexpr int BP_LDS = BP_W1 + BP_W2 + 8 * BP_STAGE;   // 151552
 constexpr int BP_PF = 4;
 
-// one 32 x 32 tile (D layout) -> LDS stage -> 128-byte row segments
-__device__ __forceinline__ void bp_store32(const f32x16& v, float* stage, float* dst, int64_t ld, int rows_valid, int lane) {
-  const int tl = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int rq = 0; rq < 4; ++rq) {
-    f32x4 o;
-    o.x = v[4 * rq + 0]; o.y = v[4 * rq + 1]; o.z = v[4 * rq + 2]; o.w = v[4 * rq + 3];
-    *reinterpret_cast<f32x4*>(stage + tl * BP_PITCH + 8 * rq + 4 * h) = o;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = i * 8 + (lane >> 3);
-    const int col = (lane & 7) * 4;
-    const f32x4 o = *reinterpret_cast<const f32x4*>(stage + row * BP_PITCH + col);
-    if (row < rows_valid) *reinterpret_cast<f32x4*>(dst + (int64_t)row * ld + col) = o;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+// one 32 x 32 tile (D layout) -> LDS stage -> 128-byte row segments, through wn_store_tile (wn_split16.h): buffer stores on
+// a descriptor that starts at dst and is rows_valid * ld * 4 bytes long (dst and rows_valid are wave-uniform).  dst is the
+// tile's first row PLUS the sub-tile's column offset (32 j floats of a 64-float g_x row, 64 part + 32 j of a 128-float g_u
+// row), so with c = that offset in bytes and L = ld * 4 (256 or 512) the segment of row r covers descriptor offsets
+// [r L, r L + 128).  Valid rows: r <= rows_valid - 1, so r L + 128 <= rows_valid L - (L - 128) < rows_valid L: inside, whole
+// (128 <= L).  Rows r >= rows_valid start at r L >= rows_valid L: outside, dropped by the hardware.  In tensor bytes the
+// descriptor ends at c + rows_valid L, i.e. c bytes into the first row behind the tile -- but the only offsets a lane
+// forms are r L + 16 q (q < 8), and none of those with r >= rows_valid is inside.
+__device__ __forceinline__ void bp_store32(const f32x16& v, float* stage, float* dst, int ld, int rows_valid, int lane) {
+  const f32x16 t[1] = {v};
+  wn_store_tile<1, BP_PITCH>(t, stage, dst, ld, rows_valid, lane);
 }
 
 }  // namespace
@@ -57,7 +57,7 @@ __device__ __forceinline__ void bp_store32(const f32x16& v, float* stage, float*
 __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[BP_LDS];
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform: what follows from the tile index stays in scalar registers
   const int tl = lane & 31, h = lane >> 5;
   float* stage = reinterpret_cast<float*>(smem + BP_W1 + BP_W2 + wave * BP_STAGE);
   {
@@ -74,24 +74,27 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
 
   const int tiles_per_b = (a.T + 31) >> 5;
   const int64_t ntiles = (int64_t)a.B * tiles_per_b;
+  // Where a tile is: all of it wave-uniform (scalar registers).  Per lane there are only t0 + tl and the row clamps.
   struct TileCtx {
-    int b, t, rows_valid;
+    int b, t0, rows_valid;
     int64_t row0;
   };
-  auto make_ctx = [&](int64_t tile, TileCtx& c) {
+  auto make_ctx = [&](int64_t tile) {
+    TileCtx c;
     c.b = (int)(tile / tiles_per_b);
-    const int t0 = (int)(tile % tiles_per_b) * 32;
-    c.t = t0 + tl;
-    c.rows_valid = min(32, a.T - t0);
-    c.row0 = (int64_t)c.b * a.T + t0;
+    c.t0 = (int)(tile % tiles_per_b) * 32;
+    c.rows_valid = min(32, a.T - c.t0);                            // 1 .. 32: every tile of a walk starts inside its utterance
+    c.row0 = (int64_t)c.b * a.T + c.t0;
+    return c;
   };
   // memory k-step m of a tile: 0..7 g_u(b+1)[t + d], 8..15 g_u(b+1)[t], 16..23 dL/da[t]  (straight-line, unconditional:
   // masked rows read a clamped row and are zeroed where they are consumed)
   auto load_x = [&](const TileCtx& c, int m, f32x4& q0, f32x4& q1, bool& okout) {
-    const int seg = m >> 3;                                        // wave-uniform
+    const int seg = m >> 3;                                        // compile-time at every call
     const int kk = m & 7;
-    const int ts = c.t + (seg == 0 ? a.dil : 0);
-    const bool ok = c.t < a.T && ts < a.T;
+    const int t = c.t0 + tl;
+    const int ts = t + (seg == 0 ? a.dil : 0);
+    const bool ok = t < a.T && ts < a.T;
     const float* base = seg == 2 ? a.gf : a.gu_in;
     const float* src = base + ((int64_t)c.b * a.T + (ok ? ts : 0)) * 128 + 4 * h + 16 * kk;
     q0 = ldg4(src);
@@ -101,21 +104,33 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
 
   float wmax_x = 0.f, wmax_u = 0.f;
   const WnTileWalk walk = wn_tile_walk(ntiles, 8, wave);          // each XCD a contiguous eighth of the tiles (wn_common.h)
-  const int64_t tstride = walk.stride, tend = walk.end;
-  int64_t tile = walk.first;
   TileCtx cur, nxt;
   f32x4 xr[BP_PF][2];
   bool okr[BP_PF];
-  if (tile < tend) {
-    make_ctx(tile, cur);
+
+  // One tile.  Whether it has a successor in the wave's walk (`nextc`) and whether its own first four k-steps are still to
+  // be requested (`firstc`) are COMPILE-TIME properties: the body is instantiated once per position in the walk (below),
+  // as in wn_layer_fwd_f16_kernel.  The ring refills of memory k-steps 20..23 belong to the next tile: with a successor
+  // they are unconditional requests, without one there are none.  As one loop with `else if (has_next)` around them they
+  // were four exec-skip branches and hipcc's wait counts those of the path that requested nothing (vmcnt(6) .. vmcnt(0) in
+  // front of the tile's last products, i.e. a wait for the next tile's loads just issued); and the loop header joined the
+  // prologue's state with the back edge's, so that a later tile's first product waited for the previous tile's stores.
+  auto do_tile = [&](int64_t tile, auto nextc, auto firstc) __attribute__((always_inline)) {
+    constexpr bool has_next = decltype(nextc)::value;
+    constexpr bool first = decltype(firstc)::value;
+    // The copies start alike: a marker that differs from copy to copy keeps hipcc from hoisting their common head in front
+    // of the branch that chooses between them (see wn_layer16.hip).
+    asm volatile("; pair tile body %0" ::"n"(2 * (int)has_next + (int)first) : "memory");
+    if constexpr (first) {
+      cur = make_ctx(tile);
 #pragma unroll
-    for (int k = 0; k < BP_PF; ++k) load_x(cur, k, xr[k][0], xr[k][1], okr[k]);
-  }
-  for (; tile < tend; tile += tstride) {
-    const bool has_next = tile + tstride < tend;                   // wave-uniform
-    if (has_next) make_ctx(tile + tstride, nxt);
-    const bool tin = cur.t < a.T;
-    const int64_t row = cur.row0 + (tin ? tl : 0);                  // rows past the end read the tile's first row (unused)
+      for (int k = 0; k < BP_PF; ++k) load_x(cur, k, xr[k][0], xr[k][1], okr[k]);
+    }
+    if constexpr (has_next) nxt = make_ctx(tile + walk.stride);
+    const int rows_valid = cur.rows_valid;
+    const int64_t row0 = cur.row0;
+    const bool tin = cur.t0 + tl < a.T;
+    const int64_t row = row0 + (tin ? tl : 0);                      // rows past the end read the tile's first row (unused)
 
     // ---- residual operand of the first product, requested before its contraction ----
     f32x4 addc[2][4];
@@ -123,6 +138,9 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int rq = 0; rq < 4; ++rq) addc[j][rq] = ldg4(a.gx_res + row * 64 + 32 * j + 8 * rq + 4 * h);
+    // pin them in front of the first operand split (in the loop copy hipcc started the split above them, with a wait for
+    // the ring's first quad in front of these requests)
+    __builtin_amdgcn_sched_barrier(0);
 
     // ---- g_x(b+1) = reversed dilated conv of g_u(b+1) ----
     f32x16 acc[2];
@@ -130,22 +148,21 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    for (int m0 = 0; m0 < BP_NK1; m0 += BP_PF) {
-      wn_static_for<BP_PF>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        h8 bh, bl;
-        split8s(xr[k][0], xr[k][1], okr[k] ? sc1 : 0.f, bh, bl);
-        __builtin_amdgcn_sched_barrier(0);
-        load_x(cur, m0 + k + BP_PF, xr[k][0], xr[k][1], okr[k]);    // m0 + k + 4 <= 19 < 24: always this tile
+    wn_static_for<BP_NK1>([&](auto mc) {
+      constexpr int m = decltype(mc)::value;
+      constexpr int k = m % BP_PF;
+      h8 bh, bl;
+      split8s(xr[k][0], xr[k][1], okr[k] ? sc1 : 0.f, bh, bl);
+      __builtin_amdgcn_sched_barrier(0);
+      load_x(cur, m + BP_PF, xr[k][0], xr[k][1], okr[k]);           // m + 4 <= 19 < 24: always this tile
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const h8 ah = w1[(((m0 + k) * 2 + j) * 2 + 0) * 64];
-          const h8 al = w1[(((m0 + k) * 2 + j) * 2 + 1) * 64];
-          mfma3(ah, al, bh, bl, acc[j]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      });
-    }
+      for (int j = 0; j < 2; ++j) {
+        const h8 ah = w1[((m * 2 + j) * 2 + 0) * 64];
+        const h8 al = w1[((m * 2 + j) * 2 + 1) * 64];
+        mfma3(ah, al, bh, bl, acc[j]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    });
     // epilogue 1: + g_x(b+2) (residual path); rows past the utterance are exact zeros (they feed the next product)
     f32x16 gx[2];
     float tmax = 0.f;
@@ -170,10 +187,8 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
         sg[j][rq] = ldg4(a.ag + row * 64 + 32 * j + 8 * rq + 4 * h);
         zz[j][rq] = ldg4(a.z + row * a.ldz + 32 * j + 8 * rq + 4 * h);
       }
-    if (cur.rows_valid > 0) {
-      bp_store32(gx[0], stage, a.gx_out + cur.row0 * 64, 64, cur.rows_valid, lane);
-      bp_store32(gx[1], stage, a.gx_out + cur.row0 * 64 + 32, 64, cur.rows_valid, lane);
-    }
+    bp_store32(gx[0], stage, a.gx_out + row0 * 64, 64, rows_valid, lane);
+    bp_store32(gx[1], stage, a.gx_out + row0 * 64 + 32, 64, rows_valid, lane);
     wmax_x = fmaxf(wmax_x, tmax);
     // per-tile power-of-two scale of the second product's B operands
 #pragma unroll
@@ -201,25 +216,24 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
         mfma3(ah, al, bh, bl, acc[j]);
       }
     });
-    for (int m0 = BP_NK1; m0 < BP_NKM; m0 += BP_PF) {
-      wn_static_for<BP_PF>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        h8 bh, bl;
-        split8s(xr[k][0], xr[k][1], okr[k] ? sc2 : 0.f, bh, bl);
-        __builtin_amdgcn_sched_barrier(0);
-        const int mn = m0 + k + BP_PF;
-        if (mn < BP_NKM) load_x(cur, mn, xr[k][0], xr[k][1], okr[k]);
-        else if (has_next) load_x(nxt, mn - BP_NKM, xr[k][0], xr[k][1], okr[k]);
-        const int ks2 = BP_NKR + (m0 + k - BP_NK1);
+    wn_static_for<BP_NKF>([&](auto mc) {
+      constexpr int m = BP_NK1 + decltype(mc)::value;
+      constexpr int k = m % BP_PF;
+      h8 bh, bl;
+      split8s(xr[k][0], xr[k][1], okr[k] ? sc2 : 0.f, bh, bl);
+      __builtin_amdgcn_sched_barrier(0);
+      constexpr int mn = m + BP_PF;
+      if constexpr (mn < BP_NKM) load_x(cur, mn, xr[k][0], xr[k][1], okr[k]);
+      else if constexpr (has_next) load_x(nxt, mn - BP_NKM, xr[k][0], xr[k][1], okr[k]);   // the next tile's k-steps 0..3
+      constexpr int ks2 = BP_NKR + (m - BP_NK1);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const h8 ah = w2[((ks2 * 2 + j) * 2 + 0) * 64];
-          const h8 al = w2[((ks2 * 2 + j) * 2 + 1) * 64];
-          mfma3(ah, al, bh, bl, acc[j]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      });
-    }
+      for (int j = 0; j < 2; ++j) {
+        const h8 ah = w2[((ks2 * 2 + j) * 2 + 0) * 64];
+        const h8 al = w2[((ks2 * 2 + j) * 2 + 1) * 64];
+        mfma3(ah, al, bh, bl, acc[j]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    });
     // epilogue 2: gate derivative (filter half -> columns 0..63, gate half -> columns 64..127 of g_u)
 #pragma unroll
     for (int part = 0; part < 2; ++part)
@@ -238,9 +252,23 @@ __global__ __launch_bounds__(512, 2) void wn_bwd_pair_kernel(WnBwdPairArgs a) {
             wmax_u = fmaxf(wmax_u, fabsf(v));
           }
         }
-        if (cur.rows_valid > 0) bp_store32(o, stage, a.gu_out + cur.row0 * 128 + 64 * part + 32 * j, 128, cur.rows_valid, lane);
+        bp_store32(o, stage, a.gu_out + row0 * 128 + 64 * part + 32 * j, 128, rows_valid, lane);
       }
-    if (has_next) cur = nxt;
+    if constexpr (has_next) cur = nxt;
+  };
+  using Next = std::true_type;
+  using Last = std::false_type;
+  using First = std::true_type;
+  using Later = std::false_type;                          // enters with k-steps 0..3 requested and the last 16 g_u stores in flight
+  if (walk.first < walk.end) {
+    int64_t tile = walk.first;
+    if (tile + walk.stride < walk.end) {
+      do_tile(tile, Next{}, First{});
+      for (tile += walk.stride; tile + walk.stride < walk.end; tile += walk.stride) do_tile(tile, Next{}, Later{});
+      do_tile(tile, Last{}, Later{});
+    } else {
+      do_tile(tile, Last{}, First{});                     // the wave's only tile (every launch of up to 2048 tiles)
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {

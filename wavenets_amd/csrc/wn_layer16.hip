@@ -32,40 +32,6 @@ struct WnL16 {
   static constexpr int LDS_BYTES = WD_BYTES + WR_BYTES + WAVES * STAGE_BYTES + BIAS_BYTES;
 };
 
-// tile (32 rows x C floats) held as D-layout registers -> LDS stage -> coalesced rows in HBM.
-// The rows leave as buffer stores on a descriptor that ends behind the tile's last valid row (dst and rows_valid are
-// wave-uniform): the hardware drops the rows of a ragged tile, and no store sits in a branch.  As `if (row < rows_valid)`
-// around a global store every store had an exec-skip branch of its own, and hipcc's wait counts behind them are those of
-// the path that stored nothing: requests made before a tile's stores could not be told from the stores (vmcnt(15) where
-// 38 were allowed).
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-template <int C32, int PITCH>
-__device__ __forceinline__ void wn_store_tile(const f32x16 (&v)[C32], float* stage, float* dst, int ld, int rows_valid, int lane) {
-  const int tl = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int j = 0; j < C32; ++j)
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      f32x4 o;
-      o.x = v[j][4 * rq + 0]; o.y = v[j][4 * rq + 1]; o.z = v[j][4 * rq + 2]; o.w = v[j][4 * rq + 3];
-      *reinterpret_cast<f32x4*>(stage + tl * PITCH + 32 * j + 8 * rq + 4 * h) = o;
-    }
-  // LDS instructions of one wave execute in order, so the reads below see every lane's writes;
-  // the asm statements only stop the compiler from moving LDS accesses across the two phases
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  constexpr int LPR = C32 * 8;                 // lanes (16-byte pieces) per row
-  constexpr int RPI = 64 / LPR;                // rows per store instruction
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, rows_valid * ld * 4, 0x00020000);
-#pragma unroll
-  for (int i = 0; i < 32 / RPI; ++i) {
-    const int row = i * RPI + lane / LPR;
-    const int col = (lane % LPR) * 4;
-    const f32x4 o = *reinterpret_cast<const f32x4*>(stage + row * PITCH + col);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs, (row * ld + col) * 4, 0, 0);
-  }
-  asm volatile("" ::: "memory");
-}
-
 // FAST = the plain training / inference call (taps from x with the block's dilation, no conditioning bias,
 // residual from the newest tap, z written, no separate pre-residual output): the optional paths and
 // their registers are compiled out.  FAST == 2 additionally saves the sigmoid (training); FAST == 3 is FAST == 2 with the
