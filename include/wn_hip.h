@@ -368,10 +368,33 @@ int64_t wn_layer_workspace_floats(const wn_layer_desc* d, int32_t B, int32_t T);
 int wn_layer_fwd(const wn_layer_desc* d, const float* params, const float* x, const float* cond,
                  int32_t B, int32_t T, float* x_out, float* skip_out, float* saved,
                  float* workspace, void* stream);
+/* Backward of the wn_layer_fwd call that filled `saved` (same d, params, x, cond, B, T):
+ * gradients of <g_x_out, x_out> + <g_skip, skip_out>.  g_x_out (B,T,R), g_skip (B,T,S), or (B,T,R) when skip_channels is 0
+ * (the skip output is then the 1x1 conv's output before the residual is added).
+ *   g_x_out == NULL  x_out does not enter the objective: no residual term in g_x; with skip_channels > 0 conv1 gets no
+ *                    gradient and dW_r, db_r are written as zeros (with skip_channels 0 they come from g_skip).
+ *   g_skip == NULL   skip_out does not enter the objective: with skip_channels > 0 dW_s, db_s are written as zeros.
+ *   both NULL        the gradient at u is zero: every element of g_params, g_x and g_cond is written as zero.
+ *   both given, skip_channels 0: the 1x1 conv's output gradient is g_x_out + g_skip (formed in the workspace).
+ *   g_x == NULL      the input gradient is not formed: the backward-data product of the stack's first conv is not run (those
+ *                    of the convs above it still are: the weight gradients below them need their results).  Nothing else
+ *                    changes.
+ *   g_cond == NULL   the condition's gradient is not formed; dW_c, db_c and everything else are unchanged.
+ * g_params (wn_layer_param_count floats, the layout of params): EVERY element is written by every call, overwritten and
+ * not accumulated; the caller need not clear it.  g_x (B,T,in_channels) and g_cond (B,T,Cc) likewise where given.
+ * workspace: wn_layer_workspace_floats(d, B, T) floats; nothing in it is carried from the forward call to this one. */
 int wn_layer_bwd(const wn_layer_desc* d, const float* params, const float* x, const float* cond,
                  const float* saved, const float* g_x_out, const float* g_skip, int32_t B, int32_t T,
                  float* g_x, float* g_cond, float* g_params, float* workspace, void* stream);
 int64_t wn_layer_param_count(const wn_layer_desc* d);
+/* test / diagnosis hook, host only: one line naming every weight-gradient product wn_layer_bwd launches over (B, T) when
+ * both output gradients are given, in launch order -- conv1, conv_skip, conv_cond, then the stack from its last conv to its
+ * first, one product per tap (`dil<i>.tap<j>`) -- separated by " | ", each as
+ *   <name> K=<rows of dW> N=<columns of dW> splits=<time ranges per utterance> nsplit=<B * splits> reduce=one-stage|two-stage
+ * computed by the functions the launches themselves call (the split heuristic and the reduce's stage decision).
+ * WN_E_INVALID: a bad descriptor, B < 1 or T < 1, a null buffer or len < 1, or a buffer too short for the line (the message
+ * names the bytes needed; buf then holds the truncated, terminated text). */
+int wn_layer_describe(const wn_layer_desc* d, int32_t B, int32_t T, char* buf, int32_t len);
 
 /* ---- elementwise pieces of the boundary ---- */
 /* prepare_target = Discretization (tf Bucketize), src/model.py:151-153: bit-exact indices */

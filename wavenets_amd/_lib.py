@@ -125,6 +125,7 @@ _SIGS = {
     'wn_layer_fwd': (C.c_int, [C.POINTER(WnLayerDesc), _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     'wn_layer_bwd': (C.c_int, [C.POINTER(WnLayerDesc), _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P,
                                _P, _P, _P]),
+    'wn_layer_describe': (C.c_int, [C.POINTER(WnLayerDesc), C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
     'wn_quantize': (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     'wn_dequantize': (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     'wn_mulaw': (C.c_int, [_P, _P, C.c_int64, _P]),

@@ -4,14 +4,24 @@
 
 namespace wnp {
 
+// the time split of one K x N weight-gradient product as wgrad() launches it (wn_layer_describe reads the same)
+struct WgradSplit { int per_b, nsplit; };
+static WgradSplit wgrad_split(int B, int T, int K, int N) {
+  WgradSplit w;
+  w.per_b = wn_wgrad_choose_splits(B, T, K, N);
+  w.nsplit = B * w.per_b;
+  return w;
+}
+
 // dW (+ optional db, + optional per-utterance column sums) through slabs
 int wgrad(const float* x, int ldx, int K, int shift, const float* g, int ldg, int N, int B, int T,
           float* dW, float* db, float* per_batch, float* slab, hipStream_t s) {
   WnWgradArgs a;
   memset(&a, 0, sizeof(a));
   a.x = x; a.ldx = ldx; a.K = K; a.shift = shift; a.g = g; a.ldg = ldg; a.N = N; a.B = B; a.T = T;
-  a.splits_per_b = wn_wgrad_choose_splits(B, T, K, N);
-  const int nsplit = B * a.splits_per_b;
+  const WgradSplit w = wgrad_split(B, T, K, N);
+  a.splits_per_b = w.per_b;
+  const int nsplit = w.nsplit;
   a.slab = slab;
   a.slab_bias = (db || per_batch) ? slab + (int64_t)nsplit * K * N : nullptr;
   int rc = wn_launch_wgrad(a, s);
@@ -451,6 +461,38 @@ extern "C" int64_t wn_layer_workspace_floats(const wn_layer_desc* d, int32_t B, 
   LayerLayout L;
   if (layer_layout(d, B, T, L)) return -1;
   return L.ws_total;
+}
+
+// The weight-gradient products of wn_layer_bwd over (B, T) and how each is split over time and reduced: the products in
+// the order block_backward launches them, K and N as it passes them to wgrad(), the split from wgrad_split() and the
+// reduce form from wn_reduce_two_stage() -- the functions the launches themselves read (host only).
+extern "C" int wn_layer_describe(const wn_layer_desc* d, int32_t B, int32_t T, char* buf, int32_t len) {
+  if (!buf || len < 1) { wn_set_error("layer_describe: no buffer"); return WN_E_INVALID; }
+  buf[0] = 0;
+  if (B < 1 || T < 1) { wn_set_error("layer_describe: B and T must be at least 1"); return WN_E_INVALID; }
+  LayerLayout L;
+  int rc = layer_layout(d, B, T, L);
+  if (rc) return rc;
+  const int R = d->channels, D = d->dilation_channels > 0 ? d->dilation_channels : R;
+  std::string out;
+  auto add = [&](const std::string& name, int K, int N) {
+    const WgradSplit w = wgrad_split(B, T, K, N);
+    char item[160];
+    snprintf(item, sizeof(item), "%s%s K=%d N=%d splits=%d nsplit=%d reduce=%s", out.empty() ? "" : " | ", name.c_str(), K, N,
+             w.per_b, w.nsplit, wn_reduce_two_stage(w.nsplit) ? "two-stage" : "one-stage");
+    out += item;
+  };
+  add("conv1", D, R);
+  if (d->skip_channels > 0) add("conv_skip", D, d->skip_channels);
+  if (d->cond_channels > 0) add("conv_cond", d->cond_channels, 2 * D);
+  for (int i = d->depth - 1; i >= 0; --i)
+    for (int t = 0; t < d->kernel_size; ++t) add("dil" + std::to_string(i) + ".tap" + std::to_string(t), L.cin[i], L.cout[i]);
+  snprintf(buf, (size_t)len, "%s", out.c_str());
+  if ((int64_t)out.size() + 1 > (int64_t)len) {
+    wn_set_error("layer_describe: the line needs %d bytes, the buffer has %d", (int)out.size() + 1, (int)len);
+    return WN_E_INVALID;
+  }
+  return WN_OK;
 }
 
 extern "C" int wn_layer_fwd(const wn_layer_desc* d, const float* params, const float* x, const float* cond,

@@ -747,13 +747,15 @@ __global__ void wn_reduce_kernel(WnReduceArgs a, int stride) {
   }
 }
 
+int wn_reduce_two_stage(int nsplit) { return nsplit > 2 * WN_RED_GROUP ? 1 : 0; }
+
 int wn_launch_reduce(const WnReduceArgs& a, hipStream_t s) {
   const int64_t total = (int64_t)a.K * a.N;
   if (total <= 0) return WN_OK;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 2048) blocks = 2048;
   int stride = 1;
-  if (a.nsplit > 2 * WN_RED_GROUP) {
+  if (wn_reduce_two_stage(a.nsplit)) {
     const int groups = (a.nsplit + WN_RED_GROUP - 1) / WN_RED_GROUP;
     hipLaunchKernelGGL(wn_reduce_stageA_kernel, dim3(blocks, groups), dim3(256), 0, s,
                        const_cast<float*>(a.slab), a.nsplit, total);

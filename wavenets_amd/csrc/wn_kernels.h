@@ -203,6 +203,8 @@ struct WnReduceArgs {
   int32_t replicate; int64_t rep_stride;   // write the same result to `replicate` places
 };
 int wn_launch_reduce(const WnReduceArgs& a, hipStream_t s);
+// whether wn_launch_reduce folds nsplit slabs in two stages (groups first, then the group rows); host only
+int wn_reduce_two_stage(int nsplit);
 
 // ---------------------------------------------------------------- fused residual block forward
 struct WnLayerFwdArgs {
