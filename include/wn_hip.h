@@ -335,6 +335,48 @@ int wn_generate_sampled(wn_plan* p, const float* params, const float* window, co
 int wn_generate_chunk(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                       int64_t first, int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
                       float* out, float* workspace, int64_t ws_floats, void* stream);
+/* ---- sampling controls per utterance ----
+ * One generate call, B utterances, each with its own temperature, top_k, top_p, seed and Philox stream.
+ * struct wn_sampling_row is the packed record of one utterance: what the check of struct wn_sampling leaves for the
+ * kernels (T, 1 / T, the effective top_k: 0 for off or >= classes, the effective top_p: 0 for off or 1), the Philox key
+ * `seed`, and `stream`, the row word of the Philox counter: utterance b draws sample t from counter (stream, t) under
+ * key seed.  A table is B records, 8 floats each (wn_sampling_rows_floats), indexed by the utterance index of the call.
+ *
+ * wn_sampling_rows_pack: host only, touches no device.  Checks sampling[0 .. B) by the rules above for `head`
+ *   (WN_HEAD_*) and `classes` (the categorical row length) and writes the B records into the caller's host memory `rows`;
+ *   *flags gets WN_SAMPLING_ROWS_ON when some row has a control on (T != 1, top_k or top_p on) and WN_SAMPLING_ROWS_TOP_P
+ *   when some row has top_p on.  stream: B values below 2^63, or NULL for stream[b] = b.  The first bad row ends it:
+ *   WN_E_INVALID / WN_E_UNSUPPORTED exactly where the check of one struct wn_sampling gives them, and the error text names
+ *   the row ("row 3: ...").  Null sampling / rows / flags, B < 1 and a stream value >= 2^63 are WN_E_INVALID.
+ *
+ * wn_generate_rows_chunk: wn_generate_chunk with `rows`, a DEVICE pointer (16-byte aligned) to the table the caller copied
+ *   there, and the flags the pack function returned, in place of the struct wn_sampling.  The table lies outside the
+ *   generation workspace (workspace size, state range and guard slot are those of wn_generate_chunk) and is only read;
+ *   it must stay as it is until the call's work on the stream is done, and a continuation passes the same table.  The
+ *   rules for window / first and the guarantee that the pieces of a sequence concatenated are the one call carry over
+ *   word for word, and so do the errors, after: rows null, rows misaligned, flags that no pack call returns.
+ *   The step's kernels are chosen once per call from the flags, i.e. from the union of the rows: with top_p on in some
+ *   row the draw of every row is the sampler launch's.  Every stochastic draw reads the record of its utterance, whichever
+ *   workgroup or tile the utterance falls into.
+ * The defining property: utterance b of such a call, with stream[b] = b, is bit for bit utterance b of
+ *   wn_generate_chunk at the same B, window, cond with {T[b], top_k[b], seed[b], top_p[b]}; a row whose controls are all off
+ *   takes the draw without controls.  So a table of equal rows with streams 0 .. B - 1 gives wn_generate_chunk's result.
+ *   Rows with equal window, cond, key and stream make equal samples.  (The samples of an utterance depend on nothing
+ *   but its own row of window and cond, its record, and the weights -- not on its index, not on B: DESIGN.md section 31
+ *   says what was checked.)
+ * deterministic != 0 ignores the table's controls, keys and streams (arg max / mode), as it ignores struct wn_sampling.
+ * Out of scope: per-row controls in wn_sample_waveform_sampled and in the training step's metric draw; a per-row
+ *   deterministic flag (top_k = 1 on a categorical row is the arg max); changing B inside a sequence. */
+typedef struct wn_sampling_row { float T, inv_T; int32_t top_k; float top_p; uint64_t seed, stream; } wn_sampling_row;
+#define WN_SAMPLING_ROWS_ON 1
+#define WN_SAMPLING_ROWS_TOP_P 2
+int64_t wn_sampling_rows_floats(int32_t B);
+int wn_sampling_rows_pack(const wn_sampling* sampling, const uint64_t* stream, int32_t B, int32_t head, int32_t classes,
+                          wn_sampling_row* rows, int32_t* flags);
+int wn_generate_rows_chunk(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                           int64_t first, int32_t length, int32_t deterministic, int32_t queued,
+                           const wn_sampling_row* rows, int32_t rows_flags, float* out, float* workspace,
+                           int64_t ws_floats, void* stream);
 int64_t wn_generate_workspace_floats(const wn_plan* p, int32_t B, int32_t queued);
 /* The one contiguous part of the generation workspace that steps write and a continuation reads, as a float offset and a
  * float count.  queued: from the raw-sample slots to the end of the layout (rings, inner rings, per-step rows, partial

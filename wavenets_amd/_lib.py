@@ -42,6 +42,15 @@ class WnSampling(C.Structure):
   _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('seed', C.c_uint64), ('top_p', C.c_float)]
 
 
+class WnSamplingRow(C.Structure):
+  """struct wn_sampling_row (include/wn_hip.h): the controls of one utterance as the kernels read them, 8 floats."""
+  _fields_ = [('T', C.c_float), ('inv_T', C.c_float), ('top_k', C.c_int32), ('top_p', C.c_float), ('seed', C.c_uint64),
+              ('stream', C.c_uint64)]
+
+
+WN_SAMPLING_ROWS_ON, WN_SAMPLING_ROWS_TOP_P = 1, 2
+
+
 class WnLayerDesc(C.Structure):
   """struct wn_layer_desc == WaveNetLayer constructor keywords, src/layers.py:10-20."""
   _fields_ = [
@@ -116,6 +125,11 @@ _SIGS = {
                                       _P, C.c_int64, _P]),
     'wn_generate_chunk': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                     C.POINTER(WnSampling), _P, _P, C.c_int64, _P]),
+    'wn_sampling_rows_floats': (C.c_int64, [C.c_int32]),
+    'wn_sampling_rows_pack': (C.c_int, [C.POINTER(WnSampling), C.POINTER(C.c_uint64), C.c_int32, C.c_int32, C.c_int32,
+                                        C.POINTER(WnSamplingRow), C.POINTER(C.c_int32)]),
+    'wn_generate_rows_chunk': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P,
+                                         C.c_int32, _P, _P, C.c_int64, _P]),
     'wn_generate_state_range': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'wn_generate_workspace_floats': (C.c_int64, [_P, C.c_int32, C.c_int32]),
     'wn_generate_guard_slot': (C.c_int64, [_P, C.c_int32, C.c_int32]),

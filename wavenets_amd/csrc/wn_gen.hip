@@ -612,7 +612,11 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
 // the next layer through LDS, exactly as the chain kernel hands x between blocks.  Per tile this is the
 // thin rows GEMM's sequence -- k-steps in order, lo*hi, hi*lo, hi*hi, then acc + bias, activation -- so
 // the logits are bit-identical to the per-layer launches (and to the sliding window).
-__device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, unsigned char* smem) {
+// ROWS: the sampling tails draw with the utterance's own record rows[utt] (per-row controls);
+// false is the body of before, instruction for instruction.
+template <bool ROWS = false>
+__device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, unsigned char* smem,
+                                             const WnSampleRow* rows = nullptr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int tl = lane & 31, h = lane >> 5;
   const int utt = tile * 32 + tl;
@@ -764,9 +768,13 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
       const int row = tile * 32 + (int)threadIdx.x;
       if (row < a.B) {
         const float* p = lg + threadIdx.x * 32;
-        const float v = a.tail == 3 ? wn_mix_det_row(p, a.mix_M)
-                        : a.ctl.on() ? wn_mix_rand_row<true>(p, a.mix_M, a.mix_kind, row, a.seed, a.offset, a.ctl)
-                                     : wn_mix_rand_row(p, a.mix_M, a.mix_kind, row, a.seed, a.offset);
+        float v;
+        if constexpr (ROWS)         // (row is the global utterance index: tile * 32 + thread)
+          v = a.tail == 3 ? wn_mix_det_row(p, a.mix_M) : wn_mix_rand_row_tab(p, a.mix_M, a.mix_kind, rows, row, a.offset);
+        else
+          v = a.tail == 3 ? wn_mix_det_row(p, a.mix_M)
+              : a.ctl.on() ? wn_mix_rand_row<true>(p, a.mix_M, a.mix_kind, row, a.seed, a.offset, a.ctl)
+                           : wn_mix_rand_row(p, a.mix_M, a.mix_kind, row, a.seed, a.offset);
         if (a.samp) a.samp[row] = v;
         wn_emit_sample(a.em, row, v);
       }
@@ -786,9 +794,14 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
       const float* l = a.ws + a.out_off + (int64_t)row * C;
       // (a.ctl is a kernel argument: the branch on the sampling controls is uniform, and off takes the draw of before;
       // a step under top_p takes the sampler launch instead of this tail, gn_head_check)
-      const float v = a.tail == 1 ? wn_cat_det_row(l, C, lane, a.inv_lv)
-                      : a.ctl.on() ? wn_cat_rand_row<true, false>(l, C, lane, q, row, a.seed, a.offset, a.inv_lv, a.ctl)
-                                   : wn_cat_rand_row(l, C, lane, q, row, a.seed, a.offset, a.inv_lv);
+      float v;
+      if constexpr (ROWS)           // (the record of the global utterance index, in scalar registers: uniform branches)
+        v = a.tail == 1 ? wn_cat_det_row(l, C, lane, a.inv_lv)
+                        : wn_cat_rand_row_tab<false>(l, C, lane, q, wn_sample_row_uniform(rows, row), a.offset, a.inv_lv);
+      else
+        v = a.tail == 1 ? wn_cat_det_row(l, C, lane, a.inv_lv)
+            : a.ctl.on() ? wn_cat_rand_row<true, false>(l, C, lane, q, row, a.seed, a.offset, a.inv_lv, a.ctl)
+                         : wn_cat_rand_row(l, C, lane, q, row, a.seed, a.offset, a.inv_lv);
       if (lane == 0) {
         if (a.samp) a.samp[row] = v;
         wn_emit_sample(a.em, row, v);
@@ -814,6 +827,24 @@ __global__ __launch_bounds__(512) void wn_gen_head_pre_kernel(WnGenHeadArgs ha, 
     gn_pre_body<R32, D32, KS>(ga, j % ntiles, j / ntiles, ntiles);
   }
 }
+// The per-row twins of the two kernels above (rows: the table, gn_head_body<true>); R32 = 0: the head alone, ga unused.
+// One template, first used at the END of this file (gn_launch_head_rows): the compiler emits instantiations in the order
+// of their first use, so the twins land behind every kernel of before in the code object and those keep their offsets.
+template <int R32, int D32, int KS>
+__global__ __launch_bounds__(512) void wn_gen_head_rows_kernel(WnGenHeadArgs ha, WnGenStepArgs ga, int ntiles,
+                                                                const WnSampleRow* rows) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 16 * 2048];
+  if (R32 == 0 || (int)blockIdx.x < ntiles) {
+    gn_head_body<true>(ha, (int)blockIdx.x, smem, rows);
+  } else if constexpr (R32 > 0) {
+    if (threadIdx.x >= 64) return;
+    const int j = (int)blockIdx.x - ntiles;
+    gn_pre_body<R32, D32, KS>(ga, j % ntiles, j / ntiles, ntiles);
+  }
+}
+// (defined at the end of the file) the launch of the twin for (R, KS), or R = 0 for the head alone; false: unsupported shape
+static bool gn_launch_head_rows(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, dim3 grid, int nt, hipStream_t s,
+                                const WnSampleRow* tab);
 
 static int gn_head_check(const WnGenHeadArgs& a) {
   if (a.nlayers < 1 || a.nlayers > WN_GEN_HEAD_MAX) { wn_set_error("gen_head: bad layer count"); return WN_E_UNSUPPORTED; }
@@ -823,15 +854,18 @@ static int gn_head_check(const WnGenHeadArgs& a) {
       return WN_E_UNSUPPORTED;
     }
   if ((a.tail == 2 || a.tail == 4) && !(a.ctl.inv_T > 0.f)) { wn_set_error("gen_head: sampling controls not set"); return WN_E_INVALID; }
+  // (per-row controls: a.ctl is the union of the rows, so this reads "no row of the table has top_p on")
   if (a.tail == 2 && a.ctl.top_p > 0.f) { wn_set_error("gen_head: a draw under top_p takes the sampler launch, not this tail"); return WN_E_INVALID; }
   return WN_OK;
 }
-int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, hipStream_t s) {
+int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, hipStream_t s, const WnSampleRow* tab) {
   const int rc = gn_head_check(a);
   if (rc) return rc;
   const int nt = (a.B + 31) / 32;
   const dim3 grid((unsigned)(nt + nt * g.nblocks));
-  if (R == 32 && KS == 2) hipLaunchKernelGGL((wn_gen_head_pre_kernel<1, 1, 2>), grid, dim3(512), 0, s, a, g, nt);
+  if (tab && (a.tail == 2 || a.tail == 4)) {
+    if (!gn_launch_head_rows(a, g, R, KS, grid, nt, s, tab)) { wn_set_error("gen_head_pre: unsupported shape"); return WN_E_UNSUPPORTED; }
+  } else if (R == 32 && KS == 2) hipLaunchKernelGGL((wn_gen_head_pre_kernel<1, 1, 2>), grid, dim3(512), 0, s, a, g, nt);
   else if (R == 32 && KS == 3) hipLaunchKernelGGL((wn_gen_head_pre_kernel<1, 1, 3>), grid, dim3(512), 0, s, a, g, nt);
   else if (R == 64 && KS == 2) hipLaunchKernelGGL((wn_gen_head_pre_kernel<2, 2, 2>), grid, dim3(512), 0, s, a, g, nt);
   else { wn_set_error("gen_head_pre: unsupported shape"); return WN_E_UNSUPPORTED; }
@@ -839,7 +873,7 @@ int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R
   return WN_OK;
 }
 
-int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s) {
+int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s, const WnSampleRow* tab) {
   const int rc = gn_head_check(a);
   if (rc) return rc;
   if (a.f32_K > 0 && (a.f32_K != a.N[a.nlayers - 1] || a.f32_K % 64 != 0 || a.f32_N < 1 || a.f32_N > 32 ||
@@ -848,7 +882,10 @@ int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s) {
     return WN_E_UNSUPPORTED;
   }
   if (a.f32_K == 0 && a.tail >= 3) { wn_set_error("gen_head: the mixture tail follows the fp32 layer"); return WN_E_UNSUPPORTED; }
-  hipLaunchKernelGGL(wn_gen_head_kernel, dim3((unsigned)((a.B + 31) / 32)), dim3(512), 0, s, a);
+  if (tab && (a.tail == 2 || a.tail == 4))
+    gn_launch_head_rows(a, WnGenStepArgs{}, 0, 0, dim3((unsigned)((a.B + 31) / 32)), (a.B + 31) / 32, s, tab);
+  else
+    hipLaunchKernelGGL(wn_gen_head_kernel, dim3((unsigned)((a.B + 31) / 32)), dim3(512), 0, s, a);
   WN_HIP_CHECK(hipGetLastError());
   return WN_OK;
 }
@@ -900,4 +937,14 @@ int wn_launch_gen_blocks(const WnGenStepArgs& a, int R, int KS, int what, hipStr
   else { wn_set_error("gen_blocks: unsupported shape"); return WN_E_UNSUPPORTED; }
   WN_HIP_CHECK(hipGetLastError());
   return WN_OK;
+}
+
+static bool gn_launch_head_rows(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, dim3 grid, int nt, hipStream_t s,
+                                const WnSampleRow* tab) {
+  if (R == 0) hipLaunchKernelGGL((wn_gen_head_rows_kernel<0, 0, 0>), grid, dim3(512), 0, s, a, g, nt, tab);
+  else if (R == 32 && KS == 2) hipLaunchKernelGGL((wn_gen_head_rows_kernel<1, 1, 2>), grid, dim3(512), 0, s, a, g, nt, tab);
+  else if (R == 32 && KS == 3) hipLaunchKernelGGL((wn_gen_head_rows_kernel<1, 1, 3>), grid, dim3(512), 0, s, a, g, nt, tab);
+  else if (R == 64 && KS == 2) hipLaunchKernelGGL((wn_gen_head_rows_kernel<2, 2, 2>), grid, dim3(512), 0, s, a, g, nt, tab);
+  else return false;
+  return true;
 }

@@ -96,7 +96,7 @@ __global__ void wn_gen_emit_kernel(const float* samp, int B, float* out, int len
 
 // sample from the logits rows [B][Cout] (src/model.py:253-255 + sample_waveform)
 int sample_rows(wn_plan* p, const float* logits_rows, int B, bool deterministic, uint64_t seed, uint64_t step,
-                float* probs_tmp, float* samp, hipStream_t s, WnSampleCtl ctl) {
+                float* probs_tmp, float* samp, hipStream_t s, WnSampleCtl ctl, const WnSampleRow* tab = nullptr) {
   const float* pred = logits_rows;
   int rc;
   if (p->c.head == WN_HEAD_CATEGORICAL) {
@@ -105,7 +105,7 @@ int sample_rows(wn_plan* p, const float* logits_rows, int B, bool deterministic,
     pred = probs_tmp;
   }
   if (deterministic) return wn_launch_sample_det(pred, B, p->Cout, p->c.num_mixtures, p->c.bits, samp, s);
-  return wn_launch_sample_rand(pred, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, step, samp, s, ctl);
+  return wn_launch_sample_rand(pred, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, step, samp, s, ctl, WN_EMIT_NONE, tab);
 }
 
 // the compute units of the current device (-1: unknown)
@@ -160,6 +160,10 @@ struct GenCall {
   wn_plan* p; const float* params; const float* cond; int B, length; bool deterministic;
   int first, end, step0;             // the call's steps are [first, end); step0: the first one that is not the priming pass
   uint64_t seed; WnSampleCtl ctl;    // the sampling controls
+  // per-row controls (wn_generate_rows_chunk): the caller's device table, one record per utterance, or null.  With a
+  // table every stochastic draw of the call -- sliding window, priming step, sampler launch, head tail -- reads its row's
+  // record; ctl is the union of the rows (what gen_paths and the launchers' checks look at) and seed is unused.
+  const WnSampleRow* rows = nullptr;
   float* out; float* ws; hipStream_t s;
   int RF;
   GenLayout G;
@@ -226,7 +230,7 @@ struct GenCall {
     for (int step = first; step < end; ++step) {
       int rc = window_forward(win[step & 1], step == 0, nullptr);
       if (rc) return rc;
-      rc = sample_rows(p, last, B, deterministic, seed, (uint64_t)step, lastp, samp, s, ctl);
+      rc = sample_rows(p, last, B, deterministic, seed, (uint64_t)step, lastp, samp, s, ctl, rows);
       if (rc) return rc;
       hipLaunchKernelGGL(wn_gen_shift_kernel, dim3((B * RF + 255) / 256), dim3(256), 0, s, win[step & 1], samp, B, RF,
                          win[(step + 1) & 1], out, length, step - first);
@@ -241,7 +245,7 @@ struct GenCall {
   int prime() {
     int rc = window_forward(win[0], true, &R);
     if (rc) return rc;
-    rc = sample_rows(p, last, B, deterministic, seed, 0, lastp, samp, s, ctl);
+    rc = sample_rows(p, last, B, deterministic, seed, 0, lastp, samp, s, ctl, rows);
     if (rc) return rc;
     // sample 0 is x[RF]; it becomes the network input at time tau = RF
     hipLaunchKernelGGL(wn_gen_emit_kernel, dim3((B + 255) / 256), dim3(256), 0, s, samp, B, out, length, 0, emit(0).xin_slot);
@@ -409,9 +413,9 @@ struct GenCall {
       if (ha.tail) { ha.offset = (uint64_t)step; ha.em = emit(step); }
       if (gp.pre_in_head && step + 1 < end) {
         ga.tau = tau(step) + 1;
-        return wn_launch_gen_head_pre(ha, ga, p->R, p->KS, s);
+        return wn_launch_gen_head_pre(ha, ga, p->R, p->KS, s, rows);
       }
-      return wn_launch_gen_head(ha, s);
+      return wn_launch_gen_head(ha, s, rows);
     }
     const float* in = hin;
     int hc = gp.hc0;
@@ -438,10 +442,10 @@ struct GenCall {
       case GEN_SAMPLE_DET:
         return wn_launch_sample_det(last, B, p->Cout, p->c.num_mixtures, p->c.bits, cat ? nullptr : samp, s, emit(step));
       case GEN_SAMPLE_RAND:
-        return wn_launch_sample_rand(last, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, (uint64_t)step, samp, s, ctl, emit(step));
+        return wn_launch_sample_rand(last, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, (uint64_t)step, samp, s, ctl, emit(step), rows);
       case GEN_SAMPLE_ROWS: break;
     }
-    const int rc = sample_rows(p, last, B, false, seed, (uint64_t)step, lastp, samp, s, ctl);
+    const int rc = sample_rows(p, last, B, false, seed, (uint64_t)step, lastp, samp, s, ctl, rows);
     if (rc) return rc;
     hipLaunchKernelGGL(wn_gen_emit_kernel, dim3((B + 255) / 256), dim3(256), 0, s, samp, B, out, length, step - first, emit(step).xin_slot);
     WN_HIP_CHECK(hipGetLastError());
@@ -507,11 +511,18 @@ extern "C" int wn_generate(wn_plan* p, const float* params, const float* window,
 }
 
 // wn_generate_sampled (window given, first = 0) and wn_generate_chunk
+// ... and wn_generate_rows_chunk: rows (device) in place of sampling, with the union of its rows from rows_flags
 static int generate_call(bool chunk, wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                          int64_t first, int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
-                         float* out, float* workspace, int64_t ws_floats, void* stream) {
+                         float* out, float* workspace, int64_t ws_floats, void* stream,
+                         const WnSampleRow* rows = nullptr, int32_t rows_flags = 0) {
   WnSampleCtl ctl = WN_SAMPLE_CTL_OFF;
-  {
+  if (rows) {
+    // the union of the rows as a WnSampleCtl: on() when some row is on, top_p > 0 when some row has top_p on (the values
+    // stand for "on" only: the kernels read the rows)
+    if (rows_flags & WN_SAMPLING_ROWS_ON) { ctl.T = 2.0f; ctl.inv_T = 0.5f; }
+    if (rows_flags & WN_SAMPLING_ROWS_TOP_P) ctl.top_p = 0.5f;
+  } else {
     const int rc = wn_sampling_check("generate", sampling, p ? p->c.head : WN_HEAD_CATEGORICAL, p ? p->Cout : 0x7fffffff, &ctl);
     if (rc) return rc;
   }
@@ -533,7 +544,8 @@ static int generate_call(bool chunk, wn_plan* p, const float* params, const floa
   if (ws_floats < G.total) { wn_set_error("generate: workspace too small"); return WN_E_INVALID; }
   if (length == 0) return WN_OK;
   GenCall c{wnp::ex(p)};
-  c.bind(p, params, cond, B, (int)first, length, deterministic != 0, sampling->seed, ctl, out, workspace, (hipStream_t)stream, std::move(G));
+  c.bind(p, params, cond, B, (int)first, length, deterministic != 0, rows ? 0 : sampling->seed, ctl, out, workspace, (hipStream_t)stream, std::move(G));
+  c.rows = rows;
   int rc = c.begin(window);
   if (rc) return rc;
   if (!queued) return c.sliding_window();
@@ -577,4 +589,53 @@ extern "C" int wn_generate_state_range(const wn_plan* p, int32_t B, int32_t queu
   *offset = queued ? G.xin : G.win0;
   *floats = queued ? G.total - G.xin : G.win1 + (int64_t)B * wn_plan_receptive_field(p) - G.win0;
   return WN_OK;
+}
+
+// ---- per-row sampling controls (include/wn_hip.h, struct wn_sampling_row) ----
+static_assert(sizeof(wn_sampling_row) == sizeof(WnSampleRow) && offsetof(wn_sampling_row, seed) == offsetof(WnSampleRow, seed) &&
+              offsetof(wn_sampling_row, stream) == offsetof(WnSampleRow, stream) && offsetof(wn_sampling_row, top_p) == offsetof(WnSampleRow, top_p),
+              "wn_sampling_row is WnSampleRow");
+
+extern "C" int64_t wn_sampling_rows_floats(int32_t B) {
+  return B < 1 ? 0 : (int64_t)B * (int64_t)(sizeof(wn_sampling_row) / sizeof(float));
+}
+
+extern "C" int wn_sampling_rows_pack(const wn_sampling* sampling, const uint64_t* stream, int32_t B, int32_t head, int32_t classes,
+                                     wn_sampling_row* rows, int32_t* flags) {
+  if (!sampling || !rows || !flags || B < 1) {
+    wn_set_error("sampling_rows_pack: bad arguments (sampling, rows and flags must not be null, B >= 1; got B = %d)", (int)B);
+    return WN_E_INVALID;
+  }
+  int32_t f = 0;
+  for (int32_t b = 0; b < B; ++b) {
+    char who[48];
+    snprintf(who, sizeof(who), "sampling_rows_pack: row %d", (int)b);
+    WnSampleCtl ctl = WN_SAMPLE_CTL_OFF;
+    const int rc = wn_sampling_check(who, sampling + b, head, classes, &ctl);
+    if (rc) return rc;
+    const uint64_t st = stream ? stream[b] : (uint64_t)b;
+    if (st >> 63) {
+      wn_set_error("sampling_rows_pack: row %d: stream must be below 2^63 (got %llu)", (int)b, (unsigned long long)st);
+      return WN_E_INVALID;
+    }
+    rows[b] = wn_sampling_row{ctl.T, ctl.inv_T, ctl.top_k, ctl.top_p, sampling[b].seed, st};
+    if (ctl.on()) f |= WN_SAMPLING_ROWS_ON;
+    if (ctl.top_p > 0.f) f |= WN_SAMPLING_ROWS_TOP_P;
+  }
+  *flags = f;
+  return WN_OK;
+}
+
+extern "C" int wn_generate_rows_chunk(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                                      int64_t first, int32_t length, int32_t deterministic, int32_t queued,
+                                      const wn_sampling_row* rows, int32_t rows_flags, float* out, float* workspace,
+                                      int64_t ws_floats, void* stream) {
+  if (!rows) { wn_set_error("generate: rows is null (the device table of wn_sampling_rows_pack)"); return WN_E_INVALID; }
+  if ((uintptr_t)rows % 16 != 0) { wn_set_error("generate: rows must be aligned to 16 bytes"); return WN_E_INVALID; }
+  if (rows_flags & ~(WN_SAMPLING_ROWS_ON | WN_SAMPLING_ROWS_TOP_P) || ((rows_flags & WN_SAMPLING_ROWS_TOP_P) && !(rows_flags & WN_SAMPLING_ROWS_ON))) {
+    wn_set_error("generate: rows_flags must be the flags wn_sampling_rows_pack returned (got %d)", (int)rows_flags);
+    return WN_E_INVALID;
+  }
+  return generate_call(true, p, params, window, cond, B, first, length, deterministic, queued, nullptr, out, workspace, ws_floats, stream,
+                       reinterpret_cast<const WnSampleRow*>(rows), rows_flags);
 }

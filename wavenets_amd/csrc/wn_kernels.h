@@ -311,6 +311,19 @@ struct WnSampleCtl {
   __host__ __device__ bool on() const { return T != 1.0f || top_k > 0 || top_p > 0.f; }
 };
 #define WN_SAMPLE_CTL_OFF (WnSampleCtl{1.0f, 1.0f, 0, 0.f})
+// The controls of one utterance of a generate call with per-row controls (struct wn_sampling_row, include/wn_hip.h; DESIGN.md
+// section 31): WnSampleCtl as wn_sampling_check leaves it, the Philox key and the counter's row word.  A table of B records
+// in device memory, indexed by the GLOBAL utterance index, read by the *_rows kernels (wn_sample.hip, wn_gen.hip) with
+// ordinary loads.  Beside a table every launcher still takes a WnSampleCtl: the union of the rows (on() when some row has
+// a control on, top_p > 0 when some row has top_p on), which the host decides paths and checks from.
+struct WnSampleRow {
+  float T, inv_T;
+  int32_t top_k;
+  float top_p;
+  uint64_t seed, stream;
+  __host__ __device__ WnSampleCtl ctl() const { return WnSampleCtl{T, inv_T, top_k, top_p}; }
+};
+static_assert(sizeof(WnSampleRow) == 32, "WnSampleRow is 8 floats");
 // the head of a generation step in one launch (wn_gen.hip)
 #define WN_GEN_HEAD_MAX 4
 struct WnGenHeadArgs {
@@ -336,13 +349,18 @@ struct WnGenHeadArgs {
   float* guard;                    // range guard of the generate call (hidden activations are cast to fp16 hi | lo), or null
   WnSampleCtl ctl;                 // tails 2 and 4: temperature / top-k, top_p off (set it: all-zero bytes are not 'off')
 };
-int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s);
+// rows (here and in wn_launch_gen_head_pre): per-row controls of tails 2 and 4, [B] records or null.  Non-null launches the
+// *_rows twins of the head kernels, in which utterance u draws with rows[u] (controls, key, counter row); a.ctl is then the
+// union of the rows and a.seed is unused.  The table is a kernel argument of the twins only: WnGenHeadArgs, and with it the
+// argument block of the kernels without a table, is what it was.
+int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s, const WnSampleRow* rows = nullptr);
 int wn_gen_blocks_supported(int R, int D, int KS);
 int wn_gen_chain_max_blocks();
 int64_t wn_gen_u0_floats(int B, int nblocks, int D);
 int wn_gen_skip_fusable(int S);
 int wn_launch_gen_blocks(const WnGenStepArgs& a, int R, int KS, int what, hipStream_t s);
-int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, hipStream_t s);
+int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, hipStream_t s,
+                           const WnSampleRow* rows = nullptr);
 
 // ---------------------------------------------------------------- elementwise (wn_elem.hip)
 int wn_launch_add(const float* a, const float* b, float* out, int64_t n, hipStream_t s);
@@ -430,11 +448,15 @@ int wn_launch_sample_det(const float* pred, int64_t rows, int C, int M, int bits
                          WnEmit em = WN_EMIT_NONE);
 // stochastic samplers (Philox4x32-10 keyed by seed, counter = row)
 int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t seed, uint64_t offset,
-                          float* out, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF, WnEmit em = WN_EMIT_NONE);
+                          float* out, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF, WnEmit em = WN_EMIT_NONE,
+                          const WnSampleRow* tab = nullptr);
+// (tab, here and below: per-row controls -- row r draws with tab[r]'s controls, key and counter row in the *_rows twin of
+// the kernel; seed is unused and ctl is the union of the rows)
 // the categorical draw straight from the logits, for up to WN_SAMPLE_FUSED_MAXC classes
 int wn_sample_from_logits_supported(int C);
 int wn_launch_sample_rand_cat_logits(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
-                                     float* out, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF, WnEmit em = WN_EMIT_NONE);
+                                     float* out, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF, WnEmit em = WN_EMIT_NONE,
+                                     const WnSampleRow* tab = nullptr);
 // top-k is offered for up to this many classes (WN_SAMPLE_FUSED_MAXC, wn_sample.hip)
 int wn_sample_top_k_max_classes();
 

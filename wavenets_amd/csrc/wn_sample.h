@@ -284,3 +284,48 @@ __device__ __forceinline__ float wn_mix_rand_row(const float* p, int M, int kind
   }
   return fminf(fmaxf(v, -1.0f), 1.0f);
 }
+
+
+// ------------------------------------------------------------------------------------------
+// Per-row controls (struct WnSampleRow, wn_kernels.h): row r of a *_rows kernel draws with tab[r] --
+// its controls, its Philox key, its counter row.  The categorical helpers make, per row, exactly the call the scalar
+// kernels make for a whole launch (<false> for a row whose controls are off, <true> otherwise); the mixture helper runs
+// <true> for every row, which at T = 1 has the bits of <false>.  So row r has the bits of the scalar launch with tab[r]'s
+// controls.
+
+// The record of a wave's row in scalar registers: every lane loads the same 32 bytes (an ordinary vector load), the first
+// lane's copy is broadcast, and the branches on it below are wave-uniform for the compiler as well.
+__device__ __forceinline__ WnSampleRow wn_sample_row_uniform(const WnSampleRow* tab, int64_t row) {
+  const uint4* src = reinterpret_cast<const uint4*>(tab + row);
+  const uint4 a = src[0], b = src[1];
+  auto u = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+  WnSampleRow r;
+  r.T = __builtin_bit_cast(float, u(a.x)); r.inv_T = __builtin_bit_cast(float, u(a.y));
+  r.top_k = (int32_t)u(a.z); r.top_p = __builtin_bit_cast(float, u(a.w));
+  r.seed = (uint64_t)u(b.x) | ((uint64_t)u(b.y) << 32);
+  r.stream = (uint64_t)u(b.z) | ((uint64_t)u(b.w) << 32);
+  return r;
+}
+// categorical draw from a stored probability row (wn_sample_rand_cat_kernel's two forms)
+__device__ __forceinline__ int wn_draw_cat_row_tab(const float* p, int C, int lane, const WnSampleRow& r, uint64_t offset) {
+  if (r.ctl().on()) return wn_draw_cat_row(wn_cat_ctl_view(p, C, lane, r.ctl()), C, lane, (int64_t)r.stream, r.seed, offset);
+  return wn_draw_cat_row(p, C, lane, (int64_t)r.stream, r.seed, offset);
+}
+// categorical draw from the logits (wn_cat_rand_row's forms; TOPP false: the head kernel, no row has top_p on)
+template <bool TOPP = true>
+__device__ __forceinline__ float wn_cat_rand_row_tab(const float* l, int C, int lane, float* q, const WnSampleRow& r,
+                                                     uint64_t offset, float inv_lv) {
+  if (r.ctl().on()) return wn_cat_rand_row<true, TOPP>(l, C, lane, q, (int64_t)r.stream, r.seed, offset, inv_lv, r.ctl());
+  return wn_cat_rand_row(l, C, lane, q, (int64_t)r.stream, r.seed, offset, inv_lv);
+}
+// mixture draw, one row per thread: lanes differ in their records, in data only -- every lane runs the <true> form.  For a
+// row at T = 1 that form has the bits of the <false> form: its only extra operations are w * inv_T and e^s * T, and a
+// product with 1.0f is exact for every finite and infinite fp32 value, denormals included (fp32 denormals are not flushed
+// on gfx950; the product and the subtraction behind it are separate source expressions, so -ffp-contract=on fuses
+// nothing, and a fused (w * 1 - wm) would round like (w - wm) anyway).  One instruction stream for all lanes: a mixed
+// batch costs what the uniform one costs (a per-lane branch between the two forms ran both, measured +2 us a step).
+__device__ __forceinline__ float wn_mix_rand_row_tab(const float* p, int M, int kind, const WnSampleRow* tab, int64_t row,
+                                                     uint64_t offset) {
+  const WnSampleRow r = tab[row];
+  return wn_mix_rand_row<true>(p, M, kind, (int64_t)r.stream, r.seed, offset, r.ctl());
+}

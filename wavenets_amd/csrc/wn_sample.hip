@@ -90,12 +90,45 @@ __global__ __launch_bounds__(256) void wn_sample_rand_cat_logits_kernel(const fl
     wn_emit_sample(em, row, v);
   }
 }
+// Per-row controls: row r draws with tab[r] -- its controls, key and counter row -- in the forms
+// wn_draw_cat_row_tab / wn_cat_rand_row_tab / wn_mix_rand_row_tab pick per row; the kernels above stay as they are.
+// LOGITS false: from a stored probability row (wn_sample_rand_cat_kernel's twin); true: from the logits, with the emit
+// (wn_sample_rand_cat_logits_kernel's twin).  Templates first used at the END of this file (wn_launch_sample_rand_rows):
+// instantiations are emitted in the order of first use, so the twins land behind the kernels of before in the code object.
+template <bool LOGITS>
+__global__ __launch_bounds__(256) void wn_sample_rand_cat_rows_kernel(const float* pred, int64_t rows, int C, float inv,
+                                                                      uint64_t offset, float* out, WnEmit em,
+                                                                      const WnSampleRow* tab) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + w;
+  if (row >= rows) return;
+  const WnSampleRow r = wn_sample_row_uniform(tab, row);
+  if constexpr (LOGITS) {
+    __shared__ float q[4][WN_SAMPLE_FUSED_MAXC];
+    const float v = wn_cat_rand_row_tab(pred + row * C, C, lane, q[w], r, offset, inv);
+    if (lane == 0) {
+      out[row] = v;
+      wn_emit_sample(em, row, v);
+    }
+  } else {
+    const int result = wn_draw_cat_row_tab(pred + row * C, C, lane, r, offset);
+    if (lane == 0) out[row] = (float)result * inv - 1.0f;
+  }
+}
+// (defined at the end of the file)
+static void wn_launch_sample_rand_rows(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t offset,
+                                       float* out, hipStream_t s, WnEmit em, const WnSampleRow* tab, bool logits);
 int wn_sample_from_logits_supported(int C) { return C <= WN_SAMPLE_FUSED_MAXC ? 1 : 0; }
 int wn_sample_top_k_max_classes() { return WN_SAMPLE_FUSED_MAXC; }
 int wn_launch_sample_rand_cat_logits(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
-                                     float* out, hipStream_t s, WnSampleCtl ctl, WnEmit em) {
+                                     float* out, hipStream_t s, WnSampleCtl ctl, WnEmit em, const WnSampleRow* tab) {
   if (rows <= 0) return WN_OK;
   if (C > WN_SAMPLE_FUSED_MAXC) { wn_set_error("sample from logits: %d classes > %d", C, WN_SAMPLE_FUSED_MAXC); return WN_E_UNSUPPORTED; }
+  if (tab) {
+    wn_launch_sample_rand_rows(logits, rows, C, 0, bits, 0, offset, out, s, em, tab, true);
+    WN_HIP_CHECK(hipGetLastError());
+    return WN_OK;
+  }
   const auto kernel = ctl.on() ? wn_sample_rand_cat_logits_kernel<true> : wn_sample_rand_cat_logits_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, rows, C,
                      1.0f / (float)(1 << (bits - 1)), seed, offset, out, em, ctl);
@@ -111,8 +144,17 @@ __global__ void wn_sample_rand_mix_kernel(const float* pred, int64_t rows, int M
   out[row] = vc;
   wn_emit_sample(em, row, vc);
 }
-int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind,
-                          uint64_t seed, uint64_t offset, float* out, hipStream_t s, WnSampleCtl ctl, WnEmit em) {
+template <bool EMIT>
+__global__ void wn_sample_rand_mix_rows_kernel(const float* pred, int64_t rows, int M, int kind, uint64_t offset, float* out,
+                                              WnEmit em, const WnSampleRow* tab) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  const float vc = wn_mix_rand_row_tab(pred + row * 3 * M, M, kind, tab, row, offset);
+  out[row] = vc;
+  if constexpr (EMIT) wn_emit_sample(em, row, vc);
+}
+int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t seed, uint64_t offset,
+                          float* out, hipStream_t s, WnSampleCtl ctl, WnEmit em, const WnSampleRow* tab) {
   if (rows <= 0) return WN_OK;
   if (M > 0 && (ctl.top_k > 0 || ctl.top_p > 0.f)) {
     wn_set_error("sample_rand: top_k and top_p apply to the categorical head only");
@@ -122,8 +164,10 @@ int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bit
     wn_set_error("sample_rand: top_k / top_p over %d classes > %d", C, WN_SAMPLE_FUSED_MAXC);
     return WN_E_UNSUPPORTED;
   }
-  if (M <= 0 && em.out) return wn_launch_sample_rand_cat_logits(pred, rows, C, bits, seed, offset, out, s, ctl, em);
-  if (M <= 0) {
+  if (M <= 0 && em.out) return wn_launch_sample_rand_cat_logits(pred, rows, C, bits, seed, offset, out, s, ctl, em, tab);
+  if (tab) {
+    wn_launch_sample_rand_rows(pred, rows, C, M, bits, kind, offset, out, s, em, tab, false);
+  } else if (M <= 0) {
     const auto kernel = ctl.on() ? wn_sample_rand_cat_kernel<true> : wn_sample_rand_cat_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
                        pred, rows, C, 1.0f / (float)(1 << (bits - 1)), seed, offset, out, ctl);
@@ -134,4 +178,16 @@ int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bit
   }
   WN_HIP_CHECK(hipGetLastError());
   return WN_OK;
+}
+
+static void wn_launch_sample_rand_rows(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t offset,
+                                       float* out, hipStream_t s, WnEmit em, const WnSampleRow* tab, bool logits) {
+  const float inv = 1.0f / (float)(1 << (bits - 1));
+  if (M <= 0) {
+    const auto kernel = logits ? wn_sample_rand_cat_rows_kernel<true> : wn_sample_rand_cat_rows_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, pred, rows, C, inv, offset, out, em, tab);
+  } else {
+    const auto kernel = em.out ? wn_sample_rand_mix_rows_kernel<true> : wn_sample_rand_mix_rows_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, pred, rows, M, kind, offset, out, em, tab);
+  }
 }

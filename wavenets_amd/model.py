@@ -185,6 +185,44 @@ _RELAY_GAVE_UP = ('wn_generate: a workgroup of the generation relay gave up wait
                   '(code {}); the samples of this {} are invalid')
 
 
+class _RowControls:
+  """Sampling controls per utterance: B checked struct wn_sampling entries and their Philox streams,
+  packed by wn_sampling_rows_pack (host only) into the table of struct wn_sampling_row that wn_generate_rows_chunk reads
+  from device memory, and the flags that say what the union of the rows asks for."""
+
+  def __init__(self, entries, streams, head, classes):
+    B = len(entries)
+    self.entries, self.streams = list(entries), (list(streams) if streams is not None else None)
+    arr = (_lib.WnSampling * B)(*[_lib.WnSampling(e.temperature, e.top_k, e.seed, e.top_p) for e in entries])
+    st = (C.c_uint64 * B)(*streams) if streams is not None else None
+    self.host = (_lib.WnSamplingRow * B)()
+    flags = C.c_int32(0)
+    _lib.check(_lib.lib().wn_sampling_rows_pack(arr, st, B, head, classes, self.host, C.byref(flags)))
+    self.flags = int(flags.value)
+
+  def __len__(self):
+    return len(self.entries)
+
+  def device_table(self, device):
+    """The table as a float tensor on `device`: one copy, made once per call or session."""
+    return torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.float32).to(device)
+
+
+def _as_rows(name, v):
+  """None for a scalar argument, else the entries of a list, tuple, numpy array or 1-D tensor as Python values."""
+  if isinstance(v, torch.Tensor):
+    v = v.detach().cpu().numpy()
+  if isinstance(v, np.ndarray):
+    if v.ndim == 0:
+      return None
+    if v.ndim != 1:
+      raise ValueError(f'{name} must be a scalar or a sequence of one entry per utterance (got shape {tuple(v.shape)})')
+    return v.tolist()
+  if isinstance(v, (list, tuple)):
+    return [e.item() if isinstance(e, (np.generic, torch.Tensor)) else e for e in v]
+  return None
+
+
 class GenerationSession:
   """One sequence of WaveNet.generation_session(...), continued chunk by chunk (wn_generate_chunk).
 
@@ -195,6 +233,8 @@ class GenerationSession:
   def __init__(self, model, sampling, condition, window, batch_size, use_queues, deterministic):
     L = _lib.lib()
     self._model, self._sampling, self._cond, self._window = model, sampling, condition, window
+    # per-row controls: the device table of the session, read by every chunk (and by the exact-fp32 rerun of one)
+    self._rows = sampling.device_table(model._device) if isinstance(sampling, _RowControls) else None
     self._B, self._queued, self._det = int(batch_size), int(bool(use_queues)), int(bool(deterministic))
     # its own workspace (never model._workspace('gen')): other sessions and one-shot generate calls leave it alone
     self._ws = torch.zeros(int(L.wn_generate_workspace_floats(model._plan, self._B, self._queued)), dtype=torch.float32,
@@ -224,6 +264,12 @@ class GenerationSession:
     out = torch.empty(self._B, n, 1, dtype=torch.float32, device=m._device)
 
     def run():
+      if self._rows is not None:
+        _lib.check(L.wn_generate_rows_chunk(m._plan, _lib.ptr(m.flat_params), _lib.ptr(self._window) if first == 0 else None,
+                                            _lib.ptr(self._cond), self._B, first, n, self._det, self._queued,
+                                            _lib.ptr(self._rows), self._sampling.flags, _lib.ptr(out), _lib.ptr(self._ws),
+                                            self._ws.numel(), _lib.stream_ptr()))
+        return
       _lib.check(L.wn_generate_chunk(m._plan, _lib.ptr(m.flat_params), _lib.ptr(self._window) if first == 0 else None,
                                      _lib.ptr(self._cond), self._B, first, n, self._det, self._queued,
                                      C.byref(self._sampling), _lib.ptr(out), _lib.ptr(self._ws), self._ws.numel(),
@@ -1065,6 +1111,47 @@ class WaveNet(torch.nn.Module):
     key = 0x0402 if seed is None else seed & 0xFFFFFFFFFFFFFFFF
     return _lib.WnSampling(float(t), top_k, key, float(tp))
 
+  def _sampling_rows(self, batch_size, temperature, top_k, seed, top_p, stream, classes, have_sample=True):
+    """Sampling controls given per utterance.  Each of temperature, top_k, seed and top_p is a
+    scalar or a sequence (list, tuple, numpy array, 1-D tensor) of batch_size entries, entry b for utterance b; scalars
+    beside sequences are broadcast.  Every row is checked by _sampling, and the error names the row.  stream: None, or
+    batch_size ints in [0, 2**63), the row word of utterance b's Philox counter (None: b).
+    Returns the one struct wn_sampling of today's scalar entry points when every row is equal and stream is None --
+    such a call runs exactly the code it ran before -- and a _RowControls otherwise."""
+    B = int(batch_size)
+    cols = {}
+    for name, v in (('temperature', temperature), ('top_k', top_k), ('seed', seed), ('top_p', top_p)):
+      rows = _as_rows(name, v)
+      if rows is not None and len(rows) != B:
+        raise ValueError(f'{name} has {len(rows)} entries for a batch of {B} utterances')
+      cols[name] = rows if rows is not None else [v] * B
+    entries = []
+    for b in range(B):
+      T = cols['temperature'][b]
+      if isinstance(T, bool):
+        raise ValueError(f'row {b}: temperature must be a real number (got {T!r})')
+      try:
+        entries.append(self._sampling(T, cols['top_k'][b], cols['seed'][b], classes, cols['top_p'][b]))
+      except ValueError as e:
+        raise ValueError(f'row {b}: {e}') from None
+    streams = None
+    if stream is not None:
+      streams = _as_rows('stream', stream)
+      if streams is None:
+        raise ValueError(f'stream must be None or a sequence of one int per utterance (got {stream!r})')
+      if len(streams) != B:
+        raise ValueError(f'stream has {len(streams)} entries for a batch of {B} utterances')
+      for b, v in enumerate(streams):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 63:
+          raise ValueError(f'row {b}: stream must be an int in [0, 2**63) (got {v!r})')
+      if not have_sample:
+        raise ValueError('stream requires `sample`: a caller who names the Philox streams owns the prompt')
+    # (compared as the library reads them: top_k >= classes and top_p = 1 are off)
+    key = lambda e: (e.temperature, 0 if e.top_k >= classes else e.top_k, e.seed, 0.0 if e.top_p >= 1 else e.top_p)
+    if streams is None and all(key(e) == key(entries[0]) for e in entries):
+      return entries[0]
+    return _RowControls(entries, streams, _lib.HEADS[self.sampling_function], classes)
+
   def sample_waveform(self, inputs, deterministic=False, temperature=1.0, top_k=0, seed=None, top_p=1.0):
     """src/model.py:393-503: (B,T,C_out) -> (B,T,1).  Stochastic draws use Philox keyed by the
     reference's seed (4,2) -> 0x0402 plus a per-call offset (TF's stream is not reproducible).
@@ -1103,17 +1190,30 @@ class WaveNet(torch.nn.Module):
 
   # ------------------------------------------------------------------ generation
   def generate(self, length, batch_size: int = 1, condition=None, sample=None,
-               use_queues=False, deterministic=False, temperature=1.0, top_k=0, seed=None, top_p=1.0):
+               use_queues=False, deterministic=False, temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None):
     """src/model.py:258-307 (intended semantics; the reference's kwarg / rank bugs are not
     reproduced).  Returns (B, length, 1).
     temperature / top_k / seed / top_p (additions) as in sample_waveform; an int seed is the Philox key of
-    the draws and seeds the initial noise window when `sample` is None.  seed=None is seed=0x0402."""
+    the draws and seeds the initial noise window when `sample` is None.  seed=None is seed=0x0402.
+    Per utterance: each of the four may be a sequence of B entries (list, tuple, numpy array, 1-D
+    tensor), entry b for utterance b; a scalar beside sequences is broadcast.  Row b of the result is bit for bit row b
+    of the call at the same B whose scalar controls are row b's.  Without `sample`, row b of the noise window is row b
+    of the window the scalar call with seed[b] draws.  stream: None, or B ints in [0, 2**63) -- utterance b draws from
+    the Philox counter row stream[b] instead of b, so a request keeps its draws whichever batch slot it lands in
+    (requires `sample`).  deterministic stays one flag for the call."""
     sampling, condition, sample, batch_size = self._generation_args(batch_size, condition, sample, deterministic,
-                                                                    temperature, top_k, seed, top_p)
+                                                                    temperature, top_k, seed, top_p, stream)
     L = _lib.lib()
     ws = self._workspace('gen', L.wn_generate_workspace_floats(self._plan, batch_size, int(bool(use_queues))))
     out = torch.empty(batch_size, int(length), 1, dtype=torch.float32, device=self._device)
+    rows = sampling.device_table(self._device) if isinstance(sampling, _RowControls) else None
     def run():
+      if rows is not None:      # (the range-guard rerun below repeats with the same table)
+        _lib.check(L.wn_generate_rows_chunk(self._plan, _lib.ptr(self.flat_params), _lib.ptr(sample), _lib.ptr(condition),
+                                            batch_size, 0, int(length), int(bool(deterministic)), int(bool(use_queues)),
+                                            _lib.ptr(rows), sampling.flags, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                            _lib.stream_ptr()))
+        return
       _lib.check(L.wn_generate_sampled(self._plan, _lib.ptr(self.flat_params), _lib.ptr(sample), _lib.ptr(condition),
                                        batch_size, int(length), int(bool(deterministic)), int(bool(use_queues)),
                                        C.byref(sampling), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
@@ -1131,11 +1231,15 @@ class WaveNet(torch.nn.Module):
           run()
     return out
 
-  def _generation_args(self, batch_size, condition, sample, deterministic, temperature, top_k, seed, top_p):
+  def _generation_args(self, batch_size, condition, sample, deterministic, temperature, top_k, seed, top_p, stream=None):
     """The argument handling of generate and generation_session: the sampling controls checked, condition and sample on
     the device, the batch size they imply, the initial window (the last receptive_field samples of `sample`, or zeros /
-    seeded noise), the model built.  Returns (sampling, condition, window, batch_size)."""
-    sampling = self._sampling(temperature, top_k, seed, 2 ** self.bits, top_p)
+    seeded noise), the model built.  Returns (sampling, condition, window, batch_size); sampling is the struct
+    wn_sampling of the call, or a _RowControls when the controls differ between utterances or `stream` is given."""
+    per_row = stream is not None or any(_as_rows(n, v) is not None for n, v in (
+        ('temperature', temperature), ('top_k', top_k), ('seed', seed), ('top_p', top_p)))
+    # (scalars: checked first, as ever; per utterance: once the batch size is known, below)
+    sampling = None if per_row else self._sampling(temperature, top_k, seed, 2 ** self.bits, top_p)
     if self.conditioning is not None and condition is None:
       raise ValueError('Conditioning must be provided.')
     if condition is not None:
@@ -1150,9 +1254,18 @@ class WaveNet(torch.nn.Module):
     if sample is not None:
       batch_size = sample.shape[0]
     rf = self.receptive_field
+    if per_row:
+      sampling = self._sampling_rows(batch_size, temperature, top_k, seed, top_p, stream, 2 ** self.bits, sample is not None)
     if sample is None:
       if deterministic:
         sample = torch.zeros(batch_size, rf, 1, device=self._device)
+      elif isinstance(sampling, _RowControls):
+        # row b of the (B, rf, 1) noise the scalar call with seed[b] draws: one host randn per distinct seed
+        noise = {}
+        for e in sampling.entries:
+          if e.seed not in noise:
+            noise[e.seed] = torch.randn(batch_size, rf, 1, generator=torch.Generator(device='cpu').manual_seed(int(e.seed)))
+        sample = torch.stack([noise[e.seed][b] for b, e in enumerate(sampling.entries)]).to(self._device)
       else:
         g = torch.Generator(device='cpu').manual_seed(int(sampling.seed))
         sample = torch.randn(batch_size, rf, 1, generator=g).to(self._device)
@@ -1165,13 +1278,14 @@ class WaveNet(torch.nn.Module):
     return sampling, condition, sample, batch_size
 
   def generation_session(self, batch_size: int = 1, condition=None, sample=None, use_queues=False, deterministic=False,
-                         temperature=1.0, top_k=0, seed=None, top_p=1.0):
-    """A sequence made in pieces: the arguments of generate without `length`, with the same checks.  The chunks of
+                         temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None):
+    """A sequence made in pieces: the arguments of generate without `length`, with the same checks (per-utterance
+    controls and `stream` included: the session keeps the device table of its rows).  The chunks of
     session.generate(n), concatenated, are bit for bit generate(total, same arguments).  The
     session owns its workspace and is bound to the weights as they are now: after an optimizer step, set_weights,
     finalize_variable_values, or entering / leaving averaged_weights() its generate raises RuntimeError."""
     sampling, condition, window, batch_size = self._generation_args(batch_size, condition, sample, deterministic,
-                                                                    temperature, top_k, seed, top_p)
+                                                                    temperature, top_k, seed, top_p, stream)
     return GenerationSession(self, sampling, condition, window, batch_size, use_queues, deterministic)
 
   def generate_stream(self, length, chunk, **kwargs):
