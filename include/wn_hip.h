@@ -366,7 +366,8 @@ int wn_generate_chunk(wn_plan* p, const float* params, const float* window, cons
  *   says what was checked.)
  * deterministic != 0 ignores the table's controls, keys and streams (arg max / mode), as it ignores struct wn_sampling.
  * Out of scope: per-row controls in wn_sample_waveform_sampled and in the training step's metric draw; a per-row
- *   deterministic flag (top_k = 1 on a categorical row is the arg max); changing B inside a sequence. */
+ *   deterministic flag (top_k = 1 on a categorical row is the arg max); changing B inside a sequence (a new request into
+ *   a row of the running batch is wn_generate_admit, below). */
 typedef struct wn_sampling_row { float T, inv_T; int32_t top_k; float top_p; uint64_t seed, stream; } wn_sampling_row;
 #define WN_SAMPLING_ROWS_ON 1
 #define WN_SAMPLING_ROWS_TOP_P 2
@@ -377,6 +378,62 @@ int wn_generate_rows_chunk(wn_plan* p, const float* params, const float* window,
                            int64_t first, int32_t length, int32_t deterministic, int32_t queued,
                            const wn_sampling_row* rows, int32_t rows_flags, float* out, float* workspace,
                            int64_t ws_floats, void* stream);
+/* ---- a new request into a row of a running batch ----
+ * wn_generate_rows_begin: begins a sequence whose first sample has index `first` >= 0.  The arguments are those of
+ *   wn_generate_rows_chunk; window is required.  Window copy, (queued) the priming pass, then the steps
+ *   first + 1 .. first + length - 1.  The priming draw is sample `first`: drawn from counter (stream, first), written to output
+ *   column 0; the window's index t stands at time t + first in every ring, and the relay's epoch, the window parity and
+ *   tau follow the index in the sequence as they do in wn_generate_chunk.  first == 0 is
+ *   wn_generate_rows_chunk(window, 0, ...) bit for bit.  The sequence is continued by wn_generate_rows_chunk(NULL, first', ...).
+ *   (wn_generate_chunk / wn_generate_rows_chunk keep their rule: a window there requires first == 0.)  A deterministic
+ *   sequence does not depend on `first`; a stochastic one does, through the counter.
+ *   WN_E_INVALID, before the device is touched: rows null or misaligned, flags that no pack call returns, first < 0,
+ *   window == NULL, first + length > 2^31 - 1.
+ *
+ * wn_generate_admit: `workspace` is a QUEUED session at B utterances in which the samples 0 .. position - 1 have been
+ *   made (position >= 1).  The call replaces the k utterances slots[0 .. k) of it (host array, distinct values in [0, B))
+ *   by k new requests: windows (k, RF), cond (k, cond_inputs) or NULL, rows_k (device, k records, 16-byte aligned) with
+ *   their flags.  It does two things on `stream`:
+ *     1. on `scratch` (wn_generate_admit_scratch_floats(p, k) floats: the queued generation workspace of k rows) the
+ *        priming part of wn_generate_rows_begin at B' = k, first = position - 1, length = 1: sample position - 1 of request
+ *        j goes to first_out[j] (device, k floats).  The pass prepares the weight images again, into the scratch.
+ *     2. one launch (wn_gen_admit_rows_kernel) copies, for every j, everything the steps read per utterance from row j of
+ *        the scratch's layout to row slots[j] of the session's: the KS raw-sample slots of xin, every slot of every block's
+ *        ring (R floats) and inner rings (D floats), and on a conditioned net the condition bias of every block (2D
+ *        floats, from the priming layout of k rows to that of B rows).  Both sequences share the time axis: slot s goes
+ *        to slot s.  Nothing else per utterance outlives a step (the per-step rows and partial accumulators are written
+ *        before they are read in every step and call; the relay's granules are tagged per step).
+ *   After it, wn_generate_rows_chunk(NULL, position, ...) on the session treats the admitted rows like any other; the
+ *   caller must have written the new records into its own device table at slots[j], and passes the new union of flags.
+ *   The defining property: row slots[j] of the session, from index position - 1 on (first_out[j], then the row of the later
+ *   chunks), is bit for bit row 0 of wn_generate_rows_begin at B = 1, first = position - 1 with request j's window,
+ *   condition and record; every row not in `slots` is bit for bit what it is without the admission.
+ *   A draw at position t uses counter (stream, t): what a request draws depends on the position it was admitted at.
+ *   Range guard: the scratch has its own slot, wn_generate_guard_slot(p, k, 1), which speaks of the admission's priming
+ *   pass; the session's slot is untouched.  A tripped admission is repeated in exact-fp32 mode (the move overwrites the
+ *   same rows), and the session then stays in that mode.
+ *   There is no `queued` argument: admission into a sliding-window session is not offered.  Not offered either: changing
+ *   B, retiring a row (a free slot runs on until something is admitted into it), sharing the session's weight images.
+ *   WN_E_INVALID, before the device is touched, the message naming the argument: a null pointer among p, params,
+ *   windows, slots, rows_k, first_out, workspace, scratch; k < 1 or k > B; a slot outside [0, B) or a duplicate (with its
+ *   index); position < 1 or > 2^31 - 2; rows_k misaligned; flags that no pack call returns; either workspace too small;
+ *   cond == NULL on a conditioned net.
+ *
+ * wn_generate_admit_describe: test / diagnosis hook, host only.  One line listing the segments the move of (k, B) copies,
+ *   separated by " | ", each as
+ *     <name> block=<block or -1> slots=<slots> width=<floats per slot and utterance> src=<float offset in the scratch> dst=<... in the session>
+ *   (a segment is [slot][rows][width]: k rows at src, B rows at dst), and last "floats_per_utterance=<sum of slots * width>".
+ *   WN_E_INVALID as wn_layer_describe: null p or buffer, len < 1, k or B out of range, a buffer too short. */
+int wn_generate_rows_begin(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                           int64_t first, int32_t length, int32_t deterministic, int32_t queued,
+                           const wn_sampling_row* rows, int32_t rows_flags, float* out, float* workspace,
+                           int64_t ws_floats, void* stream);
+int64_t wn_generate_admit_scratch_floats(const wn_plan* p, int32_t k);
+int wn_generate_admit(wn_plan* p, const float* params, const float* windows, const float* cond, int32_t k,
+                      const int32_t* slots, int32_t B, int64_t position, int32_t deterministic,
+                      const wn_sampling_row* rows_k, int32_t rows_flags_k, float* first_out, float* workspace,
+                      int64_t ws_floats, float* scratch, int64_t scratch_floats, void* stream);
+int wn_generate_admit_describe(const wn_plan* p, int32_t k, int32_t B, char* buf, int32_t len);
 int64_t wn_generate_workspace_floats(const wn_plan* p, int32_t B, int32_t queued);
 /* The one contiguous part of the generation workspace that steps write and a continuation reads, as a float offset and a
  * float count.  queued: from the raw-sample slots to the end of the layout (rings, inner rings, per-step rows, partial

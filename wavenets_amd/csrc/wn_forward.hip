@@ -3,15 +3,15 @@
 
 namespace {
 
-__global__ void wn_ring_capture_kernel(const float* src, int B, int T, int C, int nslots, float* ring) {
-  // ring[(t % nslots)][b][c] = src[b][t][c] for the last nslots time steps
+__global__ void wn_ring_capture_kernel(const float* src, int B, int T, int C, int nslots, float* ring, int64_t t0) {
+  // ring[((t + t0) % nslots)][b][c] = src[b][t][c] for the last nslots time steps (t0: the time of src's index 0)
   const int64_t n = (int64_t)nslots * B * C;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(i % C);
     const int b = (int)((i / C) % B);
     const int k = (int)(i / ((int64_t)C * B));
     const int t = T - nslots + k;
-    if (t >= 0) ring[((int64_t)(t % nslots) * B + b) * C + c] = src[((int64_t)b * T + t) * C + c];
+    if (t >= 0) ring[((int64_t)((t + t0) % nslots) * B + b) * C + c] = src[((int64_t)b * T + t) * C + c];
   }
 }
 
@@ -68,10 +68,10 @@ void deep16_ptrs(const wn_plan* p, int b, const float* fragbase, BlockPtrs& k) {
   if (bi.g16u >= 0) { k.G16u = fragbase + bi.g16u; k.JTu = std::max(2, ceil32(p->D)); }
 }
 
-int ring_capture(const float* src, int B, int T, int C, int nslots, float* ring, hipStream_t s) {
+int ring_capture(const float* src, int B, int T, int C, int nslots, float* ring, int64_t t0, hipStream_t s) {
   const int64_t n = (int64_t)nslots * B * C;
   hipLaunchKernelGGL(wn_ring_capture_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, s,
-                     src, B, T, C, nslots, ring);
+                     src, B, T, C, nslots, ring, t0);
   WN_HIP_CHECK(hipGetLastError());
   return WN_OK;
 }
@@ -223,8 +223,8 @@ struct FwdCall {
     }
     if (rc) return rc;
     if (rings) {
-      rc = ring_capture(x, B, T, 1, p->KS, rings->xin, s);
-      if (!rc) rc = ring_capture(ws + L.H[0], B, T, p->R, rings->nslots[0], rings->h[0], s);
+      rc = ring_capture(x, B, T, 1, p->KS, rings->xin, rings->t0, s);
+      if (!rc) rc = ring_capture(ws + L.H[0], B, T, p->R, rings->nslots[0], rings->h[0], rings->t0, s);
     }
     return rc;
   }
@@ -278,12 +278,12 @@ struct FwdCall {
         mark(e.prof_ev, e.prof_used, true, s);
       }
       if (rings && b + 1 < p->N) {
-        rc = ring_capture(f.x_out, B, T, p->R, rings->nslots[b + 1], rings->h[b + 1], s);
+        rc = ring_capture(f.x_out, B, T, p->R, rings->nslots[b + 1], rings->h[b + 1], rings->t0, s);
         if (rc) return rc;
       }
       if (rings)
         for (int i = 0; i + 1 < p->LPB; ++i) {
-          rc = ring_capture(f.P[i], B, T, p->D, rings->nslots_p[b][i], rings->hp[b][i], s);
+          rc = ring_capture(f.P[i], B, T, p->D, rings->nslots_p[b][i], rings->hp[b][i], rings->t0, s);
           if (rc) return rc;
         }
     }

@@ -153,12 +153,16 @@ int ensure_gen_table(const wn_plan* p, wn_exec& e, const GenLayout& G, const WsL
 // the kernel paths of the call; its phases are the member functions, in launch order.  A call makes the samples
 // first .. first + length - 1 of a sequence; every `step` below is the index in the sequence, and everything between two
 // steps lives in the workspace (xin, the rings, the relay's granule area; the weight images and cb of the priming pass),
-// so a call with first > 0 goes on where the call before it stopped.
+// so a call with first > 0 goes on where the call before it stopped.  A call that `primes` begins a sequence from a
+// window: its first step is the priming pass.  That is the call with first == 0 of every entry point, and the call of
+// wn_generate_rows_begin at any first: the window's index t then stands at time t + first, and the counter, the output
+// column, the window parity and tau of the first sample are those of step `first`.
 // ------------------------------------------------------------------------------------------
 struct GenCall {
   wn_exec& e;                        // the calling thread's execution state for p
   wn_plan* p; const float* params; const float* cond; int B, length; bool deterministic;
   int first, end, step0;             // the call's steps are [first, end); step0: the first one that is not the priming pass
+  bool primes;                       // step `first` is the priming pass over the caller's window
   uint64_t seed; WnSampleCtl ctl;    // the sampling controls
   // per-row controls (wn_generate_rows_chunk): the caller's device table, one record per utterance, or null.  With a
   // table every stochastic draw of the call -- sliding window, priming step, sampler launch, head tail -- reads its row's
@@ -181,10 +185,10 @@ struct GenCall {
   // arguments that do not change from step to step (build_*)
   WnGenStepArgs ga; WnGen128Args ca; WnGenHeadArgs ha;
 
-  void bind(wn_plan* p_, const float* params_, const float* cond_, int B_, int first_, int length_, bool det, uint64_t seed_,
-            const WnSampleCtl& ctl_, float* out_, float* workspace, hipStream_t s_, GenLayout&& G_) {
+  void bind(wn_plan* p_, const float* params_, const float* cond_, int B_, int first_, int length_, bool primes_, bool det,
+            uint64_t seed_, const WnSampleCtl& ctl_, float* out_, float* workspace, hipStream_t s_, GenLayout&& G_) {
     p = p_; params = params_; cond = cond_; B = B_; length = length_; deterministic = det; seed = seed_; ctl = ctl_;
-    first = first_; end = first_ + length_; step0 = std::max(first_, 1);
+    first = first_; end = first_ + length_; primes = primes_; step0 = primes_ ? first_ + 1 : first_;
     out = out_; ws = workspace; s = s_;
     RF = wn_plan_receptive_field(p);
     G = std::move(G_);
@@ -194,6 +198,7 @@ struct GenCall {
     last = ws + G.last; lastp = ws + G.lastp; samp = ws + G.samp; Zrow = ws + G.Zrow;
     gguard = ws + G.guard;
     R.xin = ws + G.xin;
+    R.t0 = primes ? first : 0;         // the window's index t is the sample at time t + first
     for (size_t b = 0; b < G.ring.size(); ++b) {
       R.h.push_back(ws + G.ring[b]);
       R.nslots.push_back(G.nslots[b]);
@@ -210,7 +215,8 @@ struct GenCall {
 
   // the window into the workspace (a continuation has none), the guard (and the relay's give-up word behind it) cleared
   int begin(const float* window) {
-    if (window) WN_HIP_CHECK(hipMemcpyAsync(win[0], window, (int64_t)B * RF * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // (the window buffers alternate with the step's parity: the sequence's first step reads win[first & 1])
+    if (window) WN_HIP_CHECK(hipMemcpyAsync(win[first & 1], window, (int64_t)B * RF * sizeof(float), hipMemcpyDeviceToDevice, s));
     WN_HIP_CHECK(hipMemsetAsync(gguard, 0, 2 * sizeof(float), s));
     return WN_OK;
   }
@@ -228,7 +234,7 @@ struct GenCall {
   // ---- naive sliding window: one full forward over the window per sample (src/model.py:296-305) ----
   int sliding_window() {
     for (int step = first; step < end; ++step) {
-      int rc = window_forward(win[step & 1], step == 0, nullptr);
+      int rc = window_forward(win[step & 1], primes && step == first, nullptr);
       if (rc) return rc;
       rc = sample_rows(p, last, B, deterministic, seed, (uint64_t)step, lastp, samp, s, ctl, rows);
       if (rc) return rc;
@@ -243,12 +249,12 @@ struct GenCall {
   //      sample with rows = utterances; every kernel and every per-row operation order is the one
   //      the sliding window uses, so the results are identical ----
   int prime() {
-    int rc = window_forward(win[0], true, &R);
+    int rc = window_forward(win[first & 1], true, &R);
     if (rc) return rc;
-    rc = sample_rows(p, last, B, deterministic, seed, 0, lastp, samp, s, ctl, rows);
+    rc = sample_rows(p, last, B, deterministic, seed, (uint64_t)first, lastp, samp, s, ctl, rows);
     if (rc) return rc;
-    // sample 0 is x[RF]; it becomes the network input at time tau = RF
-    hipLaunchKernelGGL(wn_gen_emit_kernel, dim3((B + 255) / 256), dim3(256), 0, s, samp, B, out, length, 0, emit(0).xin_slot);
+    // sample `first` is x[RF + first]; it becomes the network input at time tau = RF + first (output column 0)
+    hipLaunchKernelGGL(wn_gen_emit_kernel, dim3((B + 255) / 256), dim3(256), 0, s, samp, B, out, length, 0, emit(first).xin_slot);
     if (gp.chain == GEN_RELAY128)   // every granule tag starts below the first epoch
       WN_HIP_CHECK(hipMemsetAsync(ws + G.relay, 0, (size_t)wn_gen_relay128_floats(B, p->N) * sizeof(float), s));
     return WN_OK;
@@ -512,10 +518,13 @@ extern "C" int wn_generate(wn_plan* p, const float* params, const float* window,
 
 // wn_generate_sampled (window given, first = 0) and wn_generate_chunk
 // ... and wn_generate_rows_chunk: rows (device) in place of sampling, with the union of its rows from rows_flags
-static int generate_call(bool chunk, wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+// ... and wn_generate_rows_begin (GEN_ENTRY_BEGIN): a window at any first >= 0
+enum GenEntry { GEN_ENTRY_ONE, GEN_ENTRY_CHUNK, GEN_ENTRY_BEGIN };
+static int generate_call(GenEntry entry, wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                          int64_t first, int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
                          float* out, float* workspace, int64_t ws_floats, void* stream,
                          const WnSampleRow* rows = nullptr, int32_t rows_flags = 0) {
+  const bool chunk = entry != GEN_ENTRY_ONE, begins = entry == GEN_ENTRY_BEGIN;
   WnSampleCtl ctl = WN_SAMPLE_CTL_OFF;
   if (rows) {
     // the union of the rows as a WnSampleCtl: on() when some row is on, top_p > 0 when some row has top_p on (the values
@@ -528,7 +537,8 @@ static int generate_call(bool chunk, wn_plan* p, const float* params, const floa
   }
   if (chunk) {
     if (first < 0) { wn_set_error("generate: first must be >= 0 (got %lld)", (long long)first); return WN_E_INVALID; }
-    if (window && first != 0) {
+    if (begins && !window) { wn_set_error("generate: window is null (wn_generate_rows_begin begins a sequence from a window)"); return WN_E_INVALID; }
+    if (!begins && window && first != 0) {
       wn_set_error("generate: window begins a sequence and requires first == 0 (got first = %lld)", (long long)first);
       return WN_E_INVALID;
     }
@@ -544,16 +554,20 @@ static int generate_call(bool chunk, wn_plan* p, const float* params, const floa
   if (ws_floats < G.total) { wn_set_error("generate: workspace too small"); return WN_E_INVALID; }
   if (length == 0) return WN_OK;
   GenCall c{wnp::ex(p)};
-  c.bind(p, params, cond, B, (int)first, length, deterministic != 0, rows ? 0 : sampling->seed, ctl, out, workspace, (hipStream_t)stream, std::move(G));
+  c.bind(p, params, cond, B, (int)first, length, window != nullptr, deterministic != 0, rows ? 0 : sampling->seed, ctl, out, workspace,
+         (hipStream_t)stream, std::move(G));
   c.rows = rows;
   int rc = c.begin(window);
   if (rc) return rc;
   if (!queued) return c.sliding_window();
   c.gp = gen_paths(p, B, c.end, device_cu_count(), c.G.relay >= 0, c.deterministic, ctl);
-  if (window) {
+  if (c.primes) {
     rc = c.prime();
     if (rc) return rc;
   }
+  // (a call that is its priming pass alone launches no step: the admission's scratch call at B' = k leaves the session's
+  // table, cached by B, where it is)
+  if (c.step0 >= c.end) return WN_OK;
   // (in every call that reads it: a call at another B may have rebuilt the table in between)
   if (c.gp.table()) {
     rc = ensure_gen_table(p, c.e, c.G, c.L, B, c.gp.chain128());
@@ -572,13 +586,13 @@ static int generate_call(bool chunk, wn_plan* p, const float* params, const floa
 extern "C" int wn_generate_sampled(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                                    int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
                                    float* out, float* workspace, int64_t ws_floats, void* stream) {
-  return generate_call(false, p, params, window, cond, B, 0, length, deterministic, queued, sampling, out, workspace, ws_floats, stream);
+  return generate_call(GEN_ENTRY_ONE, p, params, window, cond, B, 0, length, deterministic, queued, sampling, out, workspace, ws_floats, stream);
 }
 
 extern "C" int wn_generate_chunk(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                                  int64_t first, int32_t length, int32_t deterministic, int32_t queued,
                                  const wn_sampling* sampling, float* out, float* workspace, int64_t ws_floats, void* stream) {
-  return generate_call(true, p, params, window, cond, B, first, length, deterministic, queued, sampling, out, workspace, ws_floats, stream);
+  return generate_call(GEN_ENTRY_CHUNK, p, params, window, cond, B, first, length, deterministic, queued, sampling, out, workspace, ws_floats, stream);
 }
 
 extern "C" int wn_generate_state_range(const wn_plan* p, int32_t B, int32_t queued, int64_t* offset, int64_t* floats) {
@@ -626,16 +640,199 @@ extern "C" int wn_sampling_rows_pack(const wn_sampling* sampling, const uint64_t
   return WN_OK;
 }
 
+// a caller's device table and its flags, before anything else is looked at (rows_name / flags_name: the argument names in the text)
+static int rows_table_check(const char* who, const char* rows_name, const char* flags_name, const wn_sampling_row* rows, int32_t rows_flags) {
+  if (!rows) { wn_set_error("%s: %s is null (the device table of wn_sampling_rows_pack)", who, rows_name); return WN_E_INVALID; }
+  if ((uintptr_t)rows % 16 != 0) { wn_set_error("%s: %s must be aligned to 16 bytes", who, rows_name); return WN_E_INVALID; }
+  if (rows_flags & ~(WN_SAMPLING_ROWS_ON | WN_SAMPLING_ROWS_TOP_P) || ((rows_flags & WN_SAMPLING_ROWS_TOP_P) && !(rows_flags & WN_SAMPLING_ROWS_ON))) {
+    wn_set_error("%s: %s must be the flags wn_sampling_rows_pack returned (got %d)", who, flags_name, (int)rows_flags);
+    return WN_E_INVALID;
+  }
+  return WN_OK;
+}
+
 extern "C" int wn_generate_rows_chunk(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                                       int64_t first, int32_t length, int32_t deterministic, int32_t queued,
                                       const wn_sampling_row* rows, int32_t rows_flags, float* out, float* workspace,
                                       int64_t ws_floats, void* stream) {
-  if (!rows) { wn_set_error("generate: rows is null (the device table of wn_sampling_rows_pack)"); return WN_E_INVALID; }
-  if ((uintptr_t)rows % 16 != 0) { wn_set_error("generate: rows must be aligned to 16 bytes"); return WN_E_INVALID; }
-  if (rows_flags & ~(WN_SAMPLING_ROWS_ON | WN_SAMPLING_ROWS_TOP_P) || ((rows_flags & WN_SAMPLING_ROWS_TOP_P) && !(rows_flags & WN_SAMPLING_ROWS_ON))) {
-    wn_set_error("generate: rows_flags must be the flags wn_sampling_rows_pack returned (got %d)", (int)rows_flags);
+  const int rc = rows_table_check("generate", "rows", "rows_flags", rows, rows_flags);
+  if (rc) return rc;
+  return generate_call(GEN_ENTRY_CHUNK, p, params, window, cond, B, first, length, deterministic, queued, nullptr, out, workspace, ws_floats,
+                       stream, reinterpret_cast<const WnSampleRow*>(rows), rows_flags);
+}
+
+// ---- a sequence that begins at a position other than 0, and admission into a running batch ----
+extern "C" int wn_generate_rows_begin(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                                      int64_t first, int32_t length, int32_t deterministic, int32_t queued,
+                                      const wn_sampling_row* rows, int32_t rows_flags, float* out, float* workspace,
+                                      int64_t ws_floats, void* stream) {
+  const int rc = rows_table_check("generate", "rows", "rows_flags", rows, rows_flags);
+  if (rc) return rc;
+  return generate_call(GEN_ENTRY_BEGIN, p, params, window, cond, B, first, length, deterministic, queued, nullptr, out, workspace, ws_floats,
+                       stream, reinterpret_cast<const WnSampleRow*>(rows), rows_flags);
+}
+
+namespace {
+
+// One run of consecutive ring slots that the admission moves, as wn_gen_admit_rows_kernel reads it: slot s of utterance j
+// is `width` floats at src + (s * k + j) * width in the scratch workspace and goes to dst + (s * B + slots[j]) * width in the
+// session's.  Both sequences share the time axis, so slot s goes to slot s.
+struct AdmitSeg {
+  char name[24];
+  int block;                         // the block it belongs to, or -1 (xin)
+  WnAdmitSeg d;
+};
+
+// everything the steps read per utterance (GenLayout, the step kernels; DESIGN.md section 32 says why this is all of it):
+// Gk / Lk: the scratch's layouts (k rows), G / L: the session's (B rows)
+std::vector<AdmitSeg> admit_segments(const wn_plan* p, const GenLayout& Gk, const WsLayout& Lk, int k, const GenLayout& G,
+                                     const WsLayout& L, int B) {
+  std::vector<AdmitSeg> v;
+  auto add = [&](const char* fmt, int block, int i, int64_t src, int64_t dst, int nslots, int width) {
+    AdmitSeg a;
+    snprintf(a.name, sizeof(a.name), fmt, block, i);
+    a.block = block;
+    a.d = WnAdmitSeg{src, dst, nslots, width};
+    v.push_back(a);
+  };
+  add("xin", -1, 0, Gk.xin, G.xin, p->KS, 1);
+  for (int b = 0; b < p->N; ++b) {
+    add("ring[%d]", b, 0, Gk.ring[b], G.ring[b], G.nslots[b], p->R);
+    for (size_t i = 0; i < G.ringp[b].size(); ++i) add("ringp[%d][%d]", b, (int)i, Gk.ringp[b][i], G.ringp[b][i], G.nslots_p[b][i], p->D);
+  }
+  if (p->c.cond_inputs > 0)          // [block][rows][2D] of the priming layout: one "slot" per block
+    for (int b = 0; b < p->N; ++b)
+      add("cb[%d]", b, 0, Gk.prime + Lk.cb + (int64_t)b * k * 2 * p->D, G.prime + L.cb + (int64_t)b * B * 2 * p->D, 1, 2 * p->D);
+  return v;
+}
+
+// One launch per admission: blockIdx.y = segment, blockIdx.z strides over the admitted utterances, the threads of the x
+// dimension stride over the segment's nslots * width floats of one utterance (consecutive threads, consecutive floats of a row).
+__global__ void wn_gen_admit_rows_kernel(const WnAdmitSeg* __restrict__ segs, const int32_t* __restrict__ slots, int k, int B,
+                                         const float* __restrict__ scratch, float* __restrict__ ws) {
+  const WnAdmitSeg sg = segs[blockIdx.y];
+  const int64_t n = (int64_t)sg.nslots * sg.width;
+  for (int j = blockIdx.z; j < k; j += gridDim.z) {
+    const int row = slots[j];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t s = i / sg.width, c = i % sg.width;
+      ws[sg.dst + (s * B + row) * sg.width + c] = scratch[sg.src + (s * k + j) * sg.width + c];
+    }
+  }
+}
+
+// the cached device copies of e: rebuilt when (k, B, slots) is not the key they were built for
+int ensure_admit_table(wn_exec& e, const std::vector<AdmitSeg>& segs, int k, int B, const int32_t* slots) {
+  AdmitTable& t = e.admit;
+  if (t.valid && t.k == k && t.B == B && std::equal(t.slots.begin(), t.slots.end(), slots)) return WN_OK;
+  t.valid = false;
+  if (t.k != k || t.B != B || !t.segs.d) {
+    std::vector<WnAdmitSeg> d;
+    for (const AdmitSeg& a : segs) d.push_back(a.d);
+    const int rc = t.segs.upload(d);
+    if (rc) return rc;
+  }
+  t.slots.assign(slots, slots + k);
+  const int rc = t.slots_d.upload(t.slots);
+  if (rc) return rc;
+  t.k = k; t.B = B;
+  t.valid = true;
+  return WN_OK;
+}
+
+// the arguments of wn_generate_admit that speak of k, B and the slots: WN_E_INVALID with the argument named
+int admit_slots_check(const char* who, int32_t k, const int32_t* slots, int32_t B) {
+  if (B < 1) { wn_set_error("%s: B must be >= 1 (got %d)", who, (int)B); return WN_E_INVALID; }
+  if (k < 1 || k > B) { wn_set_error("%s: k must lie in [1, B] (got k = %d, B = %d)", who, (int)k, (int)B); return WN_E_INVALID; }
+  if (!slots) return WN_OK;
+  std::vector<char> seen((size_t)B, 0);
+  for (int32_t j = 0; j < k; ++j) {
+    if (slots[j] < 0 || slots[j] >= B) {
+      wn_set_error("%s: slots[%d] = %d lies outside [0, B = %d)", who, (int)j, (int)slots[j], (int)B);
+      return WN_E_INVALID;
+    }
+    if (seen[slots[j]]) { wn_set_error("%s: slots[%d] = %d is a duplicate (the slots must be distinct)", who, (int)j, (int)slots[j]); return WN_E_INVALID; }
+    seen[slots[j]] = 1;
+  }
+  return WN_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t wn_generate_admit_scratch_floats(const wn_plan* p, int32_t k) {
+  return wn_generate_workspace_floats(p, k, 1);
+}
+
+extern "C" int wn_generate_admit_describe(const wn_plan* p, int32_t k, int32_t B, char* buf, int32_t len) {
+  if (!buf || len < 1) { wn_set_error("generate_admit_describe: no buffer"); return WN_E_INVALID; }
+  buf[0] = 0;
+  if (!p) { wn_set_error("generate_admit_describe: p is null"); return WN_E_INVALID; }
+  int rc = admit_slots_check("generate_admit_describe", k, nullptr, B);
+  if (rc) return rc;
+  const int RF = wn_plan_receptive_field(p);
+  const std::vector<AdmitSeg> segs = admit_segments(p, gen_layout(p, k, true), make_layout(p, k, RF, false), k, gen_layout(p, B, true),
+                                                    make_layout(p, B, RF, false), B);
+  int64_t per = 0;
+  std::string out;
+  for (const AdmitSeg& a : segs) {
+    char item[200];
+    snprintf(item, sizeof(item), "%s%s block=%d slots=%d width=%d src=%lld dst=%lld", out.empty() ? "" : " | ", a.name, a.block, a.d.nslots,
+             a.d.width, (long long)a.d.src, (long long)a.d.dst);
+    out += item;
+    per += (int64_t)a.d.nslots * a.d.width;
+  }
+  out += " | floats_per_utterance=" + std::to_string(per);
+  snprintf(buf, (size_t)len, "%s", out.c_str());
+  if ((int64_t)out.size() + 1 > (int64_t)len) {
+    wn_set_error("generate_admit_describe: the line needs %d bytes, the buffer has %d", (int)out.size() + 1, (int)len);
     return WN_E_INVALID;
   }
-  return generate_call(true, p, params, window, cond, B, first, length, deterministic, queued, nullptr, out, workspace, ws_floats, stream,
-                       reinterpret_cast<const WnSampleRow*>(rows), rows_flags);
+  return WN_OK;
+}
+
+extern "C" int wn_generate_admit(wn_plan* p, const float* params, const float* windows, const float* cond, int32_t k,
+                                 const int32_t* slots, int32_t B, int64_t position, int32_t deterministic,
+                                 const wn_sampling_row* rows_k, int32_t rows_flags_k, float* first_out, float* workspace,
+                                 int64_t ws_floats, float* scratch, int64_t scratch_floats, void* stream) {
+  const struct { const void* ptr; const char* name; } ptrs[] = {{p, "p"}, {params, "params"}, {windows, "windows"}, {slots, "slots"},
+                                                                {rows_k, "rows_k"}, {first_out, "first_out"}, {workspace, "workspace"},
+                                                                {scratch, "scratch"}};
+  for (const auto& a : ptrs)
+    if (!a.ptr) { wn_set_error("generate_admit: %s is null", a.name); return WN_E_INVALID; }
+  int rc = admit_slots_check("generate_admit", k, slots, B);
+  if (rc) return rc;
+  // (the admission's priming draw is sample position - 1, and the session goes on at `position`: both are 32-bit steps)
+  if (position < 1 || position > 0x7fffffffLL - 1) {
+    wn_set_error("generate_admit: position must lie in [1, 2147483646] (got %lld)", (long long)position);
+    return WN_E_INVALID;
+  }
+  rc = rows_table_check("generate_admit", "rows_k", "rows_flags_k", rows_k, rows_flags_k);
+  if (rc) return rc;
+  const int RF = wn_plan_receptive_field(p);
+  const GenLayout Gk = gen_layout(p, k, true), G = gen_layout(p, B, true);
+  if (ws_floats < G.total) {
+    wn_set_error("generate_admit: workspace too small (%lld floats, the queued session of B = %d needs %lld)", (long long)ws_floats, (int)B, (long long)G.total);
+    return WN_E_INVALID;
+  }
+  if (scratch_floats < Gk.total) {
+    wn_set_error("generate_admit: scratch too small (%lld floats, wn_generate_admit_scratch_floats(p, %d) is %lld)", (long long)scratch_floats, (int)k, (long long)Gk.total);
+    return WN_E_INVALID;
+  }
+  if (p->c.cond_inputs > 0 && !cond) { wn_set_error("generate_admit: cond is null on a conditioned net"); return WN_E_INVALID; }
+  // the tables first (a rebuild is a blocking copy: nothing of this call is queued yet), then the requests primed alone
+  // in the scratch at the session's time, then their state rows into the session's rows
+  const std::vector<AdmitSeg> segs = admit_segments(p, Gk, make_layout(p, k, RF, false), k, G, make_layout(p, B, RF, false), B);
+  if (segs.size() > 65535) { wn_set_error("generate_admit: %d state segments (the launch takes up to 65535)", (int)segs.size()); return WN_E_UNSUPPORTED; }
+  wn_exec& e = wnp::ex(p);
+  rc = ensure_admit_table(e, segs, k, B, slots);
+  if (rc) return rc;
+  rc = generate_call(GEN_ENTRY_BEGIN, p, params, windows, cond, k, position - 1, 1, deterministic, 1, nullptr, first_out, scratch,
+                     scratch_floats, stream, reinterpret_cast<const WnSampleRow*>(rows_k), rows_flags_k);
+  if (rc) return rc;
+  int64_t widest = 1;
+  for (const AdmitSeg& a : segs) widest = std::max(widest, (int64_t)a.d.nslots * a.d.width);
+  const dim3 grid((unsigned)std::min<int64_t>((widest + 255) / 256, 256), (unsigned)segs.size(), (unsigned)std::min(k, 65535));
+  hipLaunchKernelGGL(wn_gen_admit_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, e.admit.segs.d, e.admit.slots_d.d, k, B, scratch, workspace);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
 }

@@ -149,6 +149,7 @@ void exec_release(wn_exec* e) {
   if (e->ev_fjoin) (void)hipEventDestroy(e->ev_fjoin);
   if (e->side) (void)hipStreamDestroy(e->side);
   e->gen.release();
+  e->admit.release();
   if (g_bound_exec == e) g_bound_exec = nullptr;
   delete e;
 }

@@ -207,6 +207,20 @@ struct GenTable {
   void release() { valid = false; blocks.release(); }
 };
 
+// one segment of an admission's move (wn_gen_admit_rows_kernel, wn_generate.hip): nslots x width floats per utterance,
+// [slot][rows][width] at float offset src of the scratch workspace (k rows) and dst of the session's (B rows)
+struct WnAdmitSeg { int64_t src, dst; int32_t nslots, width; };
+
+// the device copies wn_generate_admit reads: the segment list of (k, B) and the slot list of the last admission
+struct AdmitTable {
+  bool valid = false;
+  int k = 0, B = 0;
+  std::vector<int32_t> slots;
+  DevTable<WnAdmitSeg> segs;
+  DevTable<int32_t> slots_d;
+  void release() { valid = false; segs.release(); slots_d.release(); }
+};
+
 }  // namespace wnp
 
 // The mutable side of a plan: per-caller state of the orchestration ("a wn_plan is immutable and shareable
@@ -227,6 +241,7 @@ struct wn_exec {
   const float* row_weights = nullptr; int64_t row_weights_n = 0;
   wnp::WgSchedule wg;           // the cached weight-gradient schedule of the last (B, T) layout it trained
   wnp::GenTable gen;            // the cached block table of the generation chains, for the last batch size it generated
+  wnp::AdmitTable admit;        // the cached segment and slot tables of the last admission (wn_generate_admit)
   // side stream: the side spans of the weight-gradient schedule run beside the per-block / skip kernels
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -532,6 +547,9 @@ struct GenRings {
   // layers_per_block > 1: hp[b][i] = [nslots_p[b][i]][B][D] inputs of dilated conv i + 1 (= outputs of conv i)
   std::vector<std::vector<float*>> hp;
   std::vector<std::vector<int>> nslots_p;
+  // the time of the captured window's index 0: index t of the priming pass goes to slot (t + t0) % nslots (0 unless the
+  // sequence begins at a position other than 0, wn_generate_rows_begin)
+  int64_t t0 = 0;
 };
 
 inline bool m16(int v) { return v > 0 && v % 16 == 0; }

@@ -228,9 +228,12 @@ class GenerationSession:
 
   position: samples emitted so far.  exact: the session runs under exact_fp32() from here on (a chunk left the range
   of the split-precision kernels, or the sequence was begun in exact-fp32 mode, whose priming pass does not prepare
-  what a split-precision step reads).  Otherwise a chunk runs in the math mode of the calling context."""
+  what a split-precision step reads).  Otherwise a chunk runs in the math mode of the calling context.
 
-  def __init__(self, model, sampling, condition, window, batch_size, use_queues, deterministic):
+  start: the index of the sequence's first sample; position begins there, the first chunk is
+  wn_generate_rows_begin.  admit() puts new requests into rows of the running batch."""
+
+  def __init__(self, model, sampling, condition, window, batch_size, use_queues, deterministic, start=0):
     L = _lib.lib()
     self._model, self._sampling, self._cond, self._window = model, sampling, condition, window
     # per-row controls: the device table of the session, read by every chunk (and by the exact-fp32 rerun of one)
@@ -247,7 +250,10 @@ class GenerationSession:
     self._slot = int(L.wn_generate_guard_slot(model._plan, self._B, self._queued))
     self._weights = (model.flat_params.data_ptr(), model._train_gen)
     self._failed = False
-    self.position = 0
+    self._start = int(start)
+    self._admitted = False                 # admit() has replaced rows: the window no longer begins this batch
+    self._scratch = {}                     # admit(): the scratch workspace of k rows, kept per k
+    self.position = self._start
     self.exact = False
 
   def generate(self, n):
@@ -255,22 +261,21 @@ class GenerationSession:
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
       raise ValueError(f'n must be an int >= 1 (got {n!r})')
     m, L, first = self._model, _lib.lib(), self.position
-    if self._failed:
-      raise RuntimeError('generation session: an earlier chunk failed; its state is invalid')
-    if (m.flat_params.data_ptr(), m._train_gen) != self._weights:
-      raise RuntimeError('generation session: the weights changed since the session was created (optimizer step, '
-                         'set_weights, finalize_variable_values, or an averaged_weights() boundary); start a new session')
+    self._check_usable()
     n = int(n)
     out = torch.empty(self._B, n, 1, dtype=torch.float32, device=m._device)
+    begins = first == self._start            # the chunk that begins the sequence from the window
 
     def run():
+      window = _lib.ptr(self._window) if begins else None
       if self._rows is not None:
-        _lib.check(L.wn_generate_rows_chunk(m._plan, _lib.ptr(m.flat_params), _lib.ptr(self._window) if first == 0 else None,
-                                            _lib.ptr(self._cond), self._B, first, n, self._det, self._queued,
-                                            _lib.ptr(self._rows), self._sampling.flags, _lib.ptr(out), _lib.ptr(self._ws),
-                                            self._ws.numel(), _lib.stream_ptr()))
+        # (start = 0 runs the call it always ran)
+        entry = L.wn_generate_rows_begin if begins and first > 0 else L.wn_generate_rows_chunk
+        _lib.check(entry(m._plan, _lib.ptr(m.flat_params), window, _lib.ptr(self._cond), self._B, first, n, self._det,
+                         self._queued, _lib.ptr(self._rows), self._sampling.flags, _lib.ptr(out), _lib.ptr(self._ws),
+                         self._ws.numel(), _lib.stream_ptr()))
         return
-      _lib.check(L.wn_generate_chunk(m._plan, _lib.ptr(m.flat_params), _lib.ptr(self._window) if first == 0 else None,
+      _lib.check(L.wn_generate_chunk(m._plan, _lib.ptr(m.flat_params), window,
                                      _lib.ptr(self._cond), self._B, first, n, self._det, self._queued,
                                      C.byref(self._sampling), _lib.ptr(out), _lib.ptr(self._ws), self._ws.numel(),
                                      _lib.stream_ptr()))
@@ -278,10 +283,10 @@ class GenerationSession:
       # exact fp32 cannot trip: no shadow copy, no host read
       with m.exact_fp32():
         run()
-      if first == 0:
+      if begins:
         self.exact = True
     else:
-      if first > 0:
+      if not begins:
         self._shadow.copy_(self._state)              # device to device, on the call's stream
       run()
       guard, watchdog = self._ws[self._slot:self._slot + 2].cpu()
@@ -292,7 +297,7 @@ class GenerationSession:
         # the tripped run has overwritten the raw-sample slots and ring slots of its steps: back to the state in front
         # of the chunk, the chunk again and everything after it on the exact-fp32 kernels (same seed: same draws); the
         # samples already handed out stand
-        if first > 0:
+        if not begins:
           self._state.copy_(self._shadow)
         with m.exact_fp32():
           run()
@@ -301,9 +306,105 @@ class GenerationSession:
     self.position = first + n
     return out
 
+  def _check_usable(self):
+    m = self._model
+    if self._failed:
+      raise RuntimeError('generation session: an earlier chunk failed; its state is invalid')
+    if (m.flat_params.data_ptr(), m._train_gen) != self._weights:
+      raise RuntimeError('generation session: the weights changed since the session was created (optimizer step, '
+                         'set_weights, finalize_variable_values, or an averaged_weights() boundary); start a new session')
+
+  def admit(self, slots, sample, condition=None, temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None):
+    """New requests into rows of the running batch (wn_generate_admit).  slots: an int or k distinct
+    ints in [0, B); sample: (k, >= receptive_field, 1), the prompts; condition: (k, cond_inputs) on a conditioned net;
+    the controls as in generate, scalars or k-sequences; stream: k ints, required.  Returns (k, 1, 1): every request's
+    first sample, index position - 1 of the session; from the next chunk on row slots[j] is request j.  That row, from
+    the returned sample on, is bit for bit a session of B = 1 begun with start = position - 1 from the request's own
+    arguments; every other row is what it is without the admission.  Queued sessions with per-row controls only, after
+    their first chunk."""
+    m, L = self._model, _lib.lib()
+    if not self._queued:
+      raise RuntimeError('generation session: admit needs a session with use_queues=True (the sliding window has no '
+                         'state rows to move)')
+    if self._rows is None:
+      raise RuntimeError('generation session: admit needs per-row controls (create the session with stream=)')
+    if self.position < 1 or self.position == self._start:
+      raise RuntimeError(f'generation session: admit needs position >= 1 and a begun sequence (position is {self.position}); '
+                         'generate the first chunk before admitting')
+    self._check_usable()
+    one = not isinstance(slots, (list, tuple, np.ndarray, torch.Tensor))
+    slot_list = [slots] if one else _as_rows('slots', slots)
+    if slot_list is None or len(slot_list) < 1:
+      raise ValueError(f'slots must be an int or a sequence of distinct ints (got {slots!r})')
+    for j, v in enumerate(slot_list):
+      if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < self._B:
+        raise ValueError(f'slots[{j}] must be an int in [0, {self._B}) (got {v!r})')
+      if v in slot_list[:j]:
+        raise ValueError(f'slots[{j}] = {v} is a duplicate (the slots must be distinct)')
+    slot_list = [int(v) for v in slot_list]
+    k, rf = len(slot_list), m.receptive_field
+    sample = torch.as_tensor(sample, dtype=torch.float32, device=m._device)
+    if sample.dim() != 3 or sample.shape[0] != k or sample.shape[2] != 1 or sample.shape[1] < rf:
+      raise ValueError(f'sample must have shape ({k}, >= {rf}, 1) for {k} slots (got {tuple(sample.shape)})')
+    sample = sample[:, -rf:, :].contiguous()
+    if m.conditioning is not None and condition is None:
+      raise ValueError('Conditioning must be provided.')
+    if condition is not None:
+      condition = torch.as_tensor(condition, dtype=torch.float32, device=m._device).contiguous()
+      if self._cond is None or tuple(condition.shape) != (k,) + tuple(self._cond.shape[1:]):
+        want = None if self._cond is None else (k,) + tuple(self._cond.shape[1:])
+        raise ValueError(f'condition must have shape {want} (got {tuple(condition.shape)})')
+    if stream is None:
+      raise ValueError('stream is required: one Philox stream id per admitted request')
+    new = m._sampling_rows(k, temperature, top_k, seed, top_p, stream, 2 ** m.bits, True)
+    # the whole table again: the error text names the session's row, the flags are the new union
+    old = self._sampling
+    entries = list(old.entries)
+    streams = list(old.streams) if old.streams is not None else list(range(self._B))
+    for j, b in enumerate(slot_list):
+      entries[b], streams[b] = new.entries[j], new.streams[j]
+    table = _RowControls(entries, streams, _lib.HEADS[m.sampling_function], 2 ** m.bits)
+    rows_k = new.device_table(m._device)
+    if k not in self._scratch:
+      self._scratch[k] = torch.zeros(int(L.wn_generate_admit_scratch_floats(m._plan, k)), dtype=torch.float32, device=m._device)
+    scratch = self._scratch[k]
+    first_out = torch.empty(k, 1, 1, dtype=torch.float32, device=m._device)
+    slots_c = (C.c_int32 * k)(*slot_list)
+
+    def run():
+      _lib.check(L.wn_generate_admit(m._plan, _lib.ptr(m.flat_params), _lib.ptr(sample), _lib.ptr(condition), k, slots_c,
+                                     self._B, self.position, self._det, _lib.ptr(rows_k), new.flags, _lib.ptr(first_out),
+                                     _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(scratch), scratch.numel(),
+                                     _lib.stream_ptr()))
+    if self.exact or L.wn_debug_value(1) == 1:
+      with m.exact_fp32():
+        run()
+    else:
+      run()
+      slot = int(L.wn_generate_guard_slot(m._plan, k, 1))
+      if not (float(scratch[slot]) < L.wn_range_limit()):
+        # the admission's priming pass left the range of the split-precision kernels: again on the exact-fp32 kernels
+        # (the move overwrites the same rows: nothing to restore), and the session stays there
+        with m.exact_fp32():
+          run()
+        m.generation_guard_trips += 1
+        self.exact = True
+    # the session's own records: rows slots[j] of the device table (in place: the chunks read this tensor) and of the condition
+    self._sampling = table
+    self._rows.copy_(table.device_table(m._device))
+    if condition is not None:
+      if not self._admitted:
+        self._cond = self._cond.clone()          # (the caller's tensor stays as it is)
+      self._cond[torch.tensor(slot_list, device=m._device)] = condition
+    self._admitted = True
+    return first_out
+
   def reset(self):
     """Back to the start: the next chunk begins the sequence again from the window, on the same workspace."""
-    self.position = 0
+    if self._admitted:
+      raise RuntimeError('generation session: reset after admit is not possible (the rows the window began are gone); '
+                         'start a new session')
+    self.position = self._start
     self._failed = False
 
 
@@ -1278,15 +1379,22 @@ class WaveNet(torch.nn.Module):
     return sampling, condition, sample, batch_size
 
   def generation_session(self, batch_size: int = 1, condition=None, sample=None, use_queues=False, deterministic=False,
-                         temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None):
+                         temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None, start=0):
     """A sequence made in pieces: the arguments of generate without `length`, with the same checks (per-utterance
     controls and `stream` included: the session keeps the device table of its rows).  The chunks of
     session.generate(n), concatenated, are bit for bit generate(total, same arguments).  The
     session owns its workspace and is bound to the weights as they are now: after an optimizer step, set_weights,
-    finalize_variable_values, or entering / leaving averaged_weights() its generate raises RuntimeError."""
+    finalize_variable_values, or entering / leaving averaged_weights() its generate raises RuntimeError.
+    start: an int >= 0, the index of the sequence's first sample -- the draw of sample t uses the
+    Philox counter (stream, t), so a sequence begun at `start` draws what a request admitted at that position draws
+    (GenerationSession.admit).  start > 0 needs per-row controls: passing stream= is enough."""
+    if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or start < 0:
+      raise ValueError(f'start must be an int >= 0 (got {start!r})')
     sampling, condition, window, batch_size = self._generation_args(batch_size, condition, sample, deterministic,
                                                                     temperature, top_k, seed, top_p, stream)
-    return GenerationSession(self, sampling, condition, window, batch_size, use_queues, deterministic)
+    if start > 0 and not isinstance(sampling, _RowControls):
+      raise ValueError('start > 0 needs per-row sampling controls: pass stream= (one Philox stream id per utterance)')
+    return GenerationSession(self, sampling, condition, window, batch_size, use_queues, deterministic, int(start))
 
   def generate_stream(self, length, chunk, **kwargs):
     """Generator over a generation_session(**kwargs): yields (B, min(chunk, rest), 1) tensors until `length` samples are
