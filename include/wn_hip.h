@@ -408,7 +408,9 @@ int wn_generate_rows_chunk(wn_plan* p, const float* params, const float* window,
  *   The defining property: row slots[j] of the session, from index position - 1 on (first_out[j], then the row of the later
  *   chunks), is bit for bit row 0 of wn_generate_rows_begin at B = 1, first = position - 1 with request j's window,
  *   condition and record; every row not in `slots` is bit for bit what it is without the admission.
- *   A draw at position t uses counter (stream, t): what a request draws depends on the position it was admitted at.
+ *   Through wn_generate_rows_chunk / wn_generate_rows_begin / wn_generate_admit a draw at position t uses counter
+ *   (stream, t): what a request draws there depends on the position it was admitted at.  Their *_origin forms below give
+ *   every row a clock of its own, and with it draws that depend on the request alone.
  *   Range guard: the scratch has its own slot, wn_generate_guard_slot(p, k, 1), which speaks of the admission's priming
  *   pass; the session's slot is untouched.  A tripped admission is repeated in exact-fp32 mode (the move overwrites the
  *   same rows), and the session then stays in that mode.
@@ -434,6 +436,39 @@ int wn_generate_admit(wn_plan* p, const float* params, const float* windows, con
                       const wn_sampling_row* rows_k, int32_t rows_flags_k, float* first_out, float* workspace,
                       int64_t ws_floats, float* scratch, int64_t scratch_floats, void* stream);
 int wn_generate_admit_describe(const wn_plan* p, int32_t k, int32_t B, char* buf, int32_t len);
+/* ---- a row's own clock ----
+ * The three entry points above with one more argument, `origin`: a DEVICE array of one uint64_t per utterance of the call
+ * (B values; origin_k: k values), 8-byte aligned, or NULL.  Utterance b draws sample t from counter
+ * (stream[b], t - origin[b]) under key seed[b]; the subtraction is unsigned 64-bit.  Nothing else changes: output columns,
+ * rings, tau, the relay's epoch and the window parity follow t, and the network is time invariant.  So a request whose
+ * origin is the index of its first sample draws from counters (stream, 0), (stream, 1), ... wherever in the sequence, in
+ * whichever row and beside whichever other rows it runs.
+ * The defining property: a request admitted at `position` with origin_k[j] = position - 1, whose row then carries that
+ *   origin in the session's array, is from first_out[j] on bit for bit row 0 of wn_generate_rows_chunk(window, first = 0, ...)
+ *   at B = 1 with the request's window, condition and record -- the request alone, from position 0.  Likewise
+ *   wn_generate_rows_begin_origin at `first` with every origin = first is wn_generate_rows_chunk(window, 0, ...).
+ * The array is treated like `rows`: it lies outside the workspace and is only read; it must stay as it is until the
+ *   call's work on the stream is done, and a continuation passes the same array.  After wn_generate_admit_origin the
+ *   caller writes origin_k[j] into its own session array at slots[j], as it does for the records.
+ * origin == NULL is the entry point without the argument, bit for bit (the same code runs); an array of zeros gives those
+ *   bits too.  deterministic != 0 ignores the array.  queued == 0 (the sliding window) takes it like the table.
+ * The library cannot see the values: origin[b] <= the index of every sample utterance b draws in the call is the
+ *   caller's duty.  Beyond it the counter word wraps modulo 2^64 (a row then draws from (stream, 2^64 - d)); nothing faults.
+ * WN_E_INVALID, before the device is touched and before any other argument is looked at: origin / origin_k not aligned to
+ *   8 bytes, the message naming the argument.  Every other error is the one of the entry point without the argument.
+ * Out of scope: origins in wn_sample_waveform_sampled and in the training step's draw; a per-row deterministic flag. */
+int wn_generate_rows_chunk_origin(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                                  int64_t first, int32_t length, int32_t deterministic, int32_t queued,
+                                  const wn_sampling_row* rows, int32_t rows_flags, const uint64_t* origin, float* out,
+                                  float* workspace, int64_t ws_floats, void* stream);
+int wn_generate_rows_begin_origin(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                                  int64_t first, int32_t length, int32_t deterministic, int32_t queued,
+                                  const wn_sampling_row* rows, int32_t rows_flags, const uint64_t* origin, float* out,
+                                  float* workspace, int64_t ws_floats, void* stream);
+int wn_generate_admit_origin(wn_plan* p, const float* params, const float* windows, const float* cond, int32_t k,
+                             const int32_t* slots, int32_t B, int64_t position, int32_t deterministic,
+                             const wn_sampling_row* rows_k, int32_t rows_flags_k, const uint64_t* origin_k, float* first_out,
+                             float* workspace, int64_t ws_floats, float* scratch, int64_t scratch_floats, void* stream);
 int64_t wn_generate_workspace_floats(const wn_plan* p, int32_t B, int32_t queued);
 /* The one contiguous part of the generation workspace that steps write and a continuation reads, as a float offset and a
  * float count.  queued: from the raw-sample slots to the end of the layout (rings, inner rings, per-step rows, partial

@@ -135,6 +135,13 @@ _SIGS = {
     'wn_generate_admit_scratch_floats': (C.c_int64, [_P, C.c_int32]),
     'wn_generate_admit': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int32, _P,
                                     C.c_int32, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    # (the three above with the rows' clock origins, a device array of uint64, behind the flags)
+    'wn_generate_rows_chunk_origin': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P,
+                                                C.c_int32, _P, _P, _P, C.c_int64, _P]),
+    'wn_generate_rows_begin_origin': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P,
+                                                C.c_int32, _P, _P, _P, C.c_int64, _P]),
+    'wn_generate_admit_origin': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int32, _P,
+                                           C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
     'wn_generate_admit_describe': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
     'wn_generate_state_range': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'wn_generate_workspace_floats': (C.c_int64, [_P, C.c_int32, C.c_int32]),

@@ -612,11 +612,12 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
 // the next layer through LDS, exactly as the chain kernel hands x between blocks.  Per tile this is the
 // thin rows GEMM's sequence -- k-steps in order, lo*hi, hi*lo, hi*hi, then acc + bias, activation -- so
 // the logits are bit-identical to the per-layer launches (and to the sliding window).
-// ROWS: the sampling tails draw with the utterance's own record rows[utt] (per-row controls);
-// false is the body of before, instruction for instruction.
+// ROWS: the sampling tails draw with the utterance's own record rows[utt] (per-row controls) and,
+// with `origin`, on the utterance's own clock (counter word a.offset - origin[utt]); false is the body
+// of before, instruction for instruction.
 template <bool ROWS = false>
 __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, unsigned char* smem,
-                                             const WnSampleRow* rows = nullptr) {
+                                             const WnSampleRow* rows = nullptr, const uint64_t* origin = nullptr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int tl = lane & 31, h = lane >> 5;
   const int utt = tile * 32 + tl;
@@ -770,7 +771,7 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
         const float* p = lg + threadIdx.x * 32;
         float v;
         if constexpr (ROWS)         // (row is the global utterance index: tile * 32 + thread)
-          v = a.tail == 3 ? wn_mix_det_row(p, a.mix_M) : wn_mix_rand_row_tab(p, a.mix_M, a.mix_kind, rows, row, a.offset);
+          v = a.tail == 3 ? wn_mix_det_row(p, a.mix_M) : wn_mix_rand_row_tab(p, a.mix_M, a.mix_kind, rows, row, a.offset, origin);
         else
           v = a.tail == 3 ? wn_mix_det_row(p, a.mix_M)
               : a.ctl.on() ? wn_mix_rand_row<true>(p, a.mix_M, a.mix_kind, row, a.seed, a.offset, a.ctl)
@@ -797,7 +798,8 @@ __device__ __forceinline__ void gn_head_body(const WnGenHeadArgs& a, int tile, u
       float v;
       if constexpr (ROWS)           // (the record of the global utterance index, in scalar registers: uniform branches)
         v = a.tail == 1 ? wn_cat_det_row(l, C, lane, a.inv_lv)
-                        : wn_cat_rand_row_tab<false>(l, C, lane, q, wn_sample_row_uniform(rows, row), a.offset, a.inv_lv);
+                        : wn_cat_rand_row_tab<false>(l, C, lane, q, wn_sample_row_uniform(rows, row),
+                                                     wn_sample_clock_uniform(origin, row, a.offset), a.inv_lv);
       else
         v = a.tail == 1 ? wn_cat_det_row(l, C, lane, a.inv_lv)
             : a.ctl.on() ? wn_cat_rand_row<true, false>(l, C, lane, q, row, a.seed, a.offset, a.inv_lv, a.ctl)
@@ -832,10 +834,10 @@ __global__ __launch_bounds__(512) void wn_gen_head_pre_kernel(WnGenHeadArgs ha, 
 // of their first use, so the twins land behind every kernel of before in the code object and those keep their offsets.
 template <int R32, int D32, int KS>
 __global__ __launch_bounds__(512) void wn_gen_head_rows_kernel(WnGenHeadArgs ha, WnGenStepArgs ga, int ntiles,
-                                                                const WnSampleRow* rows) {
+                                                                const WnSampleRow* rows, const uint64_t* origin) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 16 * 2048];
   if (R32 == 0 || (int)blockIdx.x < ntiles) {
-    gn_head_body<true>(ha, (int)blockIdx.x, smem, rows);
+    gn_head_body<true>(ha, (int)blockIdx.x, smem, rows, origin);
   } else if constexpr (R32 > 0) {
     if (threadIdx.x >= 64) return;
     const int j = (int)blockIdx.x - ntiles;
@@ -844,7 +846,7 @@ __global__ __launch_bounds__(512) void wn_gen_head_rows_kernel(WnGenHeadArgs ha,
 }
 // (defined at the end of the file) the launch of the twin for (R, KS), or R = 0 for the head alone; false: unsupported shape
 static bool gn_launch_head_rows(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, dim3 grid, int nt, hipStream_t s,
-                                const WnSampleRow* tab);
+                                const WnSampleRow* tab, const uint64_t* origin);
 
 static int gn_head_check(const WnGenHeadArgs& a) {
   if (a.nlayers < 1 || a.nlayers > WN_GEN_HEAD_MAX) { wn_set_error("gen_head: bad layer count"); return WN_E_UNSUPPORTED; }
@@ -858,13 +860,14 @@ static int gn_head_check(const WnGenHeadArgs& a) {
   if (a.tail == 2 && a.ctl.top_p > 0.f) { wn_set_error("gen_head: a draw under top_p takes the sampler launch, not this tail"); return WN_E_INVALID; }
   return WN_OK;
 }
-int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, hipStream_t s, const WnSampleRow* tab) {
+int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, hipStream_t s, const WnSampleRow* tab,
+                           const uint64_t* origin) {
   const int rc = gn_head_check(a);
   if (rc) return rc;
   const int nt = (a.B + 31) / 32;
   const dim3 grid((unsigned)(nt + nt * g.nblocks));
   if (tab && (a.tail == 2 || a.tail == 4)) {
-    if (!gn_launch_head_rows(a, g, R, KS, grid, nt, s, tab)) { wn_set_error("gen_head_pre: unsupported shape"); return WN_E_UNSUPPORTED; }
+    if (!gn_launch_head_rows(a, g, R, KS, grid, nt, s, tab, origin)) { wn_set_error("gen_head_pre: unsupported shape"); return WN_E_UNSUPPORTED; }
   } else if (R == 32 && KS == 2) hipLaunchKernelGGL((wn_gen_head_pre_kernel<1, 1, 2>), grid, dim3(512), 0, s, a, g, nt);
   else if (R == 32 && KS == 3) hipLaunchKernelGGL((wn_gen_head_pre_kernel<1, 1, 3>), grid, dim3(512), 0, s, a, g, nt);
   else if (R == 64 && KS == 2) hipLaunchKernelGGL((wn_gen_head_pre_kernel<2, 2, 2>), grid, dim3(512), 0, s, a, g, nt);
@@ -873,7 +876,7 @@ int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R
   return WN_OK;
 }
 
-int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s, const WnSampleRow* tab) {
+int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s, const WnSampleRow* tab, const uint64_t* origin) {
   const int rc = gn_head_check(a);
   if (rc) return rc;
   if (a.f32_K > 0 && (a.f32_K != a.N[a.nlayers - 1] || a.f32_K % 64 != 0 || a.f32_N < 1 || a.f32_N > 32 ||
@@ -883,7 +886,7 @@ int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s, const WnSampleRow*
   }
   if (a.f32_K == 0 && a.tail >= 3) { wn_set_error("gen_head: the mixture tail follows the fp32 layer"); return WN_E_UNSUPPORTED; }
   if (tab && (a.tail == 2 || a.tail == 4))
-    gn_launch_head_rows(a, WnGenStepArgs{}, 0, 0, dim3((unsigned)((a.B + 31) / 32)), (a.B + 31) / 32, s, tab);
+    gn_launch_head_rows(a, WnGenStepArgs{}, 0, 0, dim3((unsigned)((a.B + 31) / 32)), (a.B + 31) / 32, s, tab, origin);
   else
     hipLaunchKernelGGL(wn_gen_head_kernel, dim3((unsigned)((a.B + 31) / 32)), dim3(512), 0, s, a);
   WN_HIP_CHECK(hipGetLastError());
@@ -940,11 +943,11 @@ int wn_launch_gen_blocks(const WnGenStepArgs& a, int R, int KS, int what, hipStr
 }
 
 static bool gn_launch_head_rows(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, dim3 grid, int nt, hipStream_t s,
-                                const WnSampleRow* tab) {
-  if (R == 0) hipLaunchKernelGGL((wn_gen_head_rows_kernel<0, 0, 0>), grid, dim3(512), 0, s, a, g, nt, tab);
-  else if (R == 32 && KS == 2) hipLaunchKernelGGL((wn_gen_head_rows_kernel<1, 1, 2>), grid, dim3(512), 0, s, a, g, nt, tab);
-  else if (R == 32 && KS == 3) hipLaunchKernelGGL((wn_gen_head_rows_kernel<1, 1, 3>), grid, dim3(512), 0, s, a, g, nt, tab);
-  else if (R == 64 && KS == 2) hipLaunchKernelGGL((wn_gen_head_rows_kernel<2, 2, 2>), grid, dim3(512), 0, s, a, g, nt, tab);
+                                const WnSampleRow* tab, const uint64_t* origin) {
+  if (R == 0) hipLaunchKernelGGL((wn_gen_head_rows_kernel<0, 0, 0>), grid, dim3(512), 0, s, a, g, nt, tab, origin);
+  else if (R == 32 && KS == 2) hipLaunchKernelGGL((wn_gen_head_rows_kernel<1, 1, 2>), grid, dim3(512), 0, s, a, g, nt, tab, origin);
+  else if (R == 32 && KS == 3) hipLaunchKernelGGL((wn_gen_head_rows_kernel<1, 1, 3>), grid, dim3(512), 0, s, a, g, nt, tab, origin);
+  else if (R == 64 && KS == 2) hipLaunchKernelGGL((wn_gen_head_rows_kernel<2, 2, 2>), grid, dim3(512), 0, s, a, g, nt, tab, origin);
   else return false;
   return true;
 }

@@ -96,7 +96,8 @@ __global__ void wn_gen_emit_kernel(const float* samp, int B, float* out, int len
 
 // sample from the logits rows [B][Cout] (src/model.py:253-255 + sample_waveform)
 int sample_rows(wn_plan* p, const float* logits_rows, int B, bool deterministic, uint64_t seed, uint64_t step,
-                float* probs_tmp, float* samp, hipStream_t s, WnSampleCtl ctl, const WnSampleRow* tab = nullptr) {
+                float* probs_tmp, float* samp, hipStream_t s, WnSampleCtl ctl, const WnSampleRow* tab = nullptr,
+                const uint64_t* origin = nullptr) {
   const float* pred = logits_rows;
   int rc;
   if (p->c.head == WN_HEAD_CATEGORICAL) {
@@ -105,7 +106,7 @@ int sample_rows(wn_plan* p, const float* logits_rows, int B, bool deterministic,
     pred = probs_tmp;
   }
   if (deterministic) return wn_launch_sample_det(pred, B, p->Cout, p->c.num_mixtures, p->c.bits, samp, s);
-  return wn_launch_sample_rand(pred, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, step, samp, s, ctl, WN_EMIT_NONE, tab);
+  return wn_launch_sample_rand(pred, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, step, samp, s, ctl, WN_EMIT_NONE, tab, origin);
 }
 
 // the compute units of the current device (-1: unknown)
@@ -168,6 +169,9 @@ struct GenCall {
   // table every stochastic draw of the call -- sliding window, priming step, sampler launch, head tail -- reads its row's
   // record; ctl is the union of the rows (what gen_paths and the launchers' checks look at) and seed is unused.
   const WnSampleRow* rows = nullptr;
+  // the rows' clocks (the *_origin entry points): the caller's device array, one origin per utterance,
+  // or null.  Travels with the table to every draw that reads it: row b draws sample t from counter (stream, t - origin[b]).
+  const uint64_t* origin = nullptr;
   float* out; float* ws; hipStream_t s;
   int RF;
   GenLayout G;
@@ -236,7 +240,7 @@ struct GenCall {
     for (int step = first; step < end; ++step) {
       int rc = window_forward(win[step & 1], primes && step == first, nullptr);
       if (rc) return rc;
-      rc = sample_rows(p, last, B, deterministic, seed, (uint64_t)step, lastp, samp, s, ctl, rows);
+      rc = sample_rows(p, last, B, deterministic, seed, (uint64_t)step, lastp, samp, s, ctl, rows, origin);
       if (rc) return rc;
       hipLaunchKernelGGL(wn_gen_shift_kernel, dim3((B * RF + 255) / 256), dim3(256), 0, s, win[step & 1], samp, B, RF,
                          win[(step + 1) & 1], out, length, step - first);
@@ -251,7 +255,7 @@ struct GenCall {
   int prime() {
     int rc = window_forward(win[first & 1], true, &R);
     if (rc) return rc;
-    rc = sample_rows(p, last, B, deterministic, seed, (uint64_t)first, lastp, samp, s, ctl, rows);
+    rc = sample_rows(p, last, B, deterministic, seed, (uint64_t)first, lastp, samp, s, ctl, rows, origin);
     if (rc) return rc;
     // sample `first` is x[RF + first]; it becomes the network input at time tau = RF + first (output column 0)
     hipLaunchKernelGGL(wn_gen_emit_kernel, dim3((B + 255) / 256), dim3(256), 0, s, samp, B, out, length, 0, emit(first).xin_slot);
@@ -419,9 +423,9 @@ struct GenCall {
       if (ha.tail) { ha.offset = (uint64_t)step; ha.em = emit(step); }
       if (gp.pre_in_head && step + 1 < end) {
         ga.tau = tau(step) + 1;
-        return wn_launch_gen_head_pre(ha, ga, p->R, p->KS, s, rows);
+        return wn_launch_gen_head_pre(ha, ga, p->R, p->KS, s, rows, origin);
       }
-      return wn_launch_gen_head(ha, s, rows);
+      return wn_launch_gen_head(ha, s, rows, origin);
     }
     const float* in = hin;
     int hc = gp.hc0;
@@ -448,10 +452,10 @@ struct GenCall {
       case GEN_SAMPLE_DET:
         return wn_launch_sample_det(last, B, p->Cout, p->c.num_mixtures, p->c.bits, cat ? nullptr : samp, s, emit(step));
       case GEN_SAMPLE_RAND:
-        return wn_launch_sample_rand(last, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, (uint64_t)step, samp, s, ctl, emit(step), rows);
+        return wn_launch_sample_rand(last, B, p->Cout, p->c.num_mixtures, p->c.bits, p->c.head, seed, (uint64_t)step, samp, s, ctl, emit(step), rows, origin);
       case GEN_SAMPLE_ROWS: break;
     }
-    const int rc = sample_rows(p, last, B, false, seed, (uint64_t)step, lastp, samp, s, ctl, rows);
+    const int rc = sample_rows(p, last, B, false, seed, (uint64_t)step, lastp, samp, s, ctl, rows, origin);
     if (rc) return rc;
     hipLaunchKernelGGL(wn_gen_emit_kernel, dim3((B + 255) / 256), dim3(256), 0, s, samp, B, out, length, step - first, emit(step).xin_slot);
     WN_HIP_CHECK(hipGetLastError());
@@ -519,11 +523,12 @@ extern "C" int wn_generate(wn_plan* p, const float* params, const float* window,
 // wn_generate_sampled (window given, first = 0) and wn_generate_chunk
 // ... and wn_generate_rows_chunk: rows (device) in place of sampling, with the union of its rows from rows_flags
 // ... and wn_generate_rows_begin (GEN_ENTRY_BEGIN): a window at any first >= 0
+// ... and their *_origin forms: origin (device, with rows only), the clock origin of every utterance, or null
 enum GenEntry { GEN_ENTRY_ONE, GEN_ENTRY_CHUNK, GEN_ENTRY_BEGIN };
 static int generate_call(GenEntry entry, wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                          int64_t first, int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
                          float* out, float* workspace, int64_t ws_floats, void* stream,
-                         const WnSampleRow* rows = nullptr, int32_t rows_flags = 0) {
+                         const WnSampleRow* rows = nullptr, int32_t rows_flags = 0, const uint64_t* origin = nullptr) {
   const bool chunk = entry != GEN_ENTRY_ONE, begins = entry == GEN_ENTRY_BEGIN;
   WnSampleCtl ctl = WN_SAMPLE_CTL_OFF;
   if (rows) {
@@ -557,6 +562,7 @@ static int generate_call(GenEntry entry, wn_plan* p, const float* params, const 
   c.bind(p, params, cond, B, (int)first, length, window != nullptr, deterministic != 0, rows ? 0 : sampling->seed, ctl, out, workspace,
          (hipStream_t)stream, std::move(G));
   c.rows = rows;
+  c.origin = c.deterministic ? nullptr : origin;
   int rc = c.begin(window);
   if (rc) return rc;
   if (!queued) return c.sliding_window();
@@ -651,25 +657,49 @@ static int rows_table_check(const char* who, const char* rows_name, const char* 
   return WN_OK;
 }
 
+// the clock origins of a *_origin entry point, before anything else is looked at: null is "none"
+static int origin_check(const char* who, const char* name, const uint64_t* origin) {
+  if ((uintptr_t)origin % 8 != 0) { wn_set_error("%s: %s must be aligned to 8 bytes", who, name); return WN_E_INVALID; }
+  return WN_OK;
+}
+
+extern "C" int wn_generate_rows_chunk_origin(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                                             int64_t first, int32_t length, int32_t deterministic, int32_t queued,
+                                             const wn_sampling_row* rows, int32_t rows_flags, const uint64_t* origin, float* out,
+                                             float* workspace, int64_t ws_floats, void* stream) {
+  int rc = origin_check("generate", "origin", origin);
+  if (rc) return rc;
+  rc = rows_table_check("generate", "rows", "rows_flags", rows, rows_flags);
+  if (rc) return rc;
+  return generate_call(GEN_ENTRY_CHUNK, p, params, window, cond, B, first, length, deterministic, queued, nullptr, out, workspace, ws_floats,
+                       stream, reinterpret_cast<const WnSampleRow*>(rows), rows_flags, origin);
+}
 extern "C" int wn_generate_rows_chunk(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                                       int64_t first, int32_t length, int32_t deterministic, int32_t queued,
                                       const wn_sampling_row* rows, int32_t rows_flags, float* out, float* workspace,
                                       int64_t ws_floats, void* stream) {
-  const int rc = rows_table_check("generate", "rows", "rows_flags", rows, rows_flags);
-  if (rc) return rc;
-  return generate_call(GEN_ENTRY_CHUNK, p, params, window, cond, B, first, length, deterministic, queued, nullptr, out, workspace, ws_floats,
-                       stream, reinterpret_cast<const WnSampleRow*>(rows), rows_flags);
+  return wn_generate_rows_chunk_origin(p, params, window, cond, B, first, length, deterministic, queued, rows, rows_flags, nullptr, out,
+                                       workspace, ws_floats, stream);
 }
 
 // ---- a sequence that begins at a position other than 0, and admission into a running batch ----
+extern "C" int wn_generate_rows_begin_origin(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
+                                             int64_t first, int32_t length, int32_t deterministic, int32_t queued,
+                                             const wn_sampling_row* rows, int32_t rows_flags, const uint64_t* origin, float* out,
+                                             float* workspace, int64_t ws_floats, void* stream) {
+  int rc = origin_check("generate", "origin", origin);
+  if (rc) return rc;
+  rc = rows_table_check("generate", "rows", "rows_flags", rows, rows_flags);
+  if (rc) return rc;
+  return generate_call(GEN_ENTRY_BEGIN, p, params, window, cond, B, first, length, deterministic, queued, nullptr, out, workspace, ws_floats,
+                       stream, reinterpret_cast<const WnSampleRow*>(rows), rows_flags, origin);
+}
 extern "C" int wn_generate_rows_begin(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                                       int64_t first, int32_t length, int32_t deterministic, int32_t queued,
                                       const wn_sampling_row* rows, int32_t rows_flags, float* out, float* workspace,
                                       int64_t ws_floats, void* stream) {
-  const int rc = rows_table_check("generate", "rows", "rows_flags", rows, rows_flags);
-  if (rc) return rc;
-  return generate_call(GEN_ENTRY_BEGIN, p, params, window, cond, B, first, length, deterministic, queued, nullptr, out, workspace, ws_floats,
-                       stream, reinterpret_cast<const WnSampleRow*>(rows), rows_flags);
+  return wn_generate_rows_begin_origin(p, params, window, cond, B, first, length, deterministic, queued, rows, rows_flags, nullptr, out,
+                                       workspace, ws_floats, stream);
 }
 
 namespace {
@@ -794,12 +824,24 @@ extern "C" int wn_generate_admit(wn_plan* p, const float* params, const float* w
                                  const int32_t* slots, int32_t B, int64_t position, int32_t deterministic,
                                  const wn_sampling_row* rows_k, int32_t rows_flags_k, float* first_out, float* workspace,
                                  int64_t ws_floats, float* scratch, int64_t scratch_floats, void* stream) {
+  return wn_generate_admit_origin(p, params, windows, cond, k, slots, B, position, deterministic, rows_k, rows_flags_k, nullptr, first_out,
+                                  workspace, ws_floats, scratch, scratch_floats, stream);
+}
+
+// origin_k: the clocks of the k requests in the scratch priming pass (their priming draw is sample position - 1), or null
+extern "C" int wn_generate_admit_origin(wn_plan* p, const float* params, const float* windows, const float* cond, int32_t k,
+                                        const int32_t* slots, int32_t B, int64_t position, int32_t deterministic,
+                                        const wn_sampling_row* rows_k, int32_t rows_flags_k, const uint64_t* origin_k,
+                                        float* first_out, float* workspace, int64_t ws_floats, float* scratch,
+                                        int64_t scratch_floats, void* stream) {
+  int rc = origin_check("generate_admit", "origin_k", origin_k);
+  if (rc) return rc;
   const struct { const void* ptr; const char* name; } ptrs[] = {{p, "p"}, {params, "params"}, {windows, "windows"}, {slots, "slots"},
                                                                 {rows_k, "rows_k"}, {first_out, "first_out"}, {workspace, "workspace"},
                                                                 {scratch, "scratch"}};
   for (const auto& a : ptrs)
     if (!a.ptr) { wn_set_error("generate_admit: %s is null", a.name); return WN_E_INVALID; }
-  int rc = admit_slots_check("generate_admit", k, slots, B);
+  rc = admit_slots_check("generate_admit", k, slots, B);
   if (rc) return rc;
   // (the admission's priming draw is sample position - 1, and the session goes on at `position`: both are 32-bit steps)
   if (position < 1 || position > 0x7fffffffLL - 1) {
@@ -827,7 +869,7 @@ extern "C" int wn_generate_admit(wn_plan* p, const float* params, const float* w
   rc = ensure_admit_table(e, segs, k, B, slots);
   if (rc) return rc;
   rc = generate_call(GEN_ENTRY_BEGIN, p, params, windows, cond, k, position - 1, 1, deterministic, 1, nullptr, first_out, scratch,
-                     scratch_floats, stream, reinterpret_cast<const WnSampleRow*>(rows_k), rows_flags_k);
+                     scratch_floats, stream, reinterpret_cast<const WnSampleRow*>(rows_k), rows_flags_k, origin_k);
   if (rc) return rc;
   int64_t widest = 1;
   for (const AdmitSeg& a : segs) widest = std::max(widest, (int64_t)a.d.nslots * a.d.width);

@@ -352,15 +352,16 @@ struct WnGenHeadArgs {
 // rows (here and in wn_launch_gen_head_pre): per-row controls of tails 2 and 4, [B] records or null.  Non-null launches the
 // *_rows twins of the head kernels, in which utterance u draws with rows[u] (controls, key, counter row); a.ctl is then the
 // union of the rows and a.seed is unused.  The table is a kernel argument of the twins only: WnGenHeadArgs, and with it the
-// argument block of the kernels without a table, is what it was.
-int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s, const WnSampleRow* rows = nullptr);
+// argument block of the kernels without a table, is what it was.  origin (with rows only): [B] clock origins or null, one more
+// argument of the twins -- utterance u draws with the counter word a.offset - origin[u].
+int wn_launch_gen_head(const WnGenHeadArgs& a, hipStream_t s, const WnSampleRow* rows = nullptr, const uint64_t* origin = nullptr);
 int wn_gen_blocks_supported(int R, int D, int KS);
 int wn_gen_chain_max_blocks();
 int64_t wn_gen_u0_floats(int B, int nblocks, int D);
 int wn_gen_skip_fusable(int S);
 int wn_launch_gen_blocks(const WnGenStepArgs& a, int R, int KS, int what, hipStream_t s);
 int wn_launch_gen_head_pre(const WnGenHeadArgs& a, const WnGenStepArgs& g, int R, int KS, hipStream_t s,
-                           const WnSampleRow* rows = nullptr);
+                           const WnSampleRow* rows = nullptr, const uint64_t* origin = nullptr);
 
 // ---------------------------------------------------------------- elementwise (wn_elem.hip)
 int wn_launch_add(const float* a, const float* b, float* out, int64_t n, hipStream_t s);
@@ -449,14 +450,15 @@ int wn_launch_sample_det(const float* pred, int64_t rows, int C, int M, int bits
 // stochastic samplers (Philox4x32-10 keyed by seed, counter = row)
 int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t seed, uint64_t offset,
                           float* out, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF, WnEmit em = WN_EMIT_NONE,
-                          const WnSampleRow* tab = nullptr);
+                          const WnSampleRow* tab = nullptr, const uint64_t* origin = nullptr);
 // (tab, here and below: per-row controls -- row r draws with tab[r]'s controls, key and counter row in the *_rows twin of
-// the kernel; seed is unused and ctl is the union of the rows)
+// the kernel; seed is unused and ctl is the union of the rows.  origin, beside a table only: [rows] device values or null,
+// row r draws with the counter word offset - origin[r], wn_sample_clock_uniform; null = offset, the draw of before)
 // the categorical draw straight from the logits, for up to WN_SAMPLE_FUSED_MAXC classes
 int wn_sample_from_logits_supported(int C);
 int wn_launch_sample_rand_cat_logits(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
                                      float* out, hipStream_t s, WnSampleCtl ctl = WN_SAMPLE_CTL_OFF, WnEmit em = WN_EMIT_NONE,
-                                     const WnSampleRow* tab = nullptr);
+                                     const WnSampleRow* tab = nullptr, const uint64_t* origin = nullptr);
 // top-k is offered for up to this many classes (WN_SAMPLE_FUSED_MAXC, wn_sample.hip)
 int wn_sample_top_k_max_classes();
 

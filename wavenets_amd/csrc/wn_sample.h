@@ -306,6 +306,16 @@ __device__ __forceinline__ WnSampleRow wn_sample_row_uniform(const WnSampleRow* 
   r.stream = (uint64_t)u(b.z) | ((uint64_t)u(b.w) << 32);
   return r;
 }
+// The row's own clock: beside a table a *_rows kernel may take `origin`, one uint64_t per row of the
+// call, and row r then draws with the counter word offset - origin[r] (unsigned 64-bit: beyond offset the word wraps
+// modulo 2^64).  Null = every origin 0 = the counter word of before.  Wave-uniform form for the categorical kernels, read
+// as the record is read above; the mixture kernels load theirs per thread, beside tab[row].
+__device__ __forceinline__ uint64_t wn_sample_clock_uniform(const uint64_t* origin, int64_t row, uint64_t offset) {
+  if (!origin) return offset;
+  const uint2 o = *reinterpret_cast<const uint2*>(origin + row);
+  auto u = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+  return offset - ((uint64_t)u(o.x) | ((uint64_t)u(o.y) << 32));
+}
 // categorical draw from a stored probability row (wn_sample_rand_cat_kernel's two forms)
 __device__ __forceinline__ int wn_draw_cat_row_tab(const float* p, int C, int lane, const WnSampleRow& r, uint64_t offset) {
   if (r.ctl().on()) return wn_draw_cat_row(wn_cat_ctl_view(p, C, lane, r.ctl()), C, lane, (int64_t)r.stream, r.seed, offset);
@@ -325,7 +335,8 @@ __device__ __forceinline__ float wn_cat_rand_row_tab(const float* l, int C, int 
 // nothing, and a fused (w * 1 - wm) would round like (w - wm) anyway).  One instruction stream for all lanes: a mixed
 // batch costs what the uniform one costs (a per-lane branch between the two forms ran both, measured +2 us a step).
 __device__ __forceinline__ float wn_mix_rand_row_tab(const float* p, int M, int kind, const WnSampleRow* tab, int64_t row,
-                                                     uint64_t offset) {
+                                                     uint64_t offset, const uint64_t* origin = nullptr) {
   const WnSampleRow r = tab[row];
+  if (origin) offset -= origin[row];                 // (a kernel argument: uniform)
   return wn_mix_rand_row<true>(p, M, kind, (int64_t)r.stream, r.seed, offset, r.ctl());
 }

@@ -98,11 +98,12 @@ __global__ __launch_bounds__(256) void wn_sample_rand_cat_logits_kernel(const fl
 template <bool LOGITS>
 __global__ __launch_bounds__(256) void wn_sample_rand_cat_rows_kernel(const float* pred, int64_t rows, int C, float inv,
                                                                       uint64_t offset, float* out, WnEmit em,
-                                                                      const WnSampleRow* tab) {
+                                                                      const WnSampleRow* tab, const uint64_t* origin) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t row = (int64_t)blockIdx.x * 4 + w;
   if (row >= rows) return;
   const WnSampleRow r = wn_sample_row_uniform(tab, row);
+  offset = wn_sample_clock_uniform(origin, row, offset);     // the row's own clock
   if constexpr (LOGITS) {
     __shared__ float q[4][WN_SAMPLE_FUSED_MAXC];
     const float v = wn_cat_rand_row_tab(pred + row * C, C, lane, q[w], r, offset, inv);
@@ -117,15 +118,17 @@ __global__ __launch_bounds__(256) void wn_sample_rand_cat_rows_kernel(const floa
 }
 // (defined at the end of the file)
 static void wn_launch_sample_rand_rows(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t offset,
-                                       float* out, hipStream_t s, WnEmit em, const WnSampleRow* tab, bool logits);
+                                       float* out, hipStream_t s, WnEmit em, const WnSampleRow* tab, bool logits,
+                                       const uint64_t* origin);
 int wn_sample_from_logits_supported(int C) { return C <= WN_SAMPLE_FUSED_MAXC ? 1 : 0; }
 int wn_sample_top_k_max_classes() { return WN_SAMPLE_FUSED_MAXC; }
 int wn_launch_sample_rand_cat_logits(const float* logits, int64_t rows, int C, int bits, uint64_t seed, uint64_t offset,
-                                     float* out, hipStream_t s, WnSampleCtl ctl, WnEmit em, const WnSampleRow* tab) {
+                                     float* out, hipStream_t s, WnSampleCtl ctl, WnEmit em, const WnSampleRow* tab,
+                                     const uint64_t* origin) {
   if (rows <= 0) return WN_OK;
   if (C > WN_SAMPLE_FUSED_MAXC) { wn_set_error("sample from logits: %d classes > %d", C, WN_SAMPLE_FUSED_MAXC); return WN_E_UNSUPPORTED; }
   if (tab) {
-    wn_launch_sample_rand_rows(logits, rows, C, 0, bits, 0, offset, out, s, em, tab, true);
+    wn_launch_sample_rand_rows(logits, rows, C, 0, bits, 0, offset, out, s, em, tab, true, origin);
     WN_HIP_CHECK(hipGetLastError());
     return WN_OK;
   }
@@ -146,15 +149,15 @@ __global__ void wn_sample_rand_mix_kernel(const float* pred, int64_t rows, int M
 }
 template <bool EMIT>
 __global__ void wn_sample_rand_mix_rows_kernel(const float* pred, int64_t rows, int M, int kind, uint64_t offset, float* out,
-                                              WnEmit em, const WnSampleRow* tab) {
+                                              WnEmit em, const WnSampleRow* tab, const uint64_t* origin) {
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= rows) return;
-  const float vc = wn_mix_rand_row_tab(pred + row * 3 * M, M, kind, tab, row, offset);
+  const float vc = wn_mix_rand_row_tab(pred + row * 3 * M, M, kind, tab, row, offset, origin);
   out[row] = vc;
   if constexpr (EMIT) wn_emit_sample(em, row, vc);
 }
 int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t seed, uint64_t offset,
-                          float* out, hipStream_t s, WnSampleCtl ctl, WnEmit em, const WnSampleRow* tab) {
+                          float* out, hipStream_t s, WnSampleCtl ctl, WnEmit em, const WnSampleRow* tab, const uint64_t* origin) {
   if (rows <= 0) return WN_OK;
   if (M > 0 && (ctl.top_k > 0 || ctl.top_p > 0.f)) {
     wn_set_error("sample_rand: top_k and top_p apply to the categorical head only");
@@ -164,9 +167,9 @@ int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bit
     wn_set_error("sample_rand: top_k / top_p over %d classes > %d", C, WN_SAMPLE_FUSED_MAXC);
     return WN_E_UNSUPPORTED;
   }
-  if (M <= 0 && em.out) return wn_launch_sample_rand_cat_logits(pred, rows, C, bits, seed, offset, out, s, ctl, em, tab);
+  if (M <= 0 && em.out) return wn_launch_sample_rand_cat_logits(pred, rows, C, bits, seed, offset, out, s, ctl, em, tab, origin);
   if (tab) {
-    wn_launch_sample_rand_rows(pred, rows, C, M, bits, kind, offset, out, s, em, tab, false);
+    wn_launch_sample_rand_rows(pred, rows, C, M, bits, kind, offset, out, s, em, tab, false, origin);
   } else if (M <= 0) {
     const auto kernel = ctl.on() ? wn_sample_rand_cat_kernel<true> : wn_sample_rand_cat_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
@@ -181,13 +184,14 @@ int wn_launch_sample_rand(const float* pred, int64_t rows, int C, int M, int bit
 }
 
 static void wn_launch_sample_rand_rows(const float* pred, int64_t rows, int C, int M, int bits, int kind, uint64_t offset,
-                                       float* out, hipStream_t s, WnEmit em, const WnSampleRow* tab, bool logits) {
+                                       float* out, hipStream_t s, WnEmit em, const WnSampleRow* tab, bool logits,
+                                       const uint64_t* origin) {
   const float inv = 1.0f / (float)(1 << (bits - 1));
   if (M <= 0) {
     const auto kernel = logits ? wn_sample_rand_cat_rows_kernel<true> : wn_sample_rand_cat_rows_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, pred, rows, C, inv, offset, out, em, tab);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, pred, rows, C, inv, offset, out, em, tab, origin);
   } else {
     const auto kernel = em.out ? wn_sample_rand_mix_rows_kernel<true> : wn_sample_rand_mix_rows_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, pred, rows, M, kind, offset, out, em, tab);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, pred, rows, M, kind, offset, out, em, tab, origin);
   }
 }

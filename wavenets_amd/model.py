@@ -231,9 +231,13 @@ class GenerationSession:
   what a split-precision step reads).  Otherwise a chunk runs in the math mode of the calling context.
 
   start: the index of the sequence's first sample; position begins there, the first chunk is
-  wn_generate_rows_begin.  admit() puts new requests into rows of the running batch."""
+  wn_generate_rows_begin.  admit() puts new requests into rows of the running batch.
 
-  def __init__(self, model, sampling, condition, window, batch_size, use_queues, deterministic, start=0):
+  origins: per row, the index its clock counts from -- row b draws sample t from the Philox counter
+  (stream[b], t - origins[b]).  All zero unless the session was created with own_clock=True or a request admitted by admit_own_clock;
+  row_positions is position - origins[b], the number of samples row b's present clock has counted."""
+
+  def __init__(self, model, sampling, condition, window, batch_size, use_queues, deterministic, start=0, own_clock=False):
     L = _lib.lib()
     self._model, self._sampling, self._cond, self._window = model, sampling, condition, window
     # per-row controls: the device table of the session, read by every chunk (and by the exact-fp32 rerun of one)
@@ -255,6 +259,20 @@ class GenerationSession:
     self._scratch = {}                     # admit(): the scratch workspace of k rows, kept per k
     self.position = self._start
     self.exact = False
+    # the rows' clock origins: None (every origin 0, the entry points without the argument) or B uint64 on the device,
+    # read by every chunk like the table; own_clock: every row counts from `start`
+    self._origin = None
+    if own_clock:
+      self._origin = torch.full((self._B,), self._start, dtype=torch.int64, device=model._device)
+    self._origins = [self._start if own_clock else 0] * self._B
+
+  @property
+  def origins(self):
+    return list(self._origins)
+
+  @property
+  def row_positions(self):
+    return [self.position - o for o in self._origins]
 
   def generate(self, n):
     """The next (B, n, 1) samples, n >= 1.  A chunk that raises leaves position where it was."""
@@ -270,10 +288,15 @@ class GenerationSession:
       window = _lib.ptr(self._window) if begins else None
       if self._rows is not None:
         # (start = 0 runs the call it always ran)
-        entry = L.wn_generate_rows_begin if begins and first > 0 else L.wn_generate_rows_chunk
-        _lib.check(entry(m._plan, _lib.ptr(m.flat_params), window, _lib.ptr(self._cond), self._B, first, n, self._det,
-                         self._queued, _lib.ptr(self._rows), self._sampling.flags, _lib.ptr(out), _lib.ptr(self._ws),
-                         self._ws.numel(), _lib.stream_ptr()))
+        head = (m._plan, _lib.ptr(m.flat_params), window, _lib.ptr(self._cond), self._B, first, n, self._det, self._queued,
+                _lib.ptr(self._rows), self._sampling.flags)
+        tail = (_lib.ptr(out), _lib.ptr(self._ws), self._ws.numel(), _lib.stream_ptr())
+        if self._origin is not None:          # (the range-guard rerun below repeats with the same origins)
+          entry = L.wn_generate_rows_begin_origin if begins and first > 0 else L.wn_generate_rows_chunk_origin
+          _lib.check(entry(*head, _lib.ptr(self._origin), *tail))
+        else:
+          entry = L.wn_generate_rows_begin if begins and first > 0 else L.wn_generate_rows_chunk
+          _lib.check(entry(*head, *tail))
         return
       _lib.check(L.wn_generate_chunk(m._plan, _lib.ptr(m.flat_params), window,
                                      _lib.ptr(self._cond), self._B, first, n, self._det, self._queued,
@@ -321,7 +344,18 @@ class GenerationSession:
     first sample, index position - 1 of the session; from the next chunk on row slots[j] is request j.  That row, from
     the returned sample on, is bit for bit a session of B = 1 begun with start = position - 1 from the request's own
     arguments; every other row is what it is without the admission.  Queued sessions with per-row controls only, after
-    their first chunk."""
+    their first chunk.  The admitted rows draw on the session's clock; admit_own_clock gives them their own."""
+    return self._admit(slots, sample, condition, temperature, top_k, seed, top_p, stream, False)
+
+  def admit_own_clock(self, slots, sample, condition=None, temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None):
+    """admit, with the admitted rows on their own clock: they count from their own first sample --
+    origin position - 1, so the returned sample is drawn from counter (stream, 0).  Such a row is then bit for bit
+    model.generate(n, sample=prompt, use_queues=True, stream=[id], <its controls>) of the request alone, whichever slot,
+    batch and position it was admitted at.  The other rows keep their clocks.  (A method of its own: admit's parameter
+    list is what section 32 fixed.)"""
+    return self._admit(slots, sample, condition, temperature, top_k, seed, top_p, stream, True)
+
+  def _admit(self, slots, sample, condition, temperature, top_k, seed, top_p, stream, own_clock):
     m, L = self._model, _lib.lib()
     if not self._queued:
       raise RuntimeError('generation session: admit needs a session with use_queues=True (the sliding window has no '
@@ -370,12 +404,21 @@ class GenerationSession:
     scratch = self._scratch[k]
     first_out = torch.empty(k, 1, 1, dtype=torch.float32, device=m._device)
     slots_c = (C.c_int32 * k)(*slot_list)
+    # a session without an origin array gets one of zeros at its first admit_own_clock, and keeps it
+    origin = self._origin
+    if origin is None and own_clock:
+      origin = torch.zeros(self._B, dtype=torch.int64, device=m._device)
+    origin_k = None if origin is None else torch.full((k,), self.position - 1 if own_clock else 0, dtype=torch.int64,
+                                                      device=m._device)
 
     def run():
-      _lib.check(L.wn_generate_admit(m._plan, _lib.ptr(m.flat_params), _lib.ptr(sample), _lib.ptr(condition), k, slots_c,
-                                     self._B, self.position, self._det, _lib.ptr(rows_k), new.flags, _lib.ptr(first_out),
-                                     _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(scratch), scratch.numel(),
-                                     _lib.stream_ptr()))
+      head = (m._plan, _lib.ptr(m.flat_params), _lib.ptr(sample), _lib.ptr(condition), k, slots_c, self._B, self.position,
+              self._det, _lib.ptr(rows_k), new.flags)
+      tail = (_lib.ptr(first_out), _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr())
+      if origin_k is not None:              # (the range-guard rerun below repeats with the same origins)
+        _lib.check(L.wn_generate_admit_origin(*head, _lib.ptr(origin_k), *tail))
+      else:
+        _lib.check(L.wn_generate_admit(*head, *tail))
     if self.exact or L.wn_debug_value(1) == 1:
       with m.exact_fp32():
         run()
@@ -392,6 +435,11 @@ class GenerationSession:
     # the session's own records: rows slots[j] of the device table (in place: the chunks read this tensor) and of the condition
     self._sampling = table
     self._rows.copy_(table.device_table(m._device))
+    if origin is not None:
+      origin[torch.tensor(slot_list, device=m._device)] = origin_k
+      self._origin = origin
+      for b in slot_list:
+        self._origins[b] = self.position - 1 if own_clock else 0
     if condition is not None:
       if not self._admitted:
         self._cond = self._cond.clone()          # (the caller's tensor stays as it is)
@@ -400,7 +448,8 @@ class GenerationSession:
     return first_out
 
   def reset(self):
-    """Back to the start: the next chunk begins the sequence again from the window, on the same workspace."""
+    """Back to the start: the next chunk begins the sequence again from the window, on the same workspace (and with the
+    same origins)."""
     if self._admitted:
       raise RuntimeError('generation session: reset after admit is not possible (the rows the window began are gone); '
                          'start a new session')
@@ -1379,7 +1428,7 @@ class WaveNet(torch.nn.Module):
     return sampling, condition, sample, batch_size
 
   def generation_session(self, batch_size: int = 1, condition=None, sample=None, use_queues=False, deterministic=False,
-                         temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None, start=0):
+                         temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None, start=0, own_clock=False):
     """A sequence made in pieces: the arguments of generate without `length`, with the same checks (per-utterance
     controls and `stream` included: the session keeps the device table of its rows).  The chunks of
     session.generate(n), concatenated, are bit for bit generate(total, same arguments).  The
@@ -1387,14 +1436,20 @@ class WaveNet(torch.nn.Module):
     finalize_variable_values, or entering / leaving averaged_weights() its generate raises RuntimeError.
     start: an int >= 0, the index of the sequence's first sample -- the draw of sample t uses the
     Philox counter (stream, t), so a sequence begun at `start` draws what a request admitted at that position draws
-    (GenerationSession.admit).  start > 0 needs per-row controls: passing stream= is enough."""
+    (GenerationSession.admit).  start > 0 needs per-row controls: passing stream= is enough.
+    own_clock=True: every row counts from `start` -- sample t is drawn from counter (stream, t - start),
+    so the session is bit for bit the session with start=0, stochastic draws included.  Needs per-row controls too."""
     if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or start < 0:
       raise ValueError(f'start must be an int >= 0 (got {start!r})')
+    if not isinstance(own_clock, bool):
+      raise ValueError(f'own_clock must be a bool (got {own_clock!r})')
     sampling, condition, window, batch_size = self._generation_args(batch_size, condition, sample, deterministic,
                                                                     temperature, top_k, seed, top_p, stream)
     if start > 0 and not isinstance(sampling, _RowControls):
       raise ValueError('start > 0 needs per-row sampling controls: pass stream= (one Philox stream id per utterance)')
-    return GenerationSession(self, sampling, condition, window, batch_size, use_queues, deterministic, int(start))
+    if own_clock and not isinstance(sampling, _RowControls):
+      raise RuntimeError('generation session: own_clock needs per-row controls (create the session with stream=)')
+    return GenerationSession(self, sampling, condition, window, batch_size, use_queues, deterministic, int(start), own_clock)
 
   def generate_stream(self, length, chunk, **kwargs):
     """Generator over a generation_session(**kwargs): yields (B, min(chunk, rest), 1) tensors until `length` samples are
