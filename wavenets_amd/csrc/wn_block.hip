@@ -191,6 +191,8 @@ int block_backward(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, 
         const float* a1 = (k.S > 0 || g_o == g.g_o_tmp) ? g.am_gskip : nullptr;
         if (g.am_gu && a0) gm.w16(k.G16u).absmax(a0, a1, g.am_gu);
       }
+      // (no image for this shape: the exact-fp32 kernel, which still owes g_u's scale to the g_x product and the jobs)
+      if (!gm.w16_ && g.am_gu) gm.absmax(nullptr, nullptr, g.am_gu);
       rc = gm.gate_bwd(f.AG, k.D, f.Z, f.ldz).run(g.g_u, 2 * k.D, s);
     }
     if (rc) return rc;
@@ -282,6 +284,7 @@ int block_backward(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, 
       if (k.residual && g.g_xout) gm.addc(g.g_xout, k.R);
       if (k.G16x && k.depth == 1 && g.am_gu && g.am_gx) gm.w16(k.G16x).absmax(g.am_gu, nullptr, g.am_gx);
       else if (b16) gm.w16(k.G16i[0]).absmax(am_cur, nullptr, am_dst);
+      else if (g.am_gx) gm.absmax(nullptr, nullptr, g.am_gx);       // (exact-fp32 kernel: the next block's g_u product reads it)
       rc = gm.run(g.g_x, hc, s);
       if (rc) return rc;
     }

@@ -418,6 +418,23 @@ int wn_launch_dropout(const float* x, const float* g_res, float* out, int64_t n,
   return WN_OK;
 }
 
+// Running max-abs of a gradient tensor the exact-fp32 rows GEMM wrote (that kernel keeps none): what the split-precision
+// products and weight-gradient jobs behind it scale their operand by.
+__global__ void wn_absmax_kernel(const float* y, int64_t rows, int cols, int ld, float* slot) {
+  const int64_t n = rows * cols;
+  float m = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    m = fmaxf(m, fabsf(y[(i / cols) * ld + i % cols]));
+  m = wn_wave_max(m);
+  if ((threadIdx.x & 63) == 0) wn_absmax_publish(slot, m);
+}
+int wn_launch_absmax(const float* y, int64_t rows, int cols, int ld, float* slot, hipStream_t s) {
+  if (rows <= 0 || cols <= 0 || !slot) return WN_OK;
+  hipLaunchKernelGGL(wn_absmax_kernel, dim3(wn_blocks(rows * cols)), dim3(256), 0, s, y, rows, cols, ld, slot);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Global conditioning of ALL residual blocks at once (src/layers.py:116-120,203-204 with the
 // time-invariant condition of src/model.py:221-225: conv_cond(repeat(m)) is a per-utterance bias).

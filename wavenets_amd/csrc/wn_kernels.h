@@ -370,6 +370,9 @@ int wn_launch_dact_mul(const float* g, const float* y, float* out, int64_t n, in
 uint32_t wn_dropout_key(uint64_t seed, int block, uint64_t step);
 int wn_launch_dropout(const float* x, const float* g_res, float* out, int64_t n, float rate, uint32_t key,
                       float* absmax_out, hipStream_t s);
+// running max-abs of y[rows][cols] (row pitch ld) into a scale slot: for a gradient the exact-fp32 rows GEMM wrote inside a
+// split-precision chain, whose consumers scale it by that slot
+int wn_launch_absmax(const float* y, int64_t rows, int cols, int ld, float* slot, hipStream_t s);
 int wn_launch_gate(const float* u, int64_t rows, int D, float* ag, float* z, int ldz, hipStream_t s);
 // global conditioning of all blocks at once (wn_elem.hip)
 int wn_launch_cond_scatter(const float* tmp, const float* params, int64_t b_off0, int64_t b_stride, int B, int N, int D2,

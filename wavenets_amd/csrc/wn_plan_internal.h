@@ -408,7 +408,12 @@ struct Gemm {
     if (a.epi == WN_EPI_GATE_FWD) { wn_set_error("gate-forward contraction needs the split-precision kernel (alignment / shape)"); return WN_E_UNSUPPORTED; }
     for (int i = 0; i < a.nseg; ++i)
       if (!a.seg[i].frag) { wn_set_error("contraction without an fp32 weight image needs the split-precision kernel"); return WN_E_UNSUPPORTED; }
-    return wn_launch_gemm_rows(a, s);
+    const int rc = wn_launch_gemm_rows(a, s);
+    // A gradient inside a split-precision chain (32 output columns without a padded image, an operand width the images do
+    // not take): the next product and the weight-gradient jobs scale it by its max-abs slot, which the exact-fp32 kernel
+    // does not keep -- taken from the result.  (The gate-derivative epilogue writes both halves of u: 2 N columns.)
+    if (rc || !amo_ || a.absmax_any || wn_debug_get(1) == 1) return rc;
+    return wn_launch_absmax(y, (int64_t)a.B * a.T, a.epi == WN_EPI_GATE_BWD ? 2 * a.N : a.N, ldy, amo_, s);
   }
 };
 

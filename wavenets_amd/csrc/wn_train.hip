@@ -357,8 +357,10 @@ struct TrainCall {
       Gemm gm(B, T, c.cin, ceil32(c.cin));
       gm.seg(ws + L.GF[i], c.cout, c.cout, 0, fragbase + c.fragB);
       if (i > 0) gm.dact(ws + L.HA[i - 1], c.cin, p->c.activation);
-      if (c.frag16B >= 0)
-        gm.w16(fragbase + c.frag16B).absmax(am_GF(i), nullptr, i > 0 ? am_GF(i - 1) : (p->c.use_skip ? am_gskip : am_GH(p->N)));
+      // (a layer without an image -- 32 or 48 input columns, the 30 outputs of a mixture head -- runs the exact-fp32 kernel,
+      // which still owes its result's scale to the layer below and to the weight-gradient jobs)
+      if (c.frag16B >= 0) gm.w16(fragbase + c.frag16B);
+      gm.absmax(am_GF(i), nullptr, i > 0 ? am_GF(i - 1) : (p->c.use_skip ? am_gskip : am_GH(p->N)));
       rc = gm.run(dst, c.cin, s);
       if (rc) return rc;
     }
