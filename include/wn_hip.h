@@ -263,6 +263,55 @@ int wn_adam_step_ema(wn_plan* p, float* params, const float* grads, float* m, fl
  * device is touched).  The following wn_adam_step then takes clipnorm 0. */
 int wn_clip_gradients(wn_plan* p, float* grads, float clipnorm, float* scratch, void* stream);
 
+/* ---- Adam with the other Keras keywords: global_clipnorm, clipvalue, weight_decay (AdamW), amsgrad ----
+ * One guarded launch, a sibling of the kernels behind the three entry points above, which stay as they are: callers
+ * that use none of the keywords keep calling those.  fp32 on the device, in exactly these forms (t = step, 1-based):
+ *   clip    clip_mode is ONE of the WN_CLIP_* bits (or 0 = none) and `clip` its value c, finite and > 0:
+ *             WN_CLIP_NORM         per tensor, g' = g * (c / fmaxf(||g_t||, c)), as wn_adam_step;
+ *             WN_CLIP_GLOBAL_NORM  N2 = sum over the tensors of ||g_t||^2 (each accumulated in double, stored as a float,
+ *                                  the floats added in double in tensor order), N = sqrtf((float)N2),
+ *                                  g' = g * (c / fmaxf(N, c) + (N - N)): N <= c leaves g bit-identical, a non-finite N
+ *                                  makes every g' NaN (it does not pass silently);
+ *             WN_CLIP_VALUE        g' = g < -c ? -c : (g > c ? c : g); a NaN stays NaN.
+ *   decay   weight_decay wd, finite and >= 0 (0 = off): p0 = p - (p * wd) * lr ahead of the update of the same step, on
+ *           tensor i of wn_plan_tensor_info when decay_flags[i] != 0 -- decay_flags: num_tensors int32 in DEVICE memory, or
+ *           NULL = every tensor.  It uses lr, not alpha, and never enters g', m or v.
+ *   moments m = m + (g' - m) * (1 - beta1), v = v + (g' g' - v) * (1 - beta2)
+ *   amsgrad amsgrad == 1: vhat = fmaxf(vhat, v) (wn_plan_param_count floats, state of the caller's, zeros at the start)
+ *           and the denominator takes vhat; v keeps its own recursion.  amsgrad == 0: the denominator takes v and vhat is
+ *           not looked at (it may be NULL).
+ *   update  p = p0 - alpha * m / (sqrtf(v or vhat) + eps), alpha = lr sqrt(1 - beta2^t) / (1 - beta1^t) formed on the host
+ *   ema     ema != NULL: as wn_adam_step_ema on that p (t == 1: ema = p; else ema + (p - ema) * (1 - ema_momentum); then
+ *           p = ema when ema_overwrite is 1).  ema == NULL: ema_momentum and ema_overwrite must be 0.
+ *   guard   *skip_flag != 0 (skip_flag may be NULL) leaves p, m, v, vhat and ema untouched, the decay included.
+ * scratch: >= num_tensors floats (the squared norms of the two norm clips).
+ * WN_E_INVALID, checked before the device is touched and named in wn_last_error_string: a NULL plan, params, grads, m, v,
+ * options or scratch; step < 1; clip_mode with more than one bit or an unknown bit; a clip_mode with a clip that is not
+ * finite and > 0; weight_decay negative or not finite; ema_momentum outside [0, 1] or not finite, ema_overwrite not 0 / 1,
+ * either one non-zero without ema; amsgrad not 0 / 1, or 1 with a NULL vhat. */
+#define WN_CLIP_NONE 0
+#define WN_CLIP_NORM 1
+#define WN_CLIP_GLOBAL_NORM 2
+#define WN_CLIP_VALUE 4
+typedef struct wn_adam_options {
+  float lr, beta1, beta2, eps;
+  int32_t clip_mode;            /* one WN_CLIP_* */
+  float clip;                   /* its value; ignored when clip_mode is WN_CLIP_NONE */
+  float weight_decay;
+  float ema_momentum;
+  int32_t ema_overwrite;
+  int32_t amsgrad;              /* 0 / 1 */
+  const int32_t* decay_flags;   /* device memory, or NULL */
+} wn_adam_options;
+int wn_adam_step_ext(wn_plan* p, float* params, const float* grads, float* m, float* v, float* vhat, float* ema,
+                     int64_t step, const wn_adam_options* options, float* scratch, const float* skip_flag, void* stream);
+/* The clips of wn_adam_step_ext alone and in place, for a replica's own gradient ahead of the data-parallel all-reduce
+ * (Adam(clip_before_reduce=True)); the following step then takes WN_CLIP_NONE.  clip_mode is exactly one WN_CLIP_* bit,
+ * clip finite and > 0 (WN_E_INVALID otherwise, before the device is touched).  WN_CLIP_NORM is wn_clip_gradients.  The
+ * global form leaves a gradient inside the bound bit-identical, the value form writes only what it clamps; nothing past
+ * wn_plan_param_count floats is read or written.  scratch: >= num_tensors floats. */
+int wn_clip_gradients_ext(wn_plan* p, float* grads, int32_t clip_mode, float clip, float* scratch, void* stream);
+
 /* ---- forward range guard of the split-precision mode ----
  * The default kernels evaluate fp32 products from fp16 hi|lo operand splits; an activation beyond the fp16 range
  * (65504) would turn into inf/NaN.  Every forward pass therefore keeps the running max-abs of the tensors that feed

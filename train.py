@@ -40,6 +40,10 @@ config = {                       # defaults of the reference, train.py:22-50
     'clip_before_reduce': False,
     # Adam's exponential moving average of the weights (Keras keywords): previews and averaged.weights.h5 use the average
     'use_ema': False, 'ema_momentum': 0.99, 'ema_overwrite_frequency': None,
+    # Adam's other Keras keywords.  The reference clips every tensor to norm 1.0 (clipnorm); global_clipnorm or clipvalue
+    # replaces that clip (only one of the three can be set).  exclude_from_weight_decay: patterns searched in the
+    # variable names, e.g. ['bias']
+    'global_clipnorm': None, 'clipvalue': None, 'weight_decay': None, 'amsgrad': False, 'exclude_from_weight_decay': None,
     # hold the last n utterances' frames out of training and report val_loss (test_step) after every epoch; the monitored
     # quantity of checkpointing, plateau and early stop stays loss, as in the reference
     'validation_utterances': 0,
@@ -166,9 +170,17 @@ def main():
                   device=dev)
   if conditioned:                                                  # Keras builds on the first call (train.py:232-235):
     model.build([(per_rank, L, 1), (per_rank, cond.shape[1])])    # the condition width fixes the mapping net's shapes
-  opt = Adam(learning_rate=config['lr'], clipnorm=1.0,           # train.py:225-226
+  clipnorm = 1.0                                                  # train.py:225-226
+  if config['global_clipnorm'] is not None or config['clipvalue'] is not None:
+    clipnorm = None
+    print('global_clipnorm / clipvalue is set: the default clipnorm 1.0 is dropped') if rank == 0 else None
+  opt = Adam(learning_rate=config['lr'], clipnorm=clipnorm,
              clip_before_reduce=config['clip_before_reduce'], use_ema=config['use_ema'],
-             ema_momentum=config['ema_momentum'], ema_overwrite_frequency=config['ema_overwrite_frequency'])
+             ema_momentum=config['ema_momentum'], ema_overwrite_frequency=config['ema_overwrite_frequency'],
+             global_clipnorm=config['global_clipnorm'], clipvalue=config['clipvalue'],
+             weight_decay=config['weight_decay'], amsgrad=config['amsgrad'])
+  if config['exclude_from_weight_decay']:
+    opt.exclude_from_weight_decay(var_names=list(config['exclude_from_weight_decay']))
   averaged = model.averaged_weights if config['use_ema'] else contextlib.nullcontext
   model.compile(optimizer=opt, metrics=[MeanSquaredError()])          # train.py:225-228
   print('Receptive field') if rank == 0 else None

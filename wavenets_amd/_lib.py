@@ -51,6 +51,16 @@ class WnSamplingRow(C.Structure):
 WN_SAMPLING_ROWS_ON, WN_SAMPLING_ROWS_TOP_P = 1, 2
 
 
+class WnAdamOptions(C.Structure):
+  """struct wn_adam_options (include/wn_hip.h): what wn_adam_step_ext takes beyond the buffers and the step."""
+  _fields_ = [('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
+              ('clip_mode', C.c_int32), ('clip', C.c_float), ('weight_decay', C.c_float), ('ema_momentum', C.c_float),
+              ('ema_overwrite', C.c_int32), ('amsgrad', C.c_int32), ('decay_flags', C.c_void_p)]
+
+
+WN_CLIP_NONE, WN_CLIP_NORM, WN_CLIP_GLOBAL_NORM, WN_CLIP_VALUE = 0, 1, 2, 4      # bits of wn_adam_options.clip_mode
+
+
 class WnLayerDesc(C.Structure):
   """struct wn_layer_desc == WaveNetLayer constructor keywords, src/layers.py:10-20."""
   _fields_ = [
@@ -117,6 +127,8 @@ _SIGS = {
     'wn_adam_step_ema': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_float, C.c_int32, _P, _P, _P]),
     'wn_clip_gradients': (C.c_int, [_P, _P, C.c_float, _P, _P]),
+    'wn_adam_step_ext': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(WnAdamOptions), _P, _P, _P]),
+    'wn_clip_gradients_ext': (C.c_int, [_P, _P, C.c_int32, C.c_float, _P, _P]),
     'wn_plan_range_slot': (C.c_int64, [_P, C.c_int32, C.c_int32, C.c_int32]),
     'wn_range_limit': (C.c_float, []),
     'wn_generate': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _P,

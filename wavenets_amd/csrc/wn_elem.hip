@@ -305,6 +305,114 @@ int wn_launch_adam_ema(float* p, const float* g, float* m, float* v, float* a, c
   return WN_OK;
 }
 
+// Adam with the other Keras keywords -- global_clipnorm, clipvalue, weight_decay, amsgrad -- as further streams of the
+// same launch: a third sibling, picked by the host only when one of them is on, so the two kernels above run unchanged
+// for everybody else.  Clip mode, clip value, decay and the decay table are uniform per launch; EMA and AMSGRAD are
+// template arguments since each adds a stream (a: 2 floats per parameter, vhat: 2 more).
+//   global norm: norms2 holds the per-tensor sums of wn_sumsq_kernel; every workgroup adds the n floats itself, in double
+//     and in tensor order (uniform addresses: the same bits everywhere, no launch of its own), N = sqrtf((float)sum),
+//     scale = c / fmaxf(N, c) + (N - N): the last term is NaN for a non-finite norm and poisons the step as Keras does.
+//   value: g' = g < -c ? -c : (g > c ? c : g); both comparisons are false for a NaN, which therefore stays.
+//   decay: p0 = p - (p * wd) * lr on the tensors whose flag is set (no table: all), ahead of the update, under the
+//     same skip flag; it never enters g, m or v.
+//   amsgrad: vhat = fmaxf(vhat, v) feeds the denominator; v keeps its own recursion.
+// m, v, p and a in the expressions of the two kernels above.
+__device__ __forceinline__ float wn_global_clip_scale(const float* norms2, int n, float c) {
+  double n2 = 0.0;
+  for (int t = 0; t < n; ++t) n2 += (double)norms2[t];
+  const float N = sqrtf((float)n2);
+  return c / fmaxf(N, c) + (N - N);
+}
+
+template <bool EMA, bool AMSGRAD>
+__global__ void wn_adam_ext_kernel(float* p, const float* g, float* m, float* v, float* vhat, float* a,
+                                   const WnTensorDesc* table, int n, const float* norms2, int clip_mode, float clip,
+                                   float lr, float wd, const int32_t* decay_flags, float alpha, float beta1, float beta2,
+                                   float eps, float momentum, int first, int overwrite, const float* skip_flag) {
+  if (skip_flag && *skip_flag != 0.f) return;     // range guard tripped: nothing moves, the decay included (uniform)
+  const WnTensorDesc d = table[blockIdx.y];
+  float scale = 1.0f;
+  if (clip_mode == WN_CLIP_NORM) {
+    const float nrm = sqrtf(norms2[blockIdx.y]);
+    scale = clip / fmaxf(nrm, clip);     // tf.clip_by_norm
+  } else if (clip_mode == WN_CLIP_GLOBAL_NORM) {
+    scale = wn_global_clip_scale(norms2, n, clip);
+  }
+  const bool by_value = clip_mode == WN_CLIP_VALUE;
+  const bool decays = wd > 0.f && (!decay_flags || decay_flags[blockIdx.y] != 0);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.len;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = d.off + i;
+    const float gr = g[k];
+    const float gi = by_value ? (gr < -clip ? -clip : (gr > clip ? clip : gr)) : gr * scale;
+    const float mi = m[k] + (gi - m[k]) * (1.0f - beta1);
+    const float vi = v[k] + (gi * gi - v[k]) * (1.0f - beta2);
+    m[k] = mi;
+    v[k] = vi;
+    float den = vi;
+    if (AMSGRAD) {
+      den = fmaxf(vhat[k], vi);
+      vhat[k] = den;
+    }
+    const float p0 = decays ? p[k] - (p[k] * wd) * lr : p[k];
+    const float pi = p0 - alpha * mi / (sqrtf(den) + eps);
+    if (EMA) {
+      const float ai = first ? pi : a[k] + (pi - a[k]) * (1.0f - momentum);
+      a[k] = ai;
+      p[k] = overwrite ? ai : pi;
+    } else {
+      p[k] = pi;
+    }
+  }
+}
+int wn_launch_adam_ext(float* p, const float* g, float* m, float* v, float* vhat, float* a, const WnTensorDesc* d_table,
+                       int n, const float* norms2, int clip_mode, float clip, float lr, float wd, const int32_t* decay_flags,
+                       float alpha, float beta1, float beta2, float eps, float momentum, int first, int overwrite,
+                       const float* skip_flag, hipStream_t s) {
+  if (n <= 0) return WN_OK;
+  auto k = a ? (vhat ? wn_adam_ext_kernel<true, true> : wn_adam_ext_kernel<true, false>)
+             : (vhat ? wn_adam_ext_kernel<false, true> : wn_adam_ext_kernel<false, false>);
+  hipLaunchKernelGGL(k, dim3(32, n), dim3(256), 0, s, p, g, m, v, vhat, a, d_table, n, norms2, clip_mode, clip, lr, wd,
+                     decay_flags, alpha, beta1, beta2, eps, momentum, first, overwrite, skip_flag);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
+// The two new clips ahead of the data-parallel all-reduce (Adam(clip_before_reduce=True)), in place on the replica's own
+// gradient.  Scalar accesses over the tensors of the table, as the Adam kernels above: every access lies inside
+// [off, off + len) of a tensor, so nothing behind the last gradient (the step's scalars) is read or written.  The global
+// form runs behind wn_sumsq_kernel and writes nothing when the gradient is inside the bound (scale exactly 1.0f); the
+// value form writes only the elements it clamps.
+__global__ void wn_scale_global_kernel(float* g, const WnTensorDesc* table, int n, const float* norms2, float clip) {
+  const float scale = wn_global_clip_scale(norms2, n, clip);
+  if (scale == 1.0f) return;       // uniform: the whole gradient stays bit-identical
+  const WnTensorDesc d = table[blockIdx.y];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.len;
+       i += (int64_t)gridDim.x * blockDim.x)
+    g[d.off + i] *= scale;
+}
+__global__ void wn_clip_value_kernel(float* g, const WnTensorDesc* table, float clip) {
+  const WnTensorDesc d = table[blockIdx.y];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.len;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float gr = g[d.off + i];
+    if (gr < -clip) g[d.off + i] = -clip;
+    else if (gr > clip) g[d.off + i] = clip;
+  }
+}
+int wn_launch_scale_global(float* g, const WnTensorDesc* d_table, int n, const float* norms2, float clip, hipStream_t s) {
+  if (n <= 0) return WN_OK;
+  hipLaunchKernelGGL(wn_scale_global_kernel, dim3(32, n), dim3(256), 0, s, g, d_table, n, norms2, clip);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+int wn_launch_clip_value(float* g, const WnTensorDesc* d_table, int n, float clip, hipStream_t s) {
+  if (n <= 0) return WN_OK;
+  hipLaunchKernelGGL(wn_clip_value_kernel, dim3(32, n), dim3(256), 0, s, g, d_table, clip);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // gate of the composed (unfused) block path: u (rows, 2D) -> a = tanh(u[:, :D]), g = sigmoid(u[:, D:]),
 // z = a * g   (src/layers.py:208-210)

@@ -478,3 +478,14 @@ int wn_launch_adam(float* p, const float* g, float* m, float* v, const WnTensorD
 int wn_launch_adam_ema(float* p, const float* g, float* m, float* v, float* a, const WnTensorDesc* d_table, int n,
                        const float* norms2, float clipnorm, float alpha, float beta1, float beta2,
                        float eps, float momentum, int first, int overwrite, const float* skip_flag, hipStream_t s);
+// the step with the other Keras keywords: clip_mode one WN_CLIP_* with its value clip (the two norm modes read norms2, the
+// global one all n of them), decay p -= (p * wd) * lr where decay_flags[t] != 0 (null: everywhere), vhat non-null =
+// amsgrad, a non-null = the moving average of wn_launch_adam_ema
+int wn_launch_adam_ext(float* p, const float* g, float* m, float* v, float* vhat, float* a, const WnTensorDesc* d_table,
+                       int n, const float* norms2, int clip_mode, float clip, float lr, float wd, const int32_t* decay_flags,
+                       float alpha, float beta1, float beta2, float eps, float momentum, int first, int overwrite,
+                       const float* skip_flag, hipStream_t s);
+// in place, inside the tensors of the table only: g *= c / max(N, c) + (N - N) from the n sums of wn_launch_sumsq (no
+// write when the factor is 1.0f); g clamped to [-c, c], NaN kept (only clamped elements are written)
+int wn_launch_scale_global(float* g, const WnTensorDesc* d_table, int n, const float* norms2, float clip, hipStream_t s);
+int wn_launch_clip_value(float* g, const WnTensorDesc* d_table, int n, float clip, hipStream_t s);

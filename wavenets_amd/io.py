@@ -141,6 +141,8 @@ def save_weights(model, path: str, optimizer=None) -> None:
     arrays['adam_iterations'] = np.int64(optimizer.iterations)
     if getattr(optimizer, 'ema', None) is not None:          # Adam(use_ema=True): the weights' moving average
       arrays['adam_ema'] = optimizer.ema.detach().cpu().numpy()
+    if getattr(optimizer, 'vhat', None) is not None:         # Adam(amsgrad=True): the running maximum of v
+      arrays['adam_vhat'] = optimizer.vhat.detach().cpu().numpy()
   if getattr(model, 'dropout', 0) > 0:
     arrays['drop_step'] = np.int64(getattr(model, '_drop_step', 0))
   # write beside the target and rename: a kill mid-write must not leave a truncated file that sorts last and
@@ -171,6 +173,9 @@ def load_weights(model, path: str, optimizer=None) -> None:
       optimizer.m.copy_(torch.from_numpy(d['adam_m']).to(optimizer.m.device))
       optimizer.v.copy_(torch.from_numpy(d['adam_v']).to(optimizer.v.device))
       optimizer.iterations = int(d['adam_iterations'])
+      if getattr(optimizer, 'amsgrad', False):   # a checkpoint without the maximum starts from vhat = v; without amsgrad
+        src = d['adam_vhat'] if 'adam_vhat' in d else d['adam_v']                         # a stored one is ignored
+        optimizer.vhat.copy_(torch.from_numpy(src).to(optimizer.vhat.device))
     if optimizer is not None and getattr(optimizer, 'use_ema', False):
       optimizer.build(model)
       if 'adam_ema' in d:

@@ -14,10 +14,22 @@ average of the weights in ``ema``, written by the same launch as the update: aft
 step ``t``, ``ema = p`` at ``t == 1`` and ``ema = ema + (p - ema) * (1 - ema_momentum)`` afterwards; every
 ``ema_overwrite_frequency``-th step then sets ``p = ema``.  The average is state: ``.weights.npz`` checkpoints carry it
 (``adam_ema``).  ``WaveNet.averaged_weights()`` runs the model's passes on it.
+
+The other Keras keywords ride in a sibling of the same launch (``wn_adam_step_ext``), picked only when one of them is on:
+
+* ``global_clipnorm=c``: one factor ``c / max(N, c)`` for every tensor, ``N`` the norm of the whole gradient; a non-finite
+  norm makes every clipped gradient NaN (Keras's poisoning).  ``clipvalue=c``: elementwise clamp to ``[-c, c]``, NaN kept.
+  At most one of ``clipnorm``, ``global_clipnorm`` and ``clipvalue`` may be set.  With ``clip_before_reduce`` both are
+  applied to the replica's own gradient ahead of the all-reduce (``clip_local_gradients``), as ``clipnorm`` is.
+* ``weight_decay=wd`` (AdamW): ``p = p - (p * wd) * lr`` ahead of the Adam update of the same step, on every tensor not
+  named to ``exclude_from_weight_decay`` (before ``build``, as in Keras).  It never enters the gradient or the moments.
+* ``amsgrad=True``: ``vhat = max(vhat, v)`` is one more state stream (``adam_vhat`` in checkpoints) and the denominator.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
+import re
 
 import torch
 
@@ -27,7 +39,8 @@ from . import _lib
 class Adam:
   def __init__(self, learning_rate: float = 0.001, beta_1: float = 0.9, beta_2: float = 0.999,
                epsilon: float = 1e-7, clipnorm=None, clip_before_reduce: bool = False,
-               use_ema: bool = False, ema_momentum: float = 0.99, ema_overwrite_frequency=None):
+               use_ema: bool = False, ema_momentum: float = 0.99, ema_overwrite_frequency=None,
+               global_clipnorm=None, clipvalue=None, weight_decay=None, amsgrad: bool = False):
     if not isinstance(clip_before_reduce, bool):
       raise ValueError(f'clip_before_reduce must be a bool, got {clip_before_reduce!r}')
     if not isinstance(use_ema, bool):
@@ -39,13 +52,63 @@ class Adam:
       f = ema_overwrite_frequency
       if f is not None and (isinstance(f, bool) or not isinstance(f, int) or f < 1):
         raise ValueError(f'ema_overwrite_frequency must be None or an int >= 1, got {f!r}')
+    if sum(c is not None for c in (clipnorm, global_clipnorm, clipvalue)) > 1:
+      raise ValueError('Only one of `clipnorm`, `clipvalue` and `global_clipnorm` can be set. Received: '
+                       f'clipnorm={clipnorm!r}, clipvalue={clipvalue!r}, global_clipnorm={global_clipnorm!r}')
+    for name, c in (('global_clipnorm', global_clipnorm), ('clipvalue', clipvalue)):
+      if c is not None and (isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or not c > 0):
+        raise ValueError(f'{name} must be None or a finite number > 0, got {c!r}')
+    wd = weight_decay
+    if wd is not None and (isinstance(wd, bool) or not isinstance(wd, (int, float)) or not math.isfinite(wd) or wd < 0):
+      raise ValueError(f'weight_decay must be None or a finite number >= 0, got {wd!r}')
+    if not isinstance(amsgrad, bool):
+      raise ValueError(f'amsgrad must be a bool, got {amsgrad!r}')
     self.learning_rate = float(learning_rate)
     self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
     self.clipnorm = clipnorm
     self.clip_before_reduce = clip_before_reduce
     self.use_ema, self.ema_momentum, self.ema_overwrite_frequency = use_ema, ema_momentum, ema_overwrite_frequency
+    self.global_clipnorm = None if global_clipnorm is None else float(global_clipnorm)
+    self.clipvalue = None if clipvalue is None else float(clipvalue)
+    self.weight_decay = None if weight_decay is None else float(weight_decay)
+    self.amsgrad = amsgrad
+    self._exclude_vars, self._exclude_names = [], []
     self.iterations = 0
-    self.m = self.v = self.ema = self._scratch = None
+    self.m = self.v = self.vhat = self.ema = self._scratch = self._decay_flags = None
+    self.ext_steps = 0                               # steps that took wn_adam_step_ext (the default path never counts)
+
+  def exclude_from_weight_decay(self, var_list=None, var_names=None):
+    """Keras's method: tensors that ``weight_decay`` leaves alone.  ``var_list``: tensors of ``model.trainable_variables``
+    (matched by storage and offset); ``var_names``: patterns, ``re.search``ed in ``model.variable_names``.  Before ``build``
+    only; calls add up."""
+    if self.m is not None:
+      raise ValueError('This optimizer has already been built: `exclude_from_weight_decay()` can only be called before '
+                       'the optimizer is built.')
+    for t in var_list or []:
+      if not isinstance(t, torch.Tensor):
+        raise ValueError(f'exclude_from_weight_decay: var_list holds {type(t).__name__}, not a tensor of the model')
+      self._exclude_vars.append(t)
+    for pat in var_names or []:
+      if not isinstance(pat, str):
+        raise ValueError(f'exclude_from_weight_decay: var_names holds {pat!r}, not a string')
+      re.compile(pat)
+      self._exclude_names.append(pat)
+
+  def decays(self, model):
+    """Per tensor of ``model.variable_names``: does ``weight_decay`` touch it?  (All False without a weight decay.)"""
+    if not self.weight_decay:
+      return [False] * len(model.variable_names)
+    excluded = [any(re.search(pat, name) for pat in self._exclude_names) for name in model.variable_names]
+    if self._exclude_vars:
+      params = model.trainable_variables
+      for t in self._exclude_vars:
+        hit = [i for i, q in enumerate(params) if q is t or (
+            q.untyped_storage().data_ptr() == t.untyped_storage().data_ptr() and q.storage_offset() == t.storage_offset()
+            and q.numel() == t.numel())]
+        if not hit:
+          raise ValueError('exclude_from_weight_decay: a tensor of var_list is not a trainable variable of this model')
+        excluded[hit[0]] = True
+    return [not e for e in excluded]
 
   def build(self, model):
     """Allocate the moment buffers (src/model.py:211 optimizer.build)."""
@@ -54,7 +117,12 @@ class Adam:
       self.v = torch.zeros_like(model.flat_params.data)
       self._scratch = torch.zeros(len(model.variable_names) + 8, dtype=torch.float32,
                                   device=model.flat_params.device)
-      self.ema = None
+      self.ema = self.vhat = self._decay_flags = None
+    if self.amsgrad and self.vhat is None:
+      self.vhat = torch.zeros_like(model.flat_params.data)
+    if self.weight_decay and self._decay_flags is None and (self._exclude_vars or self._exclude_names):
+      # the per-tensor on/off table of the decay, beside the scratch (no table: every tensor decays)
+      self._decay_flags = torch.tensor([int(d) for d in self.decays(model)], dtype=torch.int32).to(model.flat_params.device)
     if self.use_ema and self.ema is None:
       # a copy of the current weights: an optimizer that starts averaging at t > 1 (a resume from a checkpoint without
       # an average) averages from the loaded weights
@@ -62,12 +130,42 @@ class Adam:
 
   def clip_local_gradients(self, model):
     """``clip_before_reduce``: clip this replica's ``model.flat_grads`` per tensor, in place, ahead of the all-reduce.
-    Nothing happens without the flag or without a clipnorm."""
-    if not (self.clip_before_reduce and self.clipnorm):
+    ``global_clipnorm`` and ``clipvalue`` likewise (the sum of squares, then one factor for all tensors; an elementwise
+    clamp).  Nothing happens without the flag or without a clip."""
+    if not self.clip_before_reduce:
+      return
+    if self.global_clipnorm or self.clipvalue:
+      self.build(model)
+      mode, c = (_lib.WN_CLIP_GLOBAL_NORM, self.global_clipnorm) if self.global_clipnorm else (_lib.WN_CLIP_VALUE, self.clipvalue)
+      _lib.check(_lib.lib().wn_clip_gradients_ext(model._plan, _lib.ptr(model.flat_grads), mode, c, _lib.ptr(self._scratch),
+                                                  _lib.stream_ptr()))
+      return
+    if not self.clipnorm:
       return
     self.build(model)
     _lib.check(_lib.lib().wn_clip_gradients(model._plan, _lib.ptr(model.flat_grads), float(self.clipnorm),
                                             _lib.ptr(self._scratch), _lib.stream_ptr()))
+
+  def _extended(self):
+    """Is a keyword on that only wn_adam_step_ext serves?  (weight_decay 0.0 is off.)"""
+    return bool(self.global_clipnorm or self.clipvalue or self.weight_decay or self.amsgrad)
+
+  def _options(self):
+    o = _lib.WnAdamOptions()
+    o.lr, o.beta1, o.beta2, o.eps = self.learning_rate, self.beta_1, self.beta_2, self.epsilon
+    if not self.clip_before_reduce:                  # (clip_local_gradients has clipped already: no second clip)
+      for mode, c in ((_lib.WN_CLIP_NORM, self.clipnorm), (_lib.WN_CLIP_GLOBAL_NORM, self.global_clipnorm),
+                      (_lib.WN_CLIP_VALUE, self.clipvalue)):
+        if c:
+          o.clip_mode, o.clip = mode, float(c)
+    o.weight_decay = self.weight_decay or 0.0
+    o.amsgrad = int(self.amsgrad)
+    o.decay_flags = None if self._decay_flags is None else self._decay_flags.data_ptr()
+    if self.use_ema:
+      f = self.ema_overwrite_frequency
+      o.ema_momentum = float(self.ema_momentum)
+      o.ema_overwrite = 1 if f is not None and self.iterations % f == 0 else 0
+    return o
 
   def apply_gradients(self, model, skip_flag=None):
     """One update of model.flat_params from model.flat_grads (src/model.py:336).  ``skip_flag``: a device float;
@@ -76,6 +174,14 @@ class Adam:
     self.build(model)
     self.iterations += 1
     model._train_gen = getattr(model, '_train_gen', 0) + 1      # the weights move: a differentiable() graph of the old ones is void
+    if self._extended():
+      self.ext_steps += 1
+      o = self._options()
+      _lib.check(_lib.lib().wn_adam_step_ext(
+          model._plan, _lib.ptr(model.flat_params), _lib.ptr(model.flat_grads), _lib.ptr(self.m), _lib.ptr(self.v),
+          _lib.ptr(self.vhat if self.amsgrad else None), _lib.ptr(self.ema if self.use_ema else None), self.iterations,
+          C.byref(o), _lib.ptr(self._scratch), _lib.ptr(skip_flag), _lib.stream_ptr()))
+      return
     if self.use_ema:
       f = self.ema_overwrite_frequency
       _lib.check(_lib.lib().wn_adam_step_ema(
