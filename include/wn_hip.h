@@ -518,6 +518,17 @@ int wn_generate_admit_origin(wn_plan* p, const float* params, const float* windo
                              const int32_t* slots, int32_t B, int64_t position, int32_t deterministic,
                              const wn_sampling_row* rows_k, int32_t rows_flags_k, const uint64_t* origin_k, float* first_out,
                              float* workspace, int64_t ws_floats, float* scratch, int64_t scratch_floats, void* stream);
+/* ---- a new condition for a running queued sequence ----
+ * cond (B, cond_inputs).  Runs the conditioning phase again (mapping stack, every block's conv_cond) into the bias table of
+ * the workspace, where the priming pass of the sequence wrote it: the table is state the steps read, not a per-step input.
+ * The steps of the following chunks use it; nothing else of the sequence changes, and the step kernels are what they were.
+ * A locally conditioned model's frame schedule is this call at every frame boundary, between two chunks.
+ * Queued sequences only.  The workspace must be the one the calling state primed last, at the same B (an admission's
+ * scratch call at another B moves that mark: call this before admitting, or begin again).
+ * WN_E_INVALID, before the device is touched, the message naming the cause: a null plan / params / cond / workspace; B < 1;
+ * queued == 0; a plan without conditioning; condition frames armed; a workspace too small; a workspace not primed. */
+int wn_generate_set_condition(wn_plan* p, const float* params, const float* cond, int32_t B, int32_t queued,
+                              float* workspace, int64_t ws_floats, void* stream);
 int64_t wn_generate_workspace_floats(const wn_plan* p, int32_t B, int32_t queued);
 /* The one contiguous part of the generation workspace that steps write and a continuation reads, as a float offset and a
  * float count.  queued: from the raw-sample slots to the end of the layout (rings, inner rings, per-step rows, partial
@@ -626,6 +637,29 @@ int wn_sum_squared_error(const float* a, const float* b, int64_t n, float scale,
  *   The armed step sample is drawn for every row as without weights; the weights do not enter it.
  * WN_E_INVALID: a null plan; w != NULL with rows < 1. */
 int wn_plan_arm_row_weights(wn_plan* plan, const float* w, int64_t rows);
+/* ---- local conditioning: a condition frame per `hop` inputs (WaveNet(conditioning='local')) ----
+ * The reference maps the condition (B, F, Cin) with 1x1 convolutions and upsamples the result to the input rate by
+ * repetition (src/model.py:216-220), so inside a frame conv_cond(condition) is constant: local conditioning is the bias table
+ * of global conditioning with one row per (utterance, frame) instead of one per utterance, and the 1x1 mapping stack is the
+ * Dense stack over the B * F rows (the flat element order of a (1, cin, w) and a (cin, w) kernel is the same; wn_config and
+ * the tensor table do not change).
+ * wn_plan_set_cond_frames arms the calling thread's execution state, in the manner of wn_plan_set_dropout: frames = 0 or 1
+ * means the calls as they are without it, bit for bit.  With frames = F > 1, in wn_forward, wn_forward_training,
+ * wn_train_fwd_bwd, wn_eval_loss, wn_score and wn_vjp:
+ *   cond is (B, F, cond_inputs) and g_cond has that shape; with T network inputs hop = T / F, and the mapped condition of
+ *   frame f acts on the inputs t in [f * hop, (f + 1) * hop);
+ *   wn_plan_workspace_floats answers for the armed F (the conditioning's regions hold B * F rows), and what an execution
+ *   state caches per (B, T) is keyed by F as well; wn_debug_ws_region likewise answers for the F armed when it is asked
+ *   (the regions carved behind the conditioning's move with F: ask with the frames of the pass armed);
+ *   T % F != 0 is WN_E_INVALID (the reference's add would fail), and so is hop % 32 != 0: every kernel that adds the bias
+ *   walks 32-row time tiles that start at multiples of 32 inside an utterance and reads ONE bias row per tile, so a frame
+ *   must hold whole tiles.  This is a limit of this implementation.  Both messages name T, F (and hop), and both are
+ *   raised before the device is touched.
+ *   The gradient of the bias table is the per-frame sum of every block's dL/du, one launch for all blocks with a fixed
+ *   summation order (wn_cond_frames.hip); from there the conditioning backward is that of global conditioning over B * F rows.
+ * The generation entry points take one condition row per utterance and return WN_E_INVALID while F > 1 is armed.
+ * WN_E_INVALID: a null plan, frames < 0, frames > 1 on a plan without conditioning. */
+int wn_plan_set_cond_frames(wn_plan* plan, int32_t frames);
 /* Keras's weighted MeanSquaredError of one step as a device scalar: out[0] = scale * sum_i w[i] (a[i] - b[i])^2 / sum_i w[i],
  * and 0 when sum_i w[i] == 0; numerator and denominator in one pass, double accumulation in two stages as
  * wn_sum_squared_error.  scale = 1 / replicas makes the SUM over the replicas the average of their ratios: the weighted

@@ -31,7 +31,7 @@ config = {                       # defaults of the reference, train.py:22-50
     'final_layers_channels': [128, 256], 'l2_reg_factor': 0,
     # additions of this driver
     'steps_per_epoch': 0, 'synthetic_utterances': 256, 'sample_rate': 16000, 'results_dir': './results',
-    'preview_length': 0, 'condition_classes': 2, 'labels': None,
+    'preview_length': 0, 'condition_classes': 2, 'labels': None, 'condition_hop': None,
     'preview_temperature': 1.0, 'preview_top_k': 0, 'preview_seed': None,   # WaveNet.generate's sampling controls
     'top_p': 1.0,                  # ... and its nucleus control (categorical head only; 1.0 = off)
     'checkpoint_format': 'npz',    # 'h5': Keras .weights.h5 exchange files (weights only, as the reference writes them)
@@ -107,8 +107,9 @@ def main():
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
     dist.init_process_group('nccl', device_id=dev)
   conditioned = config['conditioning'] is not None
-  if conditioned and config['conditioning'] != 'global':
-    raise SystemExit("only conditioning: global is supported (local conditioning is broken in the reference, src/model.py:136-137)")
+  local = config['conditioning'] == 'local'
+  if conditioned and config['conditioning'] not in ('global', 'local'):
+    raise SystemExit("conditioning must be global, local or null")
 
   # ---- data: waveforms -> frames of recording_length + 1 (src/utils.py:22-85) ----
   L = int(config['recording_length'])
@@ -122,7 +123,20 @@ def main():
   cond = None
   pad_end = bool(config['pad_end'])
   weights = None                                                    # pad_end: sample_weight of every frame, (n, L)
-  if conditioned:
+  if local:
+    # conditioning: local.  condition_hop inputs per condition frame; the synthetic condition is the
+    # mean absolute amplitude of the uncompanded waveform over each frame, in the reference's (n, F) form
+    hop = int(config['condition_hop'] or 0)
+    if hop < 1 or L % hop != 0 or (L // hop > 1 and hop % 32 != 0):
+      raise SystemExit('conditioning: local needs condition_hop, a divisor of recording_length and a multiple of 32')
+    parts = [data.preprocess_waveform(w, L, config['apply_mulaw']) for w in raw]
+    frames = torch.cat(parts, dim=0)
+    per_utterance = [p.shape[0] for p in parts]
+    plain = ops.inverse_mu_law(frames) if config['apply_mulaw'] else frames
+    cond = plain.reshape(frames.shape[0], -1)[:, :L].abs().reshape(frames.shape[0], L // hop, hop).mean(dim=2)
+    if pad_end:
+      raise SystemExit('pad_end is not offered with conditioning: local')
+  elif conditioned:
     ncls = int(config['condition_classes'])
     labels = np.load(config['labels']).astype(np.int64) if config['labels'] else np.arange(raw.shape[0]) % ncls
     if len(labels) != raw.shape[0]:
@@ -169,7 +183,8 @@ def main():
                   final_layers_channels=config['final_layers_channels'], l2_reg_factor=config['l2_reg_factor'],
                   device=dev)
   if conditioned:                                                  # Keras builds on the first call (train.py:232-235):
-    model.build([(per_rank, L, 1), (per_rank, cond.shape[1])])    # the condition width fixes the mapping net's shapes
+    # the condition width fixes the mapping net's shapes (local: (n, F) is one channel)
+    model.build([(per_rank, L, 1), (per_rank, cond.shape[1], 1) if local else (per_rank, cond.shape[1])])
   clipnorm = 1.0                                                  # train.py:225-226
   if config['global_clipnorm'] is not None or config['clipvalue'] is not None:
     clipnorm = None
@@ -249,8 +264,13 @@ def main():
   if rank == 0:
     tic = time.time()
     nprev = min(config['batch_size'], 8)
+    gen_cond, gen_kw = (cond[:nprev] if conditioned else None), {}
+    if local:                                # the frames of the first utterances, repeated to cover the preview, and the hop
+      hop = int(config['condition_hop'])
+      gen_cond = gen_cond.repeat(1, -(-preview // (gen_cond.shape[1] * hop)))
+      gen_kw = {'hop': hop}
     with averaged():
-      samples = model.generate(preview, batch_size=nprev, condition=cond[:nprev] if conditioned else None,
+      samples = model.generate(preview, batch_size=nprev, condition=gen_cond, **gen_kw,
                                use_queues=config['layers_per_block'] == 1,
                                temperature=float(config['preview_temperature']), top_k=int(config['preview_top_k']),
                                seed=None if config['preview_seed'] is None else int(config['preview_seed']),

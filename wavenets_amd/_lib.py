@@ -174,6 +174,8 @@ _SIGS = {
     'wn_plan_set_train_phases': (C.c_int, [_P, C.c_int32]),
     'wn_sum_squared_error': (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P, _P]),
     'wn_plan_arm_row_weights': (C.c_int, [_P, _P, C.c_int64]),
+    'wn_plan_set_cond_frames': (C.c_int, [_P, C.c_int32]),
+    'wn_generate_set_condition': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     'wn_weighted_squared_error': (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, _P, _P, _P]),
     'wn_sample_waveform': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_uint64, C.c_uint64, _P, _P]),

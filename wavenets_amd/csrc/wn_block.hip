@@ -80,7 +80,7 @@ int block_forward(const BlockPtrs& k, const BlockBufs& f, hipStream_t s) {
     WnLayerFwdArgs a;
     memset(&a, 0, sizeof(a));
     a.x = h; a.frag_d = k.F16n; a.frag_r = k.F16r;
-    a.bias_d = k.bd[li]; a.bias_r = k.br; a.cb = k.cb;
+    a.bias_d = k.bd[li]; a.bias_r = k.br; a.cb = k.cb; a.cb_frames = k.cb_frames; a.cb_hop = k.cb_hop;
     a.x_out = f.x_out; a.o_out = f.O; a.z_out = f.Z; a.ldz = f.ldz; a.ag_out = f.AG;
     a.res = f.res;                                      // (null: the residual is the conv input itself)
     a.xt[0] = f.xt[0]; a.xt[1] = f.xt[1]; a.xt[2] = nullptr;
@@ -114,7 +114,7 @@ int block_forward(const BlockPtrs& k, const BlockBufs& f, hipStream_t s) {
     // knob 1 = 1 forces the exact-fp32 MFMA kernel
     const bool use16 = k.F16d && k.F16r && wn_debug_get(1) != 1;
     a.x = h; a.frag_d = use16 ? k.F16d : k.Fd[li]; a.frag_r = use16 ? k.F16r : k.Fr;
-    a.bias_d = k.bd[li]; a.bias_r = k.br; a.cb = k.cb;
+    a.bias_d = k.bd[li]; a.bias_r = k.br; a.cb = k.cb; a.cb_frames = k.cb_frames; a.cb_hop = k.cb_hop;
     a.x_out = f.x_out; a.o_out = f.O; a.z_out = f.Z; a.ldz = f.ldz; a.ag_out = f.AG;
     a.res = f.res ? f.res : ((k.depth > 1) ? f.x : nullptr);
     a.xt[0] = f.xt[0]; a.xt[1] = f.xt[1]; a.xt[2] = f.xt[2];
@@ -131,7 +131,7 @@ int block_forward(const BlockPtrs& k, const BlockBufs& f, hipStream_t s) {
     }
     if (k.Cc > 0) g.seg(k.cond, k.Cc, k.Cc, 0, k.Fc);
     g.bias(k.bd[li]);
-    if (k.cb) g.rowbias(k.cb, 2 * k.D);
+    if (k.cb) g.rowbias(k.cb, 2 * k.D, k.cb_frames, k.cb_hop);
     rc = g.run(f.U, 2 * k.D, s);
     if (rc) return rc;
   }

@@ -85,6 +85,7 @@ struct FwdCall {
   wn_plan* p; const float* params; const float* x; const float* cond; int B, T; bool training, prep;
   float* ws; const WsLayout& L; hipStream_t s; const GenRings* rings; LossFuse* lf;
   int64_t rows; float* fragbase;
+  int F, hop, Bc;                    // condition frames per utterance (1: global), inputs per frame, condition rows B * F
   // Forward range guard.  The split-precision kernels cast fp32 activations to fp16 hi|lo unscaled: beyond 65504 the
   // hi part is inf.  Every kernel that produces an input of such a kernel -- the residual stream H[b], the skip sum,
   // the head activations (z is bounded by 1) -- publishes its running max-abs here; the callers turn it into a flag
@@ -97,7 +98,8 @@ struct FwdCall {
   FwdCall(wn_plan* p_, const float* params_, const float* x_, bool prep_, const float* cond_, int B_, int T_, bool training_,
           float* ws_, const WsLayout& L_, hipStream_t s_, const GenRings* rings_, LossFuse* lf_)
       : e(wnp::ex(p_)), p(p_), params(params_), x(x_), cond(cond_), B(B_), T(T_), training(training_), prep(prep_), ws(ws_),
-        L(L_), s(s_), rings(rings_), lf(lf_), rows((int64_t)B_ * T_), fragbase(ws_ + L_.frag), fam(ws_ + L_.fwd_absmax),
+        L(L_), s(s_), rings(rings_), lf(lf_), rows((int64_t)B_ * T_), fragbase(ws_ + L_.frag), F(L_.frames), hop(T_ / L_.frames),
+        Bc(B_ * L_.frames), fam(ws_ + L_.fwd_absmax),
         fp(fwd_paths(p_, e, B_, T_, training_, prep_, rings_ != nullptr, !lf_ ? FWD_LOSS_NONE : lf_->eval ? FWD_LOSS_EVAL : FWD_LOSS_TRAIN)) {}
 
   const float* par(int tensor) const { return params + p->tensors[tensor].off; }
@@ -167,7 +169,11 @@ struct FwdCall {
   }
 
   // conditioning: mapping Dense stack + per-block time-invariant bias  (src/model.py:221-225,
-  // src/layers.py:203-204: conv_cond(repeat(m)) == per-utterance bias)
+  // src/layers.py:203-204: conv_cond(repeat(m)) == per-utterance bias).  With F frames armed (local conditioning,
+  // src/model.py:216-220: the mapped condition is upsampled by repetition) the same phase runs over Bc = B * F rows: the
+  // 1x1 mapping convs over (B, F, Cin) are the Dense stack over its rows, and the bias table has a row per (utterance, frame).
+  // Which kernel each product takes does not depend on Bc: the small-product kernel tiles its rows by 32, the rows GEMM
+  // walks them as one "utterance" of Bc time steps.
   int condition() {
     if (fp.cond == FWD_COND_NONE) return WN_OK;
     if (!cond) { wn_set_error("Conditioning must be provided."); return WN_E_INVALID; }
@@ -178,9 +184,9 @@ struct FwdCall {
       const ConvInfo& c = p->mapping[j];
       if (small)              // Dense: M[j] = act(m W + b), W = kernel (cin, cout)
         rc = wn_launch_sgemm_small_batched(m, mc, 1, 0, par(c.kernel_t), c.cout, 1, 0, ws + L.M[j], c.cout, 0,
-                                           B, c.cout, mc, 1, par(c.bias_t), p->c.mapping_activation, s);
+                                           Bc, c.cout, mc, 1, par(c.bias_t), p->c.mapping_activation, s);
       else
-        rc = Gemm(1, B, c.cout, ceil32(c.cout)).seg(m, mc, mc, 0, fragbase + c.fragF)
+        rc = Gemm(1, Bc, c.cout, ceil32(c.cout)).seg(m, mc, mc, 0, fragbase + c.fragF)
                  .bias(par(c.bias_t)).act(p->c.mapping_activation).run(ws + L.M[j], c.cout, s);
       if (rc) return rc;
       m = ws + L.M[j]; mc = c.cout;
@@ -189,8 +195,8 @@ struct FwdCall {
     if (!fp.cond_batched) {
       for (int b = 0; b < p->N; ++b) {
         const ConvInfo& c = p->blocks[b].conv_cond;
-        rc = Gemm(1, B, D2, ceil32(D2)).seg(m, p->Cc, p->Cc, 0, fragbase + c.fragF)
-                 .bias(par(c.bias_t)).run(ws + L.cb + (int64_t)b * B * D2, D2, s);
+        rc = Gemm(1, Bc, D2, ceil32(D2)).seg(m, p->Cc, p->Cc, 0, fragbase + c.fragF)
+                 .bias(par(c.bias_t)).run(ws + L.cb + (int64_t)b * Bc * D2, D2, s);
         if (rc) return rc;
       }
       return WN_OK;
@@ -201,12 +207,12 @@ struct FwdCall {
     if (small) {              // block z: cbt[:, z * 2D ..] = m W_c(z), W_c = kernel (1, Cc, 2D)
       const int64_t wst = p->N > 1 ? p->tensors[p->blocks[1].conv_cond.kernel_t].off - p->tensors[c0.kernel_t].off : 0;
       rc = wn_launch_sgemm_small_batched(m, p->Cc, 1, 0, par(c0.kernel_t), D2, 1, wst, ws + L.cbt, p->N * D2, D2,
-                                         B, D2, p->Cc, p->N, nullptr, 0, s);
+                                         Bc, D2, p->Cc, p->N, nullptr, 0, s);
     } else {
-      rc = Gemm(1, B, p->N * D2, ceil32(p->N * D2)).seg(m, p->Cc, p->Cc, 0, fragbase + p->frag_condF).run(ws + L.cbt, p->N * D2, s);
+      rc = Gemm(1, Bc, p->N * D2, ceil32(p->N * D2)).seg(m, p->Cc, p->Cc, 0, fragbase + p->frag_condF).run(ws + L.cbt, p->N * D2, s);
     }
     if (rc) return rc;
-    return wn_launch_cond_scatter(ws + L.cbt, params, p->tensors[c0.bias_t].off, bst, B, p->N, D2, ws + L.cb, s);
+    return wn_launch_cond_scatter(ws + L.cbt, params, p->tensors[c0.bias_t].off, bst, Bc, p->N, D2, ws + L.cb, s);
   }
 
   // input causal conv, src/model.py:84-88,228 : KS taps with C_in = 1 (behind the cleared range-guard slot)
@@ -248,7 +254,10 @@ struct FwdCall {
     for (int b = 0; b < p->N; ++b) {
       BlockPtrs k = block_ptrs(p, b, params, fragbase, B, T);
       if (fp.deep16) deep16_ptrs(p, b, fragbase, k);
-      if (fp.cond != FWD_COND_NONE) k.cb = ws + L.cb + (int64_t)b * B * 2 * p->D;
+      if (fp.cond != FWD_COND_NONE) {
+        k.cb = ws + L.cb + (int64_t)b * Bc * 2 * p->D;
+        k.cb_frames = F; k.cb_hop = hop;                 // (F == 1: the row is the utterance)
+      }
       BlockBufs f;
       memset(&f, 0, sizeof(f));
       const int hi = training ? b : (b & 1), ho = training ? b + 1 : ((b + 1) & 1);
@@ -432,6 +441,28 @@ int loss_rows_stage(wn_plan* p, int64_t rows, float gscale, float* g_logits, boo
   return rc;
 }
 
+int condition_only(wn_plan* p, const float* params, const float* cond, int B, int T, float* ws, const WsLayout& L, hipStream_t s) {
+  // (prep = false: the weight images of the priming pass are in the workspace)
+  FwdCall c(p, params, nullptr, false, cond, B, T, false, ws, L, s, nullptr, nullptr);
+  return c.condition();
+}
+
+int cond_frames_check(const char* who, const wn_plan* p, int T) {
+  const int F = ex(p).cond_frames;
+  if (F <= 1 || p->c.cond_inputs <= 0) return 1;
+  if (T % F != 0) {
+    wn_set_error("%s: T = %d inputs do not divide into F = %d condition frames (hop = T / F)", who, T, F);
+    return WN_E_INVALID;
+  }
+  const int hop = T / F;
+  if (hop % 32 != 0) {
+    wn_set_error("%s: T = %d, F = %d gives hop = %d, which is not a multiple of 32 (F > 1 needs whole 32-row tiles per frame)",
+                 who, T, F, hop);
+    return WN_E_INVALID;
+  }
+  return F;
+}
+
 int row_weights_check(const char* who, const wn_exec& e, int B, int T) {
   if (!e.row_weights || e.row_weights_n == (int64_t)B * T) return WN_OK;
   wn_set_error("%s: the armed row weights cover %lld rows, the call has B * T = %lld", who, (long long)e.row_weights_n,
@@ -447,6 +478,7 @@ using namespace wnp;
 static int forward_entry(const char* who, bool training, wn_plan* p, const float* params, const float* x, const float* cond,
                          int32_t B, int32_t T, float* out, float* logits_out, float* workspace, int64_t ws_floats, void* stream) {
   if (!p || !params || !x || !workspace || B < 1 || T < 1) { wn_set_error("%s: bad arguments", who); return WN_E_INVALID; }
+  if (cond_frames_check(who, p, T) < 0) return WN_E_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const WsLayout L = make_layout(p, B, T, training);
   if (ws_floats < L.total) { wn_set_error("%s: workspace too small (%lld < %lld floats)", who, (long long)ws_floats, (long long)L.total); return WN_E_INVALID; }
@@ -474,6 +506,7 @@ extern "C" int wn_eval_loss(wn_plan* p, const float* params, const float* x_full
                             float* workspace, int64_t ws_floats, void* stream) {
   if (!p || !params || !x_full || !workspace || !loss_out || B < 1 || T < 1) { wn_set_error("eval_loss: bad arguments"); return WN_E_INVALID; }
   if (row_weights_check("eval_loss", wnp::ex(p), B, T)) return WN_E_INVALID;
+  if (cond_frames_check("eval_loss", p, T) < 0) return WN_E_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const WsLayout L = make_layout(p, B, T, false);
   if (ws_floats < L.total) { wn_set_error("eval_loss: workspace too small"); return WN_E_INVALID; }
@@ -505,6 +538,7 @@ extern "C" int wn_score(wn_plan* p, const float* params, const float* x_full, co
   if (p->c.cond_inputs > 0 && !cond) { wn_set_error("score: the plan is conditioned (%d inputs) and cond is null", p->c.cond_inputs); return WN_E_INVALID; }
   if (B < 1 || T < 1) { wn_set_error("score: B = %d, T = %d: both must be at least 1", (int)B, (int)T); return WN_E_INVALID; }
   if (row_weights_check("score", wnp::ex(p), B, T)) return WN_E_INVALID;
+  if (cond_frames_check("score", p, T) < 0) return WN_E_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const WsLayout L = make_layout(p, B, T, false);
   if (ws_floats < L.total) {

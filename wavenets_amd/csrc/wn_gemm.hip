@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256, (JT >= 8 ? 2 : (JT >= 4 ? 3 : 4))) void wn_gem
           v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
         }
         if (a.rowbias) {
-          const float* rb = a.rowbias + (int64_t)b * a.ld_rowbias + n0;
+          const float* rb = a.rowbias + wn_cb_row(b, t0, a.rb_frames, a.rb_hop) * a.ld_rowbias + n0;
           v[0] += rb[0]; v[1] += rb[1]; v[2] += rb[2]; v[3] += rb[3];
         }
         if (a.addc) {
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256, (JT >= 8 ? 2 : (JT >= 4 ? 3 : 4))) void wn_gem
           if (n >= a.N) continue;
           float w = v[e];
           if (a.bias) w += a.bias[n];
-          if (a.rowbias) w += a.rowbias[(int64_t)b * a.ld_rowbias + n];
+          if (a.rowbias) w += a.rowbias[wn_cb_row(b, t0, a.rb_frames, a.rb_hop) * a.ld_rowbias + n];
           if (a.addc) w += a.addc[row * a.ld_addc + n];
           if (a.epi == WN_EPI_PLAIN) {
             a.y[row * a.ldy + n] = wn_act(w, a.act);

@@ -786,6 +786,7 @@ int wn_gemm_rows16_ok(const WnGemmArgs& a) {
     if (a.seg[s].plane_k > 0 && (s != 0 || a.seg[s].plane_k % 16 != 0)) return 0;
   }
   if (a.rowbias && (a.ld_rowbias % 4 != 0)) return 0;
+  if (a.rowbias && a.rb_frames > 1) return 0;   // a row bias per frame (local conditioning): the exact-fp32 rows kernel reads it
   return 1;
 }
 

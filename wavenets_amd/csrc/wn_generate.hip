@@ -555,6 +555,11 @@ static int generate_call(GenEntry entry, wn_plan* p, const float* params, const 
     }
   }
   if (!p || !params || (!window && first == 0) || !out || !workspace || B < 1 || length < 0) { wn_set_error("generate: bad arguments"); return WN_E_INVALID; }
+  // (a step is one time row and takes one condition row per utterance: frames belong to the training-form calls)
+  if (wnp::ex(p).cond_frames > 1) {
+    wn_set_error("generate: %d condition frames are armed (wn_plan_set_cond_frames); generation takes one condition row per utterance", wnp::ex(p).cond_frames);
+    return WN_E_INVALID;
+  }
   GenLayout G = gen_layout(p, B, queued != 0);
   if (ws_floats < G.total) { wn_set_error("generate: workspace too small"); return WN_E_INVALID; }
   if (length == 0) return WN_OK;
@@ -570,6 +575,7 @@ static int generate_call(GenEntry entry, wn_plan* p, const float* params, const 
   if (c.primes) {
     rc = c.prime();
     if (rc) return rc;
+    c.e.primed_ws = workspace; c.e.primed_B = B;       // (what wn_generate_set_condition may write into)
   }
   // (a call that is its priming pass alone launches no step: the admission's scratch call at B' = k leaves the session's
   // table, cached by B, where it is)
@@ -587,6 +593,31 @@ static int generate_call(GenEntry entry, wn_plan* p, const float* params, const 
     if ((rc = c.sample(step)) != WN_OK) return rc;
   }
   return WN_OK;
+}
+
+// A new condition for a running queued sequence: the conditioning phase again, into the bias table of the primed workspace.
+// The steps read cb from there (it is state, not a per-step input), so the next step of the next chunk uses it; a chunk's
+// first step does its own pre work (wn_generate_chunk), which is where the 64-channel chain adds cb.
+extern "C" int wn_generate_set_condition(wn_plan* p, const float* params, const float* cond, int32_t B, int32_t queued,
+                                         float* workspace, int64_t ws_floats, void* stream) {
+  if (!p || !params || !cond || !workspace) {
+    wn_set_error("generate_set_condition: null %s", !p ? "plan" : !params ? "params" : !cond ? "cond" : "workspace");
+    return WN_E_INVALID;
+  }
+  if (B < 1) { wn_set_error("generate_set_condition: B must be >= 1 (got %d)", (int)B); return WN_E_INVALID; }
+  if (!queued) { wn_set_error("generate_set_condition: queued sequences only (the sliding window maps the condition in every step)"); return WN_E_INVALID; }
+  if (p->c.cond_inputs <= 0) { wn_set_error("generate_set_condition: the plan has no conditioning"); return WN_E_INVALID; }
+  if (wnp::ex(p).cond_frames > 1) { wn_set_error("generate_set_condition: %d condition frames are armed; a step takes one row per utterance", wnp::ex(p).cond_frames); return WN_E_INVALID; }
+  const GenLayout G = gen_layout(p, B, true);
+  if (ws_floats < G.total) { wn_set_error("generate_set_condition: workspace too small (%lld < %lld floats)", (long long)ws_floats, (long long)G.total); return WN_E_INVALID; }
+  const wn_exec& e = wnp::ex(p);
+  if (e.primed_ws != workspace || e.primed_B != B) {
+    wn_set_error("generate_set_condition: the workspace has not been primed at B = %d by this state (begin the sequence first)", (int)B);
+    return WN_E_INVALID;
+  }
+  const int RF = wn_plan_receptive_field(p);
+  const WsLayout L = make_layout(p, B, RF, false);
+  return condition_only(p, params, cond, B, RF, workspace + G.prime, L, (hipStream_t)stream);
 }
 
 extern "C" int wn_generate_sampled(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
@@ -843,6 +874,10 @@ extern "C" int wn_generate_admit_origin(wn_plan* p, const float* params, const f
     if (!a.ptr) { wn_set_error("generate_admit: %s is null", a.name); return WN_E_INVALID; }
   rc = admit_slots_check("generate_admit", k, slots, B);
   if (rc) return rc;
+  if (wnp::ex(p).cond_frames > 1) {
+    wn_set_error("generate_admit: %d condition frames are armed (wn_plan_set_cond_frames); generation takes one condition row per utterance", wnp::ex(p).cond_frames);
+    return WN_E_INVALID;
+  }
   // (the admission's priming draw is sample position - 1, and the session goes on at `position`: both are 32-bit steps)
   if (position < 1 || position > 0x7fffffffLL - 1) {
     wn_set_error("generate_admit: position must lie in [1, 2147483646] (got %lld)", (long long)position);
@@ -871,6 +906,7 @@ extern "C" int wn_generate_admit_origin(wn_plan* p, const float* params, const f
   rc = generate_call(GEN_ENTRY_BEGIN, p, params, windows, cond, k, position - 1, 1, deterministic, 1, nullptr, first_out, scratch,
                      scratch_floats, stream, reinterpret_cast<const WnSampleRow*>(rows_k), rows_flags_k, origin_k);
   if (rc) return rc;
+  e.primed_ws = workspace; e.primed_B = B;             // (the scratch's priming pass moved the mark: back to the session)
   int64_t widest = 1;
   for (const AdmitSeg& a : segs) widest = std::max(widest, (int64_t)a.d.nslots * a.d.width);
   const dim3 grid((unsigned)std::min<int64_t>((widest + 255) / 256, 256), (unsigned)segs.size(), (unsigned)std::min(k, 65535));

@@ -62,6 +62,9 @@ struct WnGemmArgs {
   float* y2;              // WN_EPI_GATE_FWD: the sigmoid [rows][ld_y2], or null (inference)
   int32_t ld_y2;
   int32_t absmax_any;     // 1: absmax_out is a forward range-guard slot (records inf / NaN too), 0: a gradient's scale slot
+  // rb_frames > 1: rowbias is [B * rb_frames][ld_rowbias], a 32-row tile starting at t0 reads row b * rb_frames + t0 / rb_hop
+  // (local conditioning: rb_hop % 32 == 0, so a tile lies in one frame); 0 / 1: one row per utterance
+  int32_t rb_frames, rb_hop;
 };
 int wn_launch_gemm_rows(const WnGemmArgs& a, hipStream_t s);
 // split-precision variant: w16 = ONE fp16 hi|lo image of all segments' weights concatenated along k
@@ -222,7 +225,14 @@ struct WnLayerFwdArgs {
   const float* xt[3];    // queued generation: tap j reads rows of xt[j] (no time shift) instead of x; or null
   int32_t B, T, R, D, KS, dilation, residual;
   float* absmax_out;     // split-precision kernel: running max-abs of x_out (forward range guard), or null
+  // cb_frames > 1: cb is [B * cb_frames][2D] and the tile at t0 of utterance b reads row b * cb_frames + t0 / cb_hop (local
+  // conditioning: cb_hop % 32 == 0, so a 32-row tile lies in one frame); 0 / 1: row b
+  int32_t cb_frames, cb_hop;
 };
+// the conditioning-bias row of the 32-row tile at t0 of utterance b (wave-uniform)
+__host__ __device__ inline int64_t wn_cb_row(int b, int t0, int frames, int hop) {
+  return frames > 1 ? (int64_t)b * frames + t0 / hop : (int64_t)b;
+}
 int wn_layer_fwd_supported(int R, int D, int KS);
 // fp16 hi/lo split (3-product) variant with LDS-resident weights; frag_d / frag_r are kind-1 images
 int wn_layer_fwd_f16_supported(int R, int D, int KS);
@@ -381,6 +391,10 @@ int wn_launch_cond_gather(const float* slab, int64_t P, int spb, int64_t bd_off0
                           float* dcb, hipStream_t s);
 int wn_launch_cond_wgrad(const float* m, const float* dcb, int B, int Cc, int N, int D2, float* grads, int64_t w_off0,
                          int64_t w_stride, int64_t b_off0, int64_t b_stride, hipStream_t s);
+// local conditioning (wn_cond_frames.hip): dcb[(b * F + f)][n][0 .. D2) = sum of block n's g_u over the T / F rows of frame f of
+// utterance b, all N blocks in one launch, fixed summation order; block n's g_u [B*T][D2] at gu + n * gu_stride
+int wn_launch_cond_frame_sum(const float* gu, int64_t gu_stride, int B, int T, int F, int N, int D2, float* dcb,
+                             hipStream_t s);
 // skip path folded into the head's first convolution (wn_elem.hip): V(b) = W_s(b) W_f0, b' = b_f0 + W_f0^T sum b_s;
 // and the weight gradients of conv_skip (all blocks) and of that convolution from M = Z^T dL/da
 int wn_launch_skip_fold(const float* params, int64_t ws_off0, int64_t ws_stride, int64_t wf0_off, int64_t bf0_off,

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256, MINW) void wn_layer_fwd_kernel(WnLayerFwdArgs 
       u[j][4 * rq + 2] = bv.z; u[j][4 * rq + 3] = bv.w;
     }
   if (a.cb) {   // wave-uniform
-    const float* cbp = a.cb + (int64_t)b * 2 * D + 4 * h;
+    const float* cbp = a.cb + wn_cb_row(b, t0, a.cb_frames, a.cb_hop) * 2 * D + 4 * h;   // the utterance's row, or its frame's
     f32x4 cv[JU][4];
 #pragma unroll
     for (int j = 0; j < JU; ++j)

@@ -81,6 +81,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
     int b, rows_valid;
     bool tin, xvalid[KS];
     int64_t row0;
+    int64_t cbrow;                                       // row of a.cb: the utterance, or its frame at t0 (local conditioning)
     const float* xrow[KS];
   };
   auto tile_at = [&](int64_t tile) {
@@ -91,6 +92,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
     s.tin = t < a.T;
     s.rows_valid = min(32, a.T - t0);
     s.row0 = (int64_t)s.b * a.T + t0;
+    s.cbrow = wn_cb_row(s.b, t0, a.cb_frames, a.cb_hop);
 #pragma unroll
     for (int tap = 0; tap < KS; ++tap) {
       const int ts = a.xt[tap] ? t : t - (KS - 1 - tap) * a.dilation;
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
   // activations, spread to the accumulator layout through the wave's (still idle) output stage.  (As 16 D-layout loads
   // behind the pin it cost a second, exposed round trip per tile: 38.8 against 34.5 us a launch with global conditioning.)
   auto request_cb = [&](const Tile& s) {
-    if (a.cb && 4 * lane < 2 * D) cbv = *reinterpret_cast<const f32x4*>(a.cb + (int64_t)s.b * 2 * D + 4 * lane);
+    if (a.cb && 4 * lane < 2 * D) cbv = *reinterpret_cast<const f32x4*>(a.cb + s.cbrow * 2 * D + 4 * lane);
   };
 
   // The training forms (FAST >= 2) rotate the tap registers through the tile loop: a tap's quads die at its last k-step
@@ -159,7 +161,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_fwd_f16_kernel(WnLayerFwdArgs
       f32x4* cbl = reinterpret_cast<f32x4*>(stage);
       if (4 * lane < 2 * D) cbl[lane] = cbv;
       if constexpr (ROT) {
-        if constexpr (has_next) request_cb(nxt);                   // the bias of the tile that will use it: its utterance may differ
+        if constexpr (has_next) request_cb(nxt);                   // the bias of the tile that will use it: its utterance or frame may differ
       }
 #pragma unroll
       for (int j = 0; j < JU; ++j)

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void wn_layer_fwd_s128_kernel(WnLayerFwdArg
         u[j][4 * rq + 0] = bv.x; u[j][4 * rq + 1] = bv.y; u[j][4 * rq + 2] = bv.z; u[j][4 * rq + 3] = bv.w;
       }
     if (a.cb) {   // wave-uniform
-      const float* cbp = a.cb + (int64_t)b * 2 * D + 4 * h;
+      const float* cbp = a.cb + wn_cb_row(b, t0, a.cb_frames, a.cb_hop) * 2 * D + 4 * h;   // the utterance's row, or its frame's
 #pragma unroll
       for (int j = 0; j < C::JU; ++j)
 #pragma unroll

@@ -411,15 +411,19 @@ WsLayout make_layout(const wn_plan* p, int B, int T, bool training) {
   L.absmax = cv.take(L.n_absmax);
   L.fwd_absmax = cv.take(1);
   // conditioning
+  // (condition rows: one per utterance, or one per (utterance, frame) while the calling state has frames armed)
+  // (p->own is null while wn_plan_create lays out the fold's fixed offsets)
+  L.frames = (p->c.cond_inputs > 0 && p->own && wnp::ex(p).cond_frames > 1) ? wnp::ex(p).cond_frames : 1;
+  const int64_t Bc = (int64_t)B * L.frames;
   if (p->c.cond_inputs > 0) {
-    for (size_t j = 0; j < p->mapping.size(); ++j) L.M.push_back(cv.take((int64_t)B * p->mapping[j].cout));
-    L.cb = cv.take((int64_t)p->N * B * 2 * p->D);
-    L.dcb = cv.take((int64_t)B * 2 * p->D);
-    L.cbt = cv.take((int64_t)B * p->N * 2 * p->D);
+    for (size_t j = 0; j < p->mapping.size(); ++j) L.M.push_back(cv.take(Bc * p->mapping[j].cout));
+    L.cb = cv.take((int64_t)p->N * Bc * 2 * p->D);
+    L.dcb = cv.take(Bc * 2 * p->D);
+    L.cbt = cv.take(Bc * p->N * 2 * p->D);
     int mw = std::max(p->Cc, p->c.cond_inputs);
     for (auto& m : p->mapping) mw = std::max(mw, m.cout);
-    L.g_m0 = cv.take((int64_t)B * mw);
-    L.g_m1 = cv.take((int64_t)B * mw);
+    L.g_m0 = cv.take(Bc * mw);
+    L.g_m1 = cv.take(Bc * mw);
   } else {
     L.cb = L.dcb = L.g_m0 = L.g_m1 = L.cbt = 0;
   }
@@ -439,9 +443,9 @@ WsLayout make_layout(const wn_plan* p, int B, int T, bool training) {
     }
     for (const ConvInfo& c : p->finals) need = std::max(need, slab_need(B, T, c.cin, c.cout));
     if (p->fold_F0 > 0) need = std::max(need, slab_need(1, p->N * p->D + 1, p->S, p->fold_F0));
-    for (const ConvInfo& c : p->mapping) need = std::max(need, slab_need(1, B, c.cin, c.cout));
+    for (const ConvInfo& c : p->mapping) need = std::max(need, slab_need(1, (int)Bc, c.cin, c.cout));
     if (p->c.cond_inputs > 0) {
-      need = std::max(need, slab_need(1, B, p->Cc, 2 * p->D));
+      need = std::max(need, slab_need(1, (int)Bc, p->Cc, 2 * p->D));
       need = std::max(need, wn_colsum_scratch_floats(B, 2 * p->D));
     }
     L.slab_floats = need;
@@ -793,6 +797,18 @@ extern "C" int wn_exec_bind(wn_exec* e) {
 extern "C" int wn_plan_set_dropout(wn_plan* p, float rate, uint64_t seed, uint64_t step) {
   if (!p || rate < 0.f || rate >= 1.f) { wn_set_error("Dropout must be between 0 and 1."); return WN_E_INVALID; }
   wnp::ex(p).drop_rate = rate; wnp::ex(p).drop_seed = seed; wnp::ex(p).drop_step = step;
+  return WN_OK;
+}
+// Local conditioning: the condition of the following training-form calls of the calling state holds
+// `frames` rows per utterance.  Host only; the calls check T against it.
+extern "C" int wn_plan_set_cond_frames(wn_plan* p, int32_t frames) {
+  if (!p) { wn_set_error("set_cond_frames: null plan"); return WN_E_INVALID; }
+  if (frames < 0) { wn_set_error("set_cond_frames: frames must be >= 0 (got %d)", (int)frames); return WN_E_INVALID; }
+  if (frames > 1 && p->c.cond_inputs <= 0) {
+    wn_set_error("set_cond_frames: %d frames on a plan without conditioning", (int)frames);
+    return WN_E_INVALID;
+  }
+  wnp::ex(p).cond_frames = frames;
   return WN_OK;
 }
 extern "C" uint32_t wn_dropout_key_for(uint64_t seed, int32_t block, uint64_t step) { return wn_dropout_key(seed, block, step); }

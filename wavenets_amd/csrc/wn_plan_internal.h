@@ -182,6 +182,7 @@ struct WgSpan {
 struct WgSchedule {
   bool valid = false;
   int B = 0, T = 0, bsplits = 0;
+  int frames = 0;                    // condition frames the layout was carved for (the job tables hold workspace offsets)
   TrainPaths paths;
   DevTable<WnWgJob> jobs;
   DevTable<WnWgLayer> layers, inner;
@@ -239,6 +240,11 @@ struct wn_exec {
   // armed by wn_plan_arm_row_weights: sample_weight of the (B, T) target rows for wn_train_fwd_bwd / wn_eval_loss / wn_score; it stays
   // armed until the caller disarms it
   const float* row_weights = nullptr; int64_t row_weights_n = 0;
+  // armed by wn_plan_set_cond_frames: the condition of the training-form entry points holds this many frames per utterance
+  // (local conditioning); 0 / 1 = one row per utterance (global conditioning)
+  int cond_frames = 0;
+  // the queued generation workspace this state primed last and its batch size (wn_generate_set_condition writes into it)
+  const float* primed_ws = nullptr; int primed_B = 0;
   wnp::WgSchedule wg;           // the cached weight-gradient schedule of the last (B, T) layout it trained
   wnp::GenTable gen;            // the cached block table of the generation chains, for the last batch size it generated
   wnp::AdmitTable admit;        // the cached segment and slot tables of the last admission (wn_generate_admit)
@@ -345,10 +351,13 @@ struct WsLayout {
   int64_t absmax; int n_absmax;         // running max-abs scalars of the gradient tensors (AbsmaxSlots)
   int64_t fwd_absmax;                   // forward range guard: running max-abs of H[b], skip sum, head activations
   int64_t sum_scratch;
-  std::vector<int64_t> M;               // mapping activations [B][w]
-  int64_t cb;                           // [N][B][2D]
+  // conditioning.  Bc = B * frames condition rows: one per utterance (global), one per (utterance, frame) when frames are
+  // armed (local, wn_plan_set_cond_frames)
+  int frames;                           // >= 1
+  std::vector<int64_t> M;               // mapping activations [Bc][w]
+  int64_t cb;                           // [N][Bc][2D]
   int64_t dcb, g_m0, g_m1;
-  int64_t cbt;                          // [B][N*2D]: all blocks' conditioning biases / their gradients
+  int64_t cbt;                          // [Bc][N*2D]: all blocks' conditioning biases / their gradients
   int64_t total;
 };
 
@@ -385,7 +394,11 @@ struct Gemm {
     return *this;
   }
   Gemm& bias(const float* b) { a.bias = b; return *this; }
-  Gemm& rowbias(const float* b, int ld) { a.rowbias = b; a.ld_rowbias = ld; return *this; }
+  // frames > 1: one row of b per (utterance, frame of hop rows), hop % 32 == 0 (local conditioning)
+  Gemm& rowbias(const float* b, int ld, int frames = 0, int hop = 0) {
+    a.rowbias = b; a.ld_rowbias = ld; a.rb_frames = frames; a.rb_hop = hop;
+    return *this;
+  }
   Gemm& addc(const float* c, int ld) { a.addc = c; a.ld_addc = ld; return *this; }
   Gemm& act(int act) { a.act = act; return *this; }
   Gemm& dact(const float* ysaved, int ld, int act) { a.epi = WN_EPI_DACT; a.aux = ysaved; a.ld_aux = ld; a.act = act; return *this; }
@@ -403,6 +416,13 @@ struct Gemm {
     if (a.aux2) v = v && (a.ld_aux2 % 4 == 0) && al16(a.aux2);
     if (a.y2) v = v && (a.ld_y2 % 4 == 0) && al16(a.y2);
     a.vec_out = v ? 1 : 0;
+    // The split-precision rows kernels read one row bias per utterance.  No call hands them a row per frame today (block_forward
+    // takes its two-contraction form only without a conditioning bias); one that did would otherwise drop to the exact-fp32
+    // kernel without a word
+    if (w16_ && a.rowbias && a.rb_frames > 1 && wn_debug_get(1) != 1) {
+      wn_set_error("a row bias per frame on the split-precision rows contraction is not built (local conditioning)");
+      return WN_E_UNSUPPORTED;
+    }
     // knob 1 = 1 forces the exact-fp32 MFMA kernels
     if (w16_ && wn_debug_get(1) != 1 && wn_gemm_rows16_ok(a)) return wn_launch_gemm_rows16(a, w16_, am0_, am1_, amo_, s);
     if (a.epi == WN_EPI_GATE_FWD) { wn_set_error("gate-forward contraction needs the split-precision kernel (alignment / shape)"); return WN_E_UNSUPPORTED; }
@@ -497,6 +517,7 @@ struct BlockPtrs {
   int Cc;                   // time-varying condition channels (standalone layer) or 0
   const float* cond;        // [rows][Cc]
   const float* cb;          // [B][2D] per-utterance conditioning bias (model) or null
+  int cb_frames, cb_hop;    // cb_frames > 1: cb is [B * cb_frames][2D], row b * cb_frames + t / cb_hop (cb_hop % 32 == 0)
   bool fused;
   const float* F16d; const float* F16r;   // fp16 split images of the gated conv / conv1, or null
   const float* G16u; const float* G16x;   // fp16 split images of the backward-data products, or null
@@ -586,6 +607,9 @@ void deep16_ptrs(const wn_plan* p, int b, const float* fragbase, BlockPtrs& k);
 int forward_core(wn_plan* p, const float* params, const float* x, bool prep, const float* cond, int B,
                  int T, bool training, float* ws, const WsLayout& L, hipStream_t s, const GenRings* rings = nullptr,
                  LossFuse* lf = nullptr);
+// the conditioning phase of a forward pass alone: mapping stack and the blocks' bias table cb into the workspace of layout L
+// (wn_generate_set_condition: a new condition into the table a queued generation step reads)
+int condition_only(wn_plan* p, const float* params, const float* cond, int B, int T, float* ws, const WsLayout& L, hipStream_t s);
 // what a pass hands back from the logits in the workspace: a copy of them, and the model output (their softmax for a
 // categorical head, the logits themselves for a mixture head); either may be null
 int emit_outputs(const wn_plan* p, const float* ws, const WsLayout& L, int64_t rows, float* logits_out, float* out, hipStream_t s);
@@ -599,6 +623,9 @@ int loss_rows_stage(wn_plan* p, int64_t rows, float gscale, float* g_logits, boo
                     float* absmax_out, hipStream_t s, const float* row_weight);
 // the armed row weights against the rows of a call: WN_E_INVALID with both numbers, before the device is touched
 int row_weights_check(const char* who, const wn_exec& e, int B, int T);
+// the armed condition frames against a call over T inputs: the frames per utterance (>= 1), or WN_E_INVALID (negative) with
+// T, the frames and the hop in the message when T % frames != 0 or the hop is no multiple of 32; before the device is touched
+int cond_frames_check(const char* who, const wn_plan* p, int T);
 
 }  // namespace wnp
 

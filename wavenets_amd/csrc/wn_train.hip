@@ -20,10 +20,11 @@ void add_jobs(std::vector<WnWgJob>& jobs, int64_t x_off, int ldx, int K, int shi
     }
 }
 
-// the cached schedule of e: rebuilt when (B, T, bsplits, paths) is not the key it was built for
+// the cached schedule of e: rebuilt when (B, T, bsplits, condition frames, paths) is not the key it was built for (the
+// tables hold workspace offsets, and the regions behind the conditioning's move with its row count)
 int ensure_schedule(const wn_plan* p, wn_exec& e, const WsLayout& L, int B, int T, const TrainPaths& tp) {
   WgSchedule& g = e.wg;
-  if (g.valid && g.B == B && g.T == T && g.bsplits == L.bsplits && g.paths == tp) return WN_OK;
+  if (g.valid && g.B == B && g.T == T && g.bsplits == L.bsplits && g.frames == L.frames && g.paths == tp) return WN_OK;
   const bool layerk = tp.layerk(), pairk = tp.pairk(), fold = tp.fold;
   std::vector<WnWgLayer> wgl, wgli;
   std::vector<WnWgPair> pairs[3];
@@ -212,7 +213,7 @@ int ensure_schedule(const wn_plan* p, wn_exec& e, const WsLayout& L, int B, int 
   if (rc) return rc;
   g.h_cov.swap(cov); g.spans.swap(spans);
   g.n_side = n_side; g.overlap = layerk || pairk; g.cov_head = head_own ? cov_head : (int)g.h_cov.size();
-  g.B = B; g.T = T; g.bsplits = L.bsplits; g.paths = tp;
+  g.B = B; g.T = T; g.bsplits = L.bsplits; g.frames = L.frames; g.paths = tp;
   g.valid = true;
   return WN_OK;
 }
@@ -235,6 +236,7 @@ struct TrainCall {
   const float* mlast = nullptr;      // the mapped condition (input of every conv_cond)
   TrainPaths tp;                     // backward half: the kernel families of this call
   bool cond_batched = false;
+  int F = 1, Bc = 0;                 // condition frames per utterance (local conditioning; 1: global) and condition rows B * F
   float* g_x = nullptr; float* g_cond = nullptr;   // wn_vjp: gradients at the input waveform / the condition (null: not formed)
   int64_t pm = 0;                    // folded skip path: row pitch of the slab of M = Z^T dL/da with the column sums behind it
   float* am_GF(int i) const { return am + slot.gf(i); }
@@ -251,6 +253,7 @@ struct TrainCall {
     p = p_; params = params_; x_full = nullptr; cond = cond_; B = B_; T = T_; global_batch = B_; n_replicas = 1;
     grads = grads_; loss_out = nullptr; pred_out = nullptr; ws = workspace; s = s_;
     L = make_layout(p, B, T, true);
+    F = L.frames; Bc = B * F;
     rows = (int64_t)B * T;
     inputs = workspace + L.probs;
     am = workspace + L.absmax;
@@ -329,13 +332,23 @@ struct TrainCall {
   }
 
   // conv_cond of ONE block on the time-invariant mapped condition: dW_c = m^T dcb, db_c = sum_b dcb, g_m += dcb W_c^T
-  int cond_block_bwd(const BlockInfo& bi) {
+  // (dcb: the Bc sums of this block's g_u, [Bc][ld])
+  int cond_block_bwd(const BlockInfo& bi, const float* dcb, int ld) {
     const ConvInfo& c = bi.conv_cond;
-    int r = wgrad(mlast, p->Cc, p->Cc, 0, ws + L.dcb, 2 * p->D, 2 * p->D, 1, B, grads + p->tensors[c.kernel_t].off,
+    int r = wgrad(mlast, p->Cc, p->Cc, 0, dcb, ld, 2 * p->D, 1, Bc, grads + p->tensors[c.kernel_t].off,
                   grads + p->tensors[c.bias_t].off, nullptr, slab, s);
     if (r) return r;
-    return Gemm(1, B, p->Cc, ceil32(p->Cc)).seg(ws + L.dcb, 2 * p->D, 2 * p->D, 0, fragbase + c.fragB)
+    return Gemm(1, Bc, p->Cc, ceil32(p->Cc)).seg(dcb, ld, 2 * p->D, 0, fragbase + c.fragB)
         .addc(ws + L.g_m0, p->Cc).run(ws + L.g_m0, p->Cc, s);
+  }
+
+  // local conditioning: the per-frame sums of every block's g_u, [Bc][N * 2D] into cbt (wn_cond_frames.hip).  The blocks'
+  // own per-utterance sums and the slab gather are the F == 1 paths.
+  int frame_sums() {
+    const int64_t stride = p->N > 1 ? L.GU[1] - L.GU[0] : 0;
+    for (int b = 1; b < p->N; ++b)
+      if (L.GU[b] != L.GU[0] + (int64_t)b * stride) { wn_set_error("cond_frame_sum: g_u regions are not evenly spaced"); return WN_E_UNSUPPORTED; }
+    return wn_launch_cond_frame_sum(ws + L.GU[0], stride, B, T, F, p->N, 2 * p->D, ws + L.cbt, s);
   }
 
   // ---- head, last conv first: d loss / d logits (written by the loss stage into GF.back()) down to the skip sum ----
@@ -433,7 +446,7 @@ struct TrainCall {
       bg.g_o_tmp = p->S == 0 ? ws + L.GO[b] : nullptr;
       bg.g_u = ws + L.GU[b];
       bg.g_x = pairk ? nullptr : ws + L.GH[b];     // (pairs: the next launch forms g_x of this block)
-      bg.dcb = (bi.has_cond && !cond_batched) ? ws + L.dcb : nullptr;
+      bg.dcb = (bi.has_cond && !cond_batched && F == 1) ? ws + L.dcb : nullptr;
       bg.slab = slab;
       bg.am_gxout = bg.g_xout ? am_GH(b + 1) : nullptr;
       bg.am_gskip = g_skip ? am_gskip : nullptr;
@@ -445,10 +458,16 @@ struct TrainCall {
         // g_o == g_skip for this block: the job table reads GO[b]
         WN_HIP_CHECK(hipMemcpyAsync(ws + L.GO[b], g_skip, rows * p->R * sizeof(float), hipMemcpyDeviceToDevice, s));
       }
-      if (bi.has_cond && !cond_batched) {
-        rc = cond_block_bwd(bi);
+      if (bi.has_cond && !cond_batched && F == 1) {
+        rc = cond_block_bwd(bi, ws + L.dcb, 2 * p->D);
         if (rc) return rc;
       }
+    }
+    if (F > 1 && p->c.cond_inputs > 0 && !cond_batched) {
+      // frames: every block's sums in one launch behind the chain, then the per-block products on their columns of cbt
+      if ((rc = frame_sums())) return rc;
+      for (int b = p->N - 1; b >= 0; --b)
+        if (p->blocks[b].has_cond && (rc = cond_block_bwd(p->blocks[b], ws + L.cbt + (int64_t)b * 2 * p->D, p->N * 2 * p->D))) return rc;
     }
     return WN_OK;
   }
@@ -492,19 +511,31 @@ struct TrainCall {
     const BlockInfo& b0 = p->blocks[0]; const BlockInfo& b1 = p->blocks[p->N > 1 ? 1 : 0];
     const Strided db = strided(b0.dil.back().bias_t, b1.dil.back().bias_t);
     const Strided cw = strided(b0.conv_cond.kernel_t, b1.conv_cond.kernel_t), cbi = strided(b0.conv_cond.bias_t, b1.conv_cond.bias_t);
-    rc = wn_launch_cond_gather(ws + L.bslab, p->nparams, L.bsplits, db.off, db.stride, B, p->N, D2, ws + L.cbt, s);
+    rc = F > 1 ? frame_sums()
+               : wn_launch_cond_gather(ws + L.bslab, p->nparams, L.bsplits, db.off, db.stride, B, p->N, D2, ws + L.cbt, s);
     if (rc) return rc;
-    if (cond_small(p) && (int64_t)p->N * B * p->Cc <= L.slab_floats) {
+    if (cond_small(p) && (int64_t)p->N * Bc * p->Cc <= L.slab_floats) {
       // g_m = sum_z dcb_z W_c(z)^T: one product per block into the (idle) slab, then their sum
       rc = wn_launch_sgemm_small_batched(ws + L.cbt, p->N * D2, 1, D2, params + cw.off, 1, D2, cw.stride,
-                                         slab, p->Cc, (int64_t)B * p->Cc, B, p->Cc, D2, p->N, nullptr, 0, s);
+                                         slab, p->Cc, (int64_t)Bc * p->Cc, Bc, p->Cc, D2, p->N, nullptr, 0, s);
       if (rc) return rc;
       WnVecSumArgs v;
-      v.base = slab; v.off0 = 0; v.stride = (int64_t)B * p->Cc; v.count = p->N; v.len = B * p->Cc; v.out = ws + L.g_m0;
+      v.base = slab; v.off0 = 0; v.stride = (int64_t)Bc * p->Cc; v.count = p->N; v.len = Bc * p->Cc; v.out = ws + L.g_m0;
       rc = wn_launch_vecsum(v, s);
     } else
-    rc = Gemm(1, B, p->Cc, ceil32(p->Cc)).seg(ws + L.cbt, p->N * D2, p->N * D2, 0, fragbase + p->frag_condB).run(ws + L.g_m0, p->Cc, s);
+    rc = Gemm(1, Bc, p->Cc, ceil32(p->Cc)).seg(ws + L.cbt, p->N * D2, p->N * D2, 0, fragbase + p->frag_condB).run(ws + L.g_m0, p->Cc, s);
     if (rc) return rc;
+    // dW_c, db_c: one thread per element walks the condition rows (wn_cond_wgrad_kernel) -- written for a handful of
+    // utterances.  With frames the rows are B * F: the generic weight-gradient product per block, as cond_block_bwd takes it
+    if (F > 1) {
+      for (int b = 0; b < p->N; ++b) {
+        const ConvInfo& c = p->blocks[b].conv_cond;
+        rc = wgrad(mlast, p->Cc, p->Cc, 0, ws + L.cbt + (int64_t)b * D2, p->N * D2, D2, 1, Bc, grads + p->tensors[c.kernel_t].off,
+                   grads + p->tensors[c.bias_t].off, nullptr, slab, s);
+        if (rc) return rc;
+      }
+      return WN_OK;
+    }
     return wn_launch_cond_wgrad(mlast, ws + L.cbt, B, p->Cc, p->N, D2, grads, cw.off, cw.stride, cbi.off, cbi.stride, s);
   }
 
@@ -600,19 +631,20 @@ struct TrainCall {
       const float* gm_cur = ws + L.g_m0;      // gradient w.r.t. post-activation output of the last Dense
       float* gm_other = ws + L.g_m1;
       if (g_cond && p->mapping.empty())       // the blocks read the condition itself
-        WN_HIP_CHECK(hipMemcpyAsync(g_cond, gm_cur, (int64_t)B * p->Cc * sizeof(float), hipMemcpyDeviceToDevice, s));
+        WN_HIP_CHECK(hipMemcpyAsync(g_cond, gm_cur, (int64_t)Bc * p->Cc * sizeof(float), hipMemcpyDeviceToDevice, s));
       for (int j = (int)p->mapping.size() - 1; j >= 0; --j) {
         const ConvInfo& c = p->mapping[j];
         const float* yin = (j == 0) ? cond : ws + L.M[j - 1];
         // pre-activation gradient g_pre = g * act'(M[j])  (tiny: B x width)
-        rc = wn_launch_dact_mul(gm_cur, ws + L.M[j], gm_other, (int64_t)B * c.cout, p->c.mapping_activation, s);
+        rc = wn_launch_dact_mul(gm_cur, ws + L.M[j], gm_other, (int64_t)Bc * c.cout, p->c.mapping_activation, s);
         if (rc) return rc;
         if (j == 0 && g_cond) {   // wn_vjp: the gradient at the condition, g_pre W_0^T (B x cond_inputs)
           rc = wn_launch_sgemm_small_batched(gm_other, c.cout, 1, 0, params + p->tensors[c.kernel_t].off, 1, c.cout, 0, g_cond, c.cin, 0,
-                                             B, c.cin, c.cout, 1, nullptr, 0, s);
+                                             Bc, c.cin, c.cout, 1, nullptr, 0, s);
           if (rc) return rc;
         }
-        if (cond_small(p)) {
+        // (the small form's bias sum is one thread per column walking the rows: for the handful of rows of global conditioning)
+        if (cond_small(p) && F == 1) {
           // dW = yin^T g_pre (cin x cout, contraction over the B utterances), db = column sums of g_pre
           rc = wn_launch_sgemm_small_batched(yin, 1, c.cin, 0, gm_other, c.cout, 1, 0, grads + p->tensors[c.kernel_t].off, c.cout, 0,
                                              c.cin, c.cout, B, 1, nullptr, 0, s);
@@ -629,12 +661,12 @@ struct TrainCall {
           }
           continue;
         }
-        rc = wgrad(yin, c.cin, c.cin, 0, gm_other, c.cout, c.cout, 1, B, grads + p->tensors[c.kernel_t].off,
+        rc = wgrad(yin, c.cin, c.cin, 0, gm_other, c.cout, c.cout, 1, Bc, grads + p->tensors[c.kernel_t].off,
                    grads + p->tensors[c.bias_t].off, nullptr, slab, s);
         if (rc) return rc;
         if (j > 0) {
           float* dst = const_cast<float*>(gm_cur);
-          rc = Gemm(1, B, c.cin, ceil32(c.cin)).seg(gm_other, c.cout, c.cout, 0, fragbase + c.fragB).run(dst, c.cin, s);
+          rc = Gemm(1, Bc, c.cin, ceil32(c.cin)).seg(gm_other, c.cout, c.cout, 0, fragbase + c.fragB).run(dst, c.cin, s);
           if (rc) return rc;
         }
       }
@@ -649,7 +681,7 @@ struct TrainCall {
     slab = ws + L.slab;
     if (p->c.cond_inputs > 0) {
       mlast = p->mapping.empty() ? cond : ws + L.M.back();
-      rc = wn_launch_fill(ws + L.g_m0, 0.f, (int64_t)B * p->Cc, s);
+      rc = wn_launch_fill(ws + L.g_m0, 0.f, (int64_t)Bc * p->Cc, s);
       if (rc) return rc;
     }
     // conditioning of all blocks as one layer: the per-utterance sums of d u come out of the weight-gradient
@@ -703,6 +735,7 @@ extern "C" int wn_train_fwd_bwd(wn_plan* p, const float* params, const float* x_
                                 void* stream) {
   if (!p || !params || !x_full || !workspace || !loss_out || !grads || B < 1 || T < 1) { wn_set_error("train_fwd_bwd: bad arguments"); return WN_E_INVALID; }
   if (wnp::row_weights_check("train_fwd_bwd", wnp::ex(p), B, T)) return WN_E_INVALID;
+  if (wnp::cond_frames_check("train_fwd_bwd", p, T) < 0) return WN_E_INVALID;
   TrainCall c{wnp::ex(p)};
   c.bind(p, params, cond, B, T, grads, workspace, (hipStream_t)stream);
   c.x_full = x_full;
@@ -730,6 +763,7 @@ extern "C" int wn_vjp(wn_plan* p, const float* params, const float* x, const flo
   if (g_kind != 0 && g_kind != 1) { wn_set_error("vjp: g_kind must be 0 (network output) or 1 (logits) (got %d)", (int)g_kind); return WN_E_INVALID; }
   if (p->c.cond_inputs > 0 && !cond) { wn_set_error("vjp: the plan is conditioned and cond is null"); return WN_E_INVALID; }
   if (p->c.cond_inputs <= 0 && g_cond) { wn_set_error("vjp: g_cond on a plan without conditioning"); return WN_E_INVALID; }
+  if (B >= 1 && T >= 1 && wnp::cond_frames_check("vjp", p, T) < 0) return WN_E_INVALID;
   TrainCall c{wnp::ex(p)};
   c.bind(p, params, cond, B, T, grads, workspace, (hipStream_t)stream);
   c.g_x = g_x; c.g_cond = g_cond;

@@ -13,6 +13,7 @@ file name:
       wavenet_blocks/wave_net_layer[_b]/dilated_stack/conv1d[_i]/vars/{0,1}
       wavenet_blocks/wave_net_layer[_b]/{conv1,conv_skip,conv_cond}/vars/{0,1}
       final/conv1d[_i]/vars/{0,1}            mapping/layers/dense[_j]/vars/{0,1}
+      (conditioning='local': mapping/layers/conv1d[_j]/vars/{0,1}, kernels (1, cin, w))
   (``mapping`` is a ``keras.Sequential``, src/model.py:142-148: saving_lib keeps a Sequential's children under an extra
   ``layers`` group; the trailing ``Identity`` layer has no variables)
   written and read by ``wavenets_amd/h5.py`` (no h5py in the image).  Weights only, like the reference.  The importer
@@ -42,8 +43,10 @@ def _suffix(name: str, i: int) -> str:
   return name if i == 0 else f'{name}_{i}'
 
 
-def keras_path(var_name: str) -> str:
-  """``block3/dil0/kernel`` -> ``wavenet_blocks/wave_net_layer_3/dilated_stack/conv1d/vars/0`` etc."""
+def keras_path(var_name: str, local: bool = False) -> str:
+  """``block3/dil0/kernel`` -> ``wavenet_blocks/wave_net_layer_3/dilated_stack/conv1d/vars/0`` etc.  ``local``: the
+  mapping network of a locally conditioned model is a Sequential of Conv1D layers behind a Lambda (src/model.py:131-140),
+  so its members are ``conv1d[_j]`` as in ``final``."""
   parts = var_name.split('/')
   idx = {'kernel': '0', 'bias': '1'}[parts[-1]]
   head = parts[0]
@@ -56,7 +59,7 @@ def keras_path(var_name: str) -> str:
   elif head.startswith('final'):
     path = ['final', _suffix('conv1d', int(head[5:]))]
   elif head.startswith('mapping'):
-    path = ['mapping', 'layers', _suffix('dense', int(head[7:]))]
+    path = ['mapping', 'layers', _suffix('conv1d' if local else 'dense', int(head[7:]))]
   else:
     raise ValueError(f'unknown variable {var_name}')
   return '/'.join(path + ['vars', idx])
@@ -79,7 +82,7 @@ def _tree_from_model(model) -> dict:
   tree: dict = {}
   for name, w in zip(model.variable_names, model.get_weights()):
     node = tree
-    parts = keras_path(name).split('/')
+    parts = keras_path(name, getattr(model, 'conditioning', None) == 'local').split('/')
     for p in parts[:-1]:
       node = node.setdefault(p, {})
     node[parts[-1]] = np.asarray(w, dtype=np.float32)

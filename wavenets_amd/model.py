@@ -8,6 +8,7 @@ device memory, streams and ``torch.distributed`` (RCCL).
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 from typing import List, Optional
 
@@ -106,6 +107,18 @@ class _Mean:
     return self.total / max(self.count, 1)
 
 
+def _disarms_frames(fn):
+  """Local conditioning: ``_split_inputs`` arms the condition's frames for the call; whatever happens, the call ends with
+  the plan disarmed, so that a pass without frames (generation, a globally conditioned model) never sees them."""
+  @functools.wraps(fn)
+  def wrapper(self, *args, **kwargs):
+    try:
+      return fn(self, *args, **kwargs)
+    finally:
+      self._arm_frames(0)
+  return wrapper
+
+
 class _NetFn(torch.autograd.Function):
   """WaveNet.differentiable: wn_forward_training on the model's training workspace, wn_vjp from the gradient autograd
   hands back.  Inputs (x, cond, flat_params) and a zero-size anchor that keeps the node alive."""
@@ -121,9 +134,12 @@ class _NetFn(torch.autograd.Function):
     else:
       model._set_dropout_state(0.0, 0)
     state = (model.dropout if drop else 0.0, model._drop_armed_step if drop else 0)
+    frames = cond.shape[1] if (cond is not None and cond.dim() == 3) else 0     # local conditioning, F > 1
     try:
+      model._arm_frames(frames)
       ws = model._workspace('train', L.wn_plan_workspace_floats(model._plan, B, T, 1))
       model._train_gen += 1
+      model._last_train_frames = frames if frames > 1 else 0
       out = torch.empty(B, T, model.spec.out_channels, dtype=torch.float32, device=model._device)
 
       def run():
@@ -139,8 +155,9 @@ class _NetFn(torch.autograd.Function):
         mode = 1
     finally:
       model._set_dropout_state(model.dropout, model._drop_armed_step)
+      model._arm_frames(0)
     ctx.model, ctx.mode, ctx.drop_state, ctx.stamp, ctx.done = model, mode, state, model._train_gen, False
-    ctx.want_probs = want_probs
+    ctx.want_probs, ctx.frames = want_probs, frames
     ctx.save_for_backward(x, cond)
     return out
 
@@ -172,12 +189,14 @@ class _NetFn(torch.autograd.Function):
     L.wn_debug_set(1, ctx.mode)
     model._set_dropout_state(*ctx.drop_state)
     try:
+      model._arm_frames(ctx.frames)
       _lib.check(L.wn_vjp(model._plan, _lib.ptr(flat_params), _lib.ptr(x), _lib.ptr(cond), B, T, _lib.ptr(g),
                           0 if ctx.want_probs else 1, _lib.ptr(model.flat_grads), _lib.ptr(g_x), _lib.ptr(g_c),
                           _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
     finally:
       L.wn_debug_set(1, prev)
       model._set_dropout_state(model.dropout, model._drop_armed_step)
+      model._arm_frames(0)
     return g_x, g_c, (model.flat_grads.clone() if need_p else None), None, None, None, None
 
 
@@ -237,9 +256,15 @@ class GenerationSession:
   (stream[b], t - origins[b]).  All zero unless the session was created with own_clock=True or a request admitted by admit_own_clock;
   row_positions is position - origins[b], the number of samples row b's present clock has counted."""
 
-  def __init__(self, model, sampling, condition, window, batch_size, use_queues, deterministic, start=0, own_clock=False):
+  def __init__(self, model, sampling, condition, window, batch_size, use_queues, deterministic, start=0, own_clock=False,
+               frames=None, hop=None):
     L = _lib.lib()
     self._model, self._sampling, self._cond, self._window = model, sampling, condition, window
+    # local conditioning (DESIGN.md section 36): frames (B, F, Cin) and the samples per frame.  The step that emits sample g,
+    # counted from `start`, uses frame g // hop; the priming pass uses frame 0 (`condition`).  A row an admission replaced
+    # has left the schedule and keeps the condition set_condition gives it.
+    self._frames, self._hop, self._frame = frames, hop, 0
+    self._off_schedule = set()
     # per-row controls: the device table of the session, read by every chunk (and by the exact-fp32 rerun of one)
     self._rows = sampling.device_table(model._device) if isinstance(sampling, _RowControls) else None
     self._B, self._queued, self._det = int(batch_size), int(bool(use_queues)), int(bool(deterministic))
@@ -275,12 +300,84 @@ class GenerationSession:
     return [self.position - o for o in self._origins]
 
   def generate(self, n):
-    """The next (B, n, 1) samples, n >= 1.  A chunk that raises leaves position where it was."""
+    """The next (B, n, 1) samples, n >= 1.  A chunk that raises leaves position where it was.  With a frame schedule
+    (local conditioning) the chunk is split at the frame boundaries and the condition table rewritten there; a chunk that
+    would run past the last frame raises ValueError before anything is made."""
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
       raise ValueError(f'n must be an int >= 1 (got {n!r})')
+    if self._frames is None:
+      return self._generate_chunk(int(n))
+    n, hop, F = int(n), self._hop, self._frames.shape[1]
+    done = self.position - self._start
+    if done + n > F * hop:
+      raise ValueError(f'generation session: {done} + {n} samples run past the {F} condition frames of hop {hop} '
+                       f'({F * hop} samples)')
+    pieces = []
+    while n > 0:
+      g = self.position - self._start
+      f = g // hop
+      if f != self._frame:
+        self._to_frame(f)
+      take = min(n, (f + 1) * hop - g)
+      pieces.append(self._generate_chunk(take))
+      n -= take
+    return pieces[0] if len(pieces) == 1 else torch.cat(pieces, 1)
+
+  def _to_frame(self, f):
+    cond = self._frames[:, f, :].clone()
+    if self._off_schedule:
+      keep = torch.tensor(sorted(self._off_schedule), device=cond.device)
+      cond[keep] = self._cond[keep]
+    self._write_condition(cond)
+    self._frame = f
+
+  def _write_condition(self, cond):
+    """self._cond = cond, and into the bias table of the workspace when the sequence has begun (the priming pass of a
+    sequence that has not takes it from self._cond)."""
+    m, L = self._model, _lib.lib()
+    cond = cond.contiguous()
+    if self.position > self._start:
+      if not self._queued:
+        raise NotImplementedError('set_condition needs use_queues=True: the sliding window maps the condition in every step')
+
+      def run():
+        _lib.check(L.wn_generate_set_condition(m._plan, _lib.ptr(m.flat_params), _lib.ptr(cond), self._B, 1, _lib.ptr(self._ws),
+                                               self._ws.numel(), _lib.stream_ptr()))
+      if self.exact:
+        with m.exact_fp32():
+          run()
+      else:
+        run()
+    self._cond = cond
+
+  def set_condition(self, condition, slots=None):
+    """A new condition for running rows, from the next step on: (B, Cin), or (k, Cin) for the k rows `slots`.  Works on a
+    globally conditioned model too.  On a session with a frame schedule the rows still on the schedule are rewritten at
+    the next frame boundary; rows an admission replaced are driven by this call alone."""
+    m = self._model
+    self._check_usable()
+    if self._cond is None:
+      raise ValueError('set_condition: the model has no conditioning')
+    condition = torch.as_tensor(condition, dtype=torch.float32, device=m._device)
+    if condition.dim() == 3 and condition.shape[1] == 1:
+      condition = condition[:, 0, :]
+    cond = self._cond.clone()
+    if slots is None:
+      if tuple(condition.shape) != tuple(cond.shape):
+        raise ValueError(f'condition must have shape {tuple(cond.shape)} (got {tuple(condition.shape)})')
+      cond.copy_(condition)
+    else:
+      slot_list = [int(slots)] if isinstance(slots, (int, np.integer)) else [int(v) for v in slots]
+      if any(v < 0 or v >= self._B for v in slot_list) or len(set(slot_list)) != len(slot_list):
+        raise ValueError(f'slots must be distinct ints in [0, {self._B}) (got {slot_list})')
+      if tuple(condition.shape) != (len(slot_list), cond.shape[1]):
+        raise ValueError(f'condition must have shape {(len(slot_list), cond.shape[1])} (got {tuple(condition.shape)})')
+      cond[torch.tensor(slot_list, device=m._device)] = condition
+    self._write_condition(cond)
+
+  def _generate_chunk(self, n):
     m, L, first = self._model, _lib.lib(), self.position
     self._check_usable()
-    n = int(n)
     out = torch.empty(self._B, n, 1, dtype=torch.float32, device=m._device)
     begins = first == self._start            # the chunk that begins the sequence from the window
 
@@ -385,6 +482,8 @@ class GenerationSession:
       raise ValueError('Conditioning must be provided.')
     if condition is not None:
       condition = torch.as_tensor(condition, dtype=torch.float32, device=m._device).contiguous()
+      if m.conditioning == 'local' and condition.dim() == 3 and condition.shape[1] == 1:
+        condition = condition[:, 0, :].contiguous()          # a held condition as one frame, (k, 1, Cin)
       if self._cond is None or tuple(condition.shape) != (k,) + tuple(self._cond.shape[1:]):
         want = None if self._cond is None else (k,) + tuple(self._cond.shape[1:])
         raise ValueError(f'condition must have shape {want} (got {tuple(condition.shape)})')
@@ -444,6 +543,7 @@ class GenerationSession:
       if not self._admitted:
         self._cond = self._cond.clone()          # (the caller's tensor stays as it is)
       self._cond[torch.tensor(slot_list, device=m._device)] = condition
+      self._off_schedule.update(slot_list)         # (a frame schedule per admitted request is a follow-up: section 36)
     self._admitted = True
     return first_out
 
@@ -545,7 +645,10 @@ class WaveNet(torch.nn.Module):
         for b in range(s.blocks)]
     self.final = [_ConvHandle(self, f'final{i}') for i in range(len(s.final_layers_channels) + 1)]
     self.mapping = [_ConvHandle(self, f'mapping{j}') for j in range(len(s.mapping_layers))] \
-        if conditioning == 'global' else None
+        if conditioning is not None else None
+    self._frames_armed = 0                # condition frames armed in the plan (local conditioning, per call)
+    self._last_frames = None              # F of the last training-form call (kernel_report)
+    self._last_train_frames = 0           # F of the last pass that wrote the training workspace (training_intermediate)
     if conditioning is None:
       self.build(None)
 
@@ -601,7 +704,10 @@ class WaveNet(torch.nn.Module):
     sh = (C.c_int64 * 3)()
     for i, (nm, shp) in enumerate(shapes):
       _lib.check(L.wn_plan_tensor_info(self._plan, i, C.byref(off), C.byref(ln), C.byref(nd), sh, C.byref(isk)))
-      assert tuple(sh[:nd.value]) == tuple(shp), (nm, tuple(sh[:nd.value]), shp)
+      # (local conditioning: the library's mapping stack is the Dense stack over the B * F condition rows; the variable is the
+      # reference's 1x1 Conv1D kernel (1, cin, w) with the same flat element order)
+      lib_shp = shp[1:] if (self.conditioning == 'local' and nm.startswith('mapping') and len(shp) == 3) else shp
+      assert tuple(sh[:nd.value]) == tuple(lib_shp), (nm, tuple(sh[:nd.value]), shp)
       self._offsets.append(off.value)
       self._shapes.append(tuple(shp))
     total = L.wn_plan_param_count(self._plan)
@@ -639,7 +745,14 @@ class WaveNet(torch.nn.Module):
     """Which kernel family each phase selects for this network (the fast paths are shape-specialised)."""
     buf = C.create_string_buffer(2048)
     _lib.check(_lib.lib().wn_plan_describe(self._plan, buf, 2048))
-    return buf.value.decode()
+    text = buf.value.decode()
+    if self.conditioning == 'local':
+      # the frames of the last training-form call (F > 1: the bias table has a row per frame and its gradient comes from
+      # wn_cond_frame_sum_kernel; F = 1 runs the global model's kernels)
+      frames = 'F=none yet' if self._last_frames is None else f'F={self._last_frames}' + \
+          (' (per-frame bias rows, wn_cond_frame_sum_kernel)' if self._last_frames > 1 else ' (the global kernels)')
+      text += f' | conditioning=local {frames}'
+    return text
 
   def _log_kernels_once(self):
     import os
@@ -753,13 +866,43 @@ class WaveNet(torch.nn.Module):
     x = torch.as_tensor(x, dtype=torch.float32, device=self._device).contiguous()
     if x.dim() != 3 or x.shape[-1] != 1:
       raise ValueError('input must have shape (batch, samples, 1)')
+    if self.conditioning == 'local':
+      return self._split_local(x, cond)
     if not self.built:
       self.build([tuple(x.shape), tuple(cond.shape)] if cond is not None else tuple(x.shape))
     if cond is not None and (cond.dim() != 2 or cond.shape[0] != x.shape[0] or cond.shape[1] != self._cond_inputs):
       raise ValueError('condition must have shape (batch, n_cond)')
     return x, cond
 
+  def _split_local(self, x, cond):
+    """Local conditioning: the condition is (B, F), the reference's form (one channel,
+    src/model.py:133), or (B, F, Cin).  Returns it as the library takes it -- (B, F, Cin) with the plan armed for F frames,
+    or (B, Cin) for F == 1, which is the global model's call -- the view keeps the caller's autograd graph.  The callers
+    are wrapped in ``_disarms_frames``."""
+    if cond.dim() == 2:
+      cond = cond[:, :, None]
+    if cond.dim() != 3 or cond.shape[0] != x.shape[0] or cond.shape[1] < 1:
+      raise ValueError('condition must have shape (batch, frames) or (batch, frames, n_cond)')
+    if not self.built:
+      self.build([tuple(x.shape), tuple(cond.shape)])
+    if cond.shape[2] != self._cond_inputs:
+      raise ValueError(f'condition must have {self._cond_inputs} channels (got {cond.shape[2]})')
+    F = int(cond.shape[1])
+    self._last_frames = F
+    if F == 1:
+      return x, cond[:, 0, :].contiguous()
+    self._arm_frames(F)          # T % F and hop % 32 are checked by the library against the T of the call, before any launch
+    return x, cond.contiguous()
+
+  def _arm_frames(self, frames):
+    frames = int(frames) if frames and frames > 1 else 0
+    # (an argument check may raise before the object has a plan)
+    if frames != getattr(self, '_frames_armed', 0) and getattr(self, '_plan', None) is not None:
+      _lib.check(_lib.lib().wn_plan_set_cond_frames(self._plan, frames))
+      self._frames_armed = frames
+
   # ------------------------------------------------------------------ call
+  @_disarms_frames
   def call(self, inputs, training=False):
     """src/model.py:213-239: probabilities (categorical) or linear mixture parameters.  (Reads the pass's range-guard
     float back -- one host sync -- and repeats the pass with the exact-fp32 kernels when an activation left the range
@@ -775,6 +918,7 @@ class WaveNet(torch.nn.Module):
     fn = L.wn_forward_training if training else L.wn_forward
     if training:
       self._train_gen += 1
+      self._last_train_frames = self._frames_armed
       # the Dropout layers are active (src/layers.py:195-196): a fresh mask per call, as in a training step
       self._arm_dropout()
 
@@ -803,6 +947,7 @@ class WaveNet(torch.nn.Module):
   def forward(self, inputs, training=False):
     return self.call(inputs, training=training)
 
+  @_disarms_frames
   def logits(self, inputs):
     """Pre-softmax head output (parity checks)."""
     x, cond = self._split_inputs(inputs)
@@ -830,7 +975,12 @@ class WaveNet(torch.nn.Module):
     block b (idx = b * (layers_per_block - 1) + i, as for 11); 14: XD[idx], the dropped copy of block input idx, which
     exists only with dropout > 0 (ValueError otherwise, as for every absent region)."""
     off, ln = C.c_int64(), C.c_int64()
-    _lib.check(_lib.lib().wn_debug_ws_region(self._plan, B, T, what, idx, C.byref(off), C.byref(ln)))
+    # (local conditioning: the regions behind the conditioning's lie where the pass with its F frames carved them)
+    try:
+      self._arm_frames(self._last_train_frames)
+      _lib.check(_lib.lib().wn_debug_ws_region(self._plan, B, T, what, idx, C.byref(off), C.byref(ln)))
+    finally:
+      self._arm_frames(0)
     return self._ws['train'][off.value:off.value + ln.value]
 
   def exact_fp32(self):
@@ -892,6 +1042,7 @@ class WaveNet(torch.nn.Module):
       w = w[:, None].expand(B, T)
     return w.reshape(B, T).contiguous()
 
+  @_disarms_frames
   def loss_and_grads(self, data, global_batch=None, n_replicas=None, want_pred=False, want_sample=False,
                      _loss_in_bucket=False, _between=None, sample_weight=None):
     """Forward + loss + backward of this replica's rows (src/model.py:319-335).
@@ -925,6 +1076,7 @@ class WaveNet(torch.nn.Module):
     self._log_kernels_once()
     ws = self._workspace('train', L.wn_plan_workspace_floats(self._plan, B, T, 1))
     self._train_gen += 1
+    self._last_train_frames = self._frames_armed
     # train_step keeps {loss, reg_loss} in the gradient bucket's tail (one all-reduce); other callers get their own tensor
     loss = self._grad_bucket[self.flat_params.numel():] if _loss_in_bucket else \
         torch.empty(3, dtype=torch.float32, device=self._device)
@@ -1025,7 +1177,10 @@ class WaveNet(torch.nn.Module):
       the few scalars between forward and backward (a second, tiny collective) and reads them early."""
     from . import dp
     if not self.built:
-      self._split_inputs(data)                          # Keras builds on the first call (the condition width fixes the shapes)
+      try:
+        self._split_inputs(data)                        # Keras builds on the first call (the condition width fixes the shapes)
+      finally:
+        self._arm_frames(0)                             # (a local condition arms its frames: loss_and_grads does so itself)
     compiled = self._metrics_from_compilation
     want_metric = len(compiled) > 0
     dev_metrics = [m for m in compiled if hasattr(m, 'update_state_device')][:self._TAIL_METRICS]
@@ -1065,6 +1220,7 @@ class WaveNet(torch.nn.Module):
     self._log_event.synchronize()
     return self._log_mirror.tolist(), dev_metrics, y_true, sample
 
+  @_disarms_frames
   def test_step(self, data, sample_weight=None):
     """src/model.py:362-391 (range guard as in train_step: a tripped pass is repeated with the exact-fp32 kernels and
     counted in ``test_guard_trips``).  ``sample_weight``: as in ``train_step`` -- loss = sum w l / global_batch, a compiled
@@ -1117,6 +1273,7 @@ class WaveNet(torch.nn.Module):
         metric.update_state(x[:, 1:, :], sample, **wkw)
     return {m.name: m.result() for m in self.metrics if m.name != 'reg_loss'}
 
+  @_disarms_frames
   def score(self, data, sample_weight=None, per_sample=False):
     """Per-utterance negative log-likelihoods of ``data`` in one evaluation pass.
 
@@ -1180,6 +1337,7 @@ class WaveNet(torch.nn.Module):
     return self._ws['fwd'][off.value:off.value + ln.value]
 
   # ------------------------------------------------------------------ autograd
+  @_disarms_frames
   def differentiable(self, inputs, training=False, output='probs'):
     """The network as one ``torch.autograd`` node: returns ``(B, T, C_out)`` with a ``grad_fn``, for losses the training
     step does not have built in (label smoothing, distillation, a loss on the expected sample, a gradient
@@ -1340,7 +1498,7 @@ class WaveNet(torch.nn.Module):
 
   # ------------------------------------------------------------------ generation
   def generate(self, length, batch_size: int = 1, condition=None, sample=None,
-               use_queues=False, deterministic=False, temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None):
+               use_queues=False, deterministic=False, temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None, hop=None):
     """src/model.py:258-307 (intended semantics; the reference's kwarg / rank bugs are not
     reproduced).  Returns (B, length, 1).
     temperature / top_k / seed / top_p (additions) as in sample_waveform; an int seed is the Philox key of
@@ -1351,6 +1509,16 @@ class WaveNet(torch.nn.Module):
     of the window the scalar call with seed[b] draws.  stream: None, or B ints in [0, 2**63) -- utterance b draws from
     the Philox counter row stream[b] instead of b, so a request keeps its draws whichever batch slot it lands in
     (requires `sample`).  deterministic stays one flag for the call."""
+    condition, frames, hop = self._local_frames(condition, hop, use_queues, length)
+    if frames is not None:
+      # a frame schedule (local conditioning): the sequence as a session, split at the frame boundaries -- the chunks of a
+      # sequence, concatenated, are the one call bit for bit (DESIGN.md section 23)
+      session = self.generation_session(batch_size=batch_size, condition=frames, sample=sample, use_queues=use_queues,
+                                        deterministic=deterministic, temperature=temperature, top_k=top_k, seed=seed,
+                                        top_p=top_p, stream=stream, hop=hop)
+      if int(length) < 1:
+        return torch.empty(session._B, 0, 1, dtype=torch.float32, device=self._device)
+      return session.generate(int(length))
     sampling, condition, sample, batch_size = self._generation_args(batch_size, condition, sample, deterministic,
                                                                     temperature, top_k, seed, top_p, stream)
     L = _lib.lib()
@@ -1380,6 +1548,34 @@ class WaveNet(torch.nn.Module):
         with self.exact_fp32():
           run()
     return out
+
+  def _local_frames(self, condition, hop, use_queues, length=None):
+    """Local conditioning in generation: condition (B, F) or (B, F, Cin) and hop, the samples per
+    frame.  Returns (the priming pass's condition = frame 0 as (B, Cin), frames (B, F, Cin) or None, hop): None is a held
+    condition with no end (F == 1 without hop).  Other models: (condition, None, None)."""
+    if self.conditioning != 'local' or condition is None:
+      if hop is not None:
+        raise ValueError('hop belongs to conditioning=\'local\' with a condition of frames')
+      return condition, None, None
+    condition = torch.as_tensor(condition, dtype=torch.float32, device=self._device)
+    if condition.dim() == 2:
+      condition = condition[:, :, None]
+    if condition.dim() != 3 or condition.shape[1] < 1:
+      raise ValueError('condition must have shape (batch, frames) or (batch, frames, n_cond)')
+    F = int(condition.shape[1])
+    first = condition[:, 0, :].contiguous()
+    if hop is None:
+      if F > 1:
+        raise ValueError(f'hop is required with {F} condition frames: the samples generated per frame')
+      return first, None, None
+    if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or hop < 1:
+      raise ValueError(f'hop must be an int >= 1 (got {hop!r})')
+    if F > 1 and not use_queues:
+      raise NotImplementedError('a frame schedule needs use_queues=True: the reference\'s sliding window re-upsamples the whole '
+                                'condition onto the window at every step, which defines nothing usable')
+    if length is not None and int(length) > F * int(hop):
+      raise ValueError(f'length {int(length)} runs past the {F} condition frames of hop {int(hop)} ({F * int(hop)} samples)')
+    return first, condition.contiguous(), int(hop)
 
   def _generation_args(self, batch_size, condition, sample, deterministic, temperature, top_k, seed, top_p, stream=None):
     """The argument handling of generate and generation_session: the sampling controls checked, condition and sample on
@@ -1428,7 +1624,7 @@ class WaveNet(torch.nn.Module):
     return sampling, condition, sample, batch_size
 
   def generation_session(self, batch_size: int = 1, condition=None, sample=None, use_queues=False, deterministic=False,
-                         temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None, start=0, own_clock=False):
+                         temperature=1.0, top_k=0, seed=None, top_p=1.0, stream=None, start=0, own_clock=False, hop=None):
     """A sequence made in pieces: the arguments of generate without `length`, with the same checks (per-utterance
     controls and `stream` included: the session keeps the device table of its rows).  The chunks of
     session.generate(n), concatenated, are bit for bit generate(total, same arguments).  The
@@ -1438,18 +1634,22 @@ class WaveNet(torch.nn.Module):
     Philox counter (stream, t), so a sequence begun at `start` draws what a request admitted at that position draws
     (GenerationSession.admit).  start > 0 needs per-row controls: passing stream= is enough.
     own_clock=True: every row counts from `start` -- sample t is drawn from counter (stream, t - start),
-    so the session is bit for bit the session with start=0, stochastic draws included.  Needs per-row controls too."""
+    so the session is bit for bit the session with start=0, stochastic draws included.  Needs per-row controls too.
+    hop (conditioning='local'): the samples per condition frame; session.generate splits its chunks at
+    the frame boundaries and raises ValueError at the chunk that would run past the last frame."""
     if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or start < 0:
       raise ValueError(f'start must be an int >= 0 (got {start!r})')
     if not isinstance(own_clock, bool):
       raise ValueError(f'own_clock must be a bool (got {own_clock!r})')
+    condition, frames, hop = self._local_frames(condition, hop, use_queues)
     sampling, condition, window, batch_size = self._generation_args(batch_size, condition, sample, deterministic,
                                                                     temperature, top_k, seed, top_p, stream)
     if start > 0 and not isinstance(sampling, _RowControls):
       raise ValueError('start > 0 needs per-row sampling controls: pass stream= (one Philox stream id per utterance)')
     if own_clock and not isinstance(sampling, _RowControls):
       raise RuntimeError('generation session: own_clock needs per-row controls (create the session with stream=)')
-    return GenerationSession(self, sampling, condition, window, batch_size, use_queues, deterministic, int(start), own_clock)
+    return GenerationSession(self, sampling, condition, window, batch_size, use_queues, deterministic, int(start), own_clock,
+                             frames, hop)
 
   def generate_stream(self, length, chunk, **kwargs):
     """Generator over a generation_session(**kwargs): yields (B, min(chunk, rest), 1) tensors until `length` samples are

@@ -80,10 +80,13 @@ class ModelSpec:
       out.append((f'final{i}/kernel', (1, cprev, ch)))
       out.append((f'final{i}/bias', (ch,)))
       cprev = ch
-    if self.conditioning == 'global':
+    if self.conditioning is not None:
+      # global: a Dense stack (src/model.py:142-148); local: 1x1 Conv1D layers over the frames (src/model.py:131-140,
+      # `Conv1D(kernel=1, ...)` read as kernel_size=1) -- the same flat element order, one more leading axis
+      lead = (1,) if self.conditioning == 'local' else ()
       cin = cond_inputs
       for j, w in enumerate(self.mapping_layers):
-        out.append((f'mapping{j}/kernel', (cin, w)))
+        out.append((f'mapping{j}/kernel', lead + (cin, w)))
         out.append((f'mapping{j}/bias', (w,)))
         cin = w
     return out
@@ -128,9 +131,6 @@ def validate(kernel_size, channels, blocks, layers_per_block, activation, condit
     if act not in SUPPORTED_ACTIVATIONS:
       raise NotImplementedError(f'activation {act!r} is not supported by the gfx950 kernels '
                                 f'(supported: {SUPPORTED_ACTIVATIONS})')
-  if conditioning == 'local':
-    # broken in the reference itself (Conv1D(kernel=1, ...) src/model.py:136-137; README "not tested")
-    raise NotImplementedError('local conditioning is not implemented')
   return ModelSpec(kernel_size, channels, blocks, layers_per_block, activation, conditioning,
                    list(mapping_layers), mapping_activation, float(dropout), dilation_bound,
                    num_mixtures, sampling_function, bits, skip_channels, dilation_channels,
