@@ -1,4 +1,4 @@
-"""Adam(use_ema=True): the exponential moving average of the weights, written by the Adam launch (wn_adam_ema_kernel),
+"""Adam(use_ema=True): the exponential moving average of the weights, written by the Adam launch (wn_adam_kernel<true, false, false>),
 and WaveNet.averaged_weights(), the scope that runs the model's passes on it.
 
 The definition, with t the 1-based iteration, after the parameter update of step t:

@@ -3,8 +3,10 @@
 //   one launch   wn_clip_kernel as shipped: one workgroup per tensor reduces and rescales its own tensor
 //   two launches wn_sumsq_kernel (one workgroup per tensor), then a rescale spread over 32 workgroups per tensor
 // Every tensor gets norm 5 before every call, so each call rescales everything (the case of a real step: 186 of 188).
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=on tools/clip_probe.hip wavenets_amd/csrc/wn_error.cpp -o tools/clip_probe
-#include "../wavenets_amd/csrc/wn_elem.hip"
+// The kernels come from wn_optim.hip, whose entry points need the plan: link against the built library.
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=on tools/clip_probe.hip -o tools/clip_probe \
+//         -Lwavenets_amd -lwn_hip -Wl,-rpath,$PWD/wavenets_amd
+#include "../wavenets_amd/csrc/wn_optim.hip"
 #include <cstdio>
 #include <vector>
 

@@ -9,7 +9,7 @@ moments and data are shared; `reference` is Adam(clipnorm=1.0), the launch of th
                                                                   no wn_adam_step_ext to bind) and without, alternating
                                                                   processes in one session on one box
   rocprofv3 --kernel-trace --stats -d DIR -- python tools/time_adam_options.py --profile
-                                                                  a few steps of each: wn_adam_kernel / wn_adam_ext_kernel
+                                                                  a few steps of each: the instantiations of wn_adam_kernel
 """
 import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -4,7 +4,7 @@ both settings (the average observes: it never feeds back into the step).
 
   python tools/time_ema.py [--steps 40] [--runs 3]                step time, flag off / on alternated, `runs` blocks each
   rocprofv3 --kernel-trace --stats -d DIR -- python tools/time_ema.py --profile
-                                                                  a few steps of each: wn_adam_kernel / wn_adam_ema_kernel
+                                                                  a few steps of each: wn_adam_kernel<false,false,false> / <true,false,false>
 """
 import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,5 @@
-// Elementwise, optimizer and small dense kernels of the WaveNet hot path (gfx950); losses: wn_loss.hip, samplers:
-// wn_sample.hip.  References: quantiser src/model.py:151-153; mu-law src/utils.py:34-35; inverse
+// Elementwise and small dense kernels of the WaveNet hot path (gfx950); losses: wn_loss.hip, samplers: wn_sample.hip,
+// optimizer: wn_optim.hip.  References: quantiser src/model.py:151-153; mu-law src/utils.py:34-35; inverse
 // src/callbacks.py:126-131.
 #include <algorithm>
 
@@ -134,281 +134,6 @@ __global__ void wn_inv_mulaw_kernel(const float* y, float* x, int64_t n) {
 int wn_launch_inv_mulaw(const float* y, float* x, int64_t n, hipStream_t s) {
   if (n <= 0) return WN_OK;
   hipLaunchKernelGGL(wn_inv_mulaw_kernel, dim3(wn_blocks(n)), dim3(256), 0, s, y, x, n);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// optimizer: per-tensor clipnorm + Keras Adam  (train.py:225-226, src/model.py:336)
-__global__ void wn_sumsq_kernel(const float* g, const WnTensorDesc* table, float* norms2) {
-  __shared__ double sm[256];
-  const WnTensorDesc d = table[blockIdx.x];
-  const float* p = g + d.off;
-  // four independent chains: a single one ran at one memory round trip per element (63 us for 1.25 M values)
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  int64_t i = threadIdx.x;
-  for (; i + 3 * 256 < d.len; i += 4 * 256) {
-    const float v0 = p[i], v1 = p[i + 256], v2 = p[i + 512], v3 = p[i + 768];
-    a0 += (double)v0 * (double)v0; a1 += (double)v1 * (double)v1;
-    a2 += (double)v2 * (double)v2; a3 += (double)v3 * (double)v3;
-  }
-  for (; i < d.len; i += 256) a0 += (double)p[i] * (double)p[i];
-  const double acc = (a0 + a1) + (a2 + a3);
-  sm[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) norms2[blockIdx.x] = (float)sm[0];
-}
-int wn_launch_sumsq(const float* g, const WnTensorDesc* d_table, int n, float* norms2, hipStream_t s) {
-  if (n <= 0) return WN_OK;
-  hipLaunchKernelGGL(wn_sumsq_kernel, dim3(n), dim3(256), 0, s, g, d_table, norms2);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// Per-replica clipnorm ahead of the data-parallel all-reduce (Adam(clip_before_reduce=True)): in place, tensor t
-// becomes g_t * clipnorm / max(||g_t||, clipnorm).  One workgroup of 1024 threads owns one tensor: it reduces the
-// squared norm in double (as wn_sumsq_kernel does), then rescales the same <= 256 KiB, which it has just pulled into
-// L2 -- no sumsq launch, no norms round trip, no scale launch.  A tensor inside the bound (norm 0 included) has scale
-// exactly 1.0f and is not written at all.  The body moves float4; the scalar head and tail keep every access inside
-// [off, off + len), whatever the alignment of the tensor: the step's scalars sit right behind the last gradient.
-#define WN_CLIP_THREADS 1024
-__global__ void __launch_bounds__(WN_CLIP_THREADS)
-wn_clip_kernel(float* g, const WnTensorDesc* table, float clipnorm, float* norms2) {
-  __shared__ double sm[WN_CLIP_THREADS / 64];
-  __shared__ float sm_scale;
-  const WnTensorDesc d = table[blockIdx.x];
-  float* p = g + d.off;
-  const int tid = threadIdx.x;
-  int64_t head = (int64_t)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2;    // floats up to 16-byte alignment
-  if (head > d.len) head = d.len;
-  const int64_t nvec = (d.len - head) >> 2;
-  const int64_t tail = head + 4 * nvec;
-  float4* pv = reinterpret_cast<float4*>(p + head);
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  int64_t i = tid;
-  for (; i + WN_CLIP_THREADS < nvec; i += 2 * WN_CLIP_THREADS) {       // two loads in flight per thread
-    const float4 x = pv[i], y = pv[i + WN_CLIP_THREADS];
-    a0 += (double)x.x * (double)x.x; a1 += (double)x.y * (double)x.y;
-    a2 += (double)x.z * (double)x.z; a3 += (double)x.w * (double)x.w;
-    a0 += (double)y.x * (double)y.x; a1 += (double)y.y * (double)y.y;
-    a2 += (double)y.z * (double)y.z; a3 += (double)y.w * (double)y.w;
-  }
-  for (; i < nvec; i += WN_CLIP_THREADS) {
-    const float4 x = pv[i];
-    a0 += (double)x.x * (double)x.x; a1 += (double)x.y * (double)x.y;
-    a2 += (double)x.z * (double)x.z; a3 += (double)x.w * (double)x.w;
-  }
-  if (tid < head) a0 += (double)p[tid] * (double)p[tid];
-  if (tail + tid < d.len) a1 += (double)p[tail + tid] * (double)p[tail + tid];
-  double acc = (a0 + a1) + (a2 + a3);
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if ((tid & 63) == 0) sm[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double n2 = 0.0;
-    for (int w = 0; w < WN_CLIP_THREADS / 64; ++w) n2 += sm[w];
-    const float n2f = (float)n2;
-    norms2[blockIdx.x] = n2f;
-    sm_scale = clipnorm / fmaxf(sqrtf(n2f), clipnorm);     // tf.clip_by_norm, the expression of wn_adam_kernel
-  }
-  __syncthreads();
-  const float scale = sm_scale;
-  if (scale == 1.0f) return;       // uniform: inside the bound, the tensor stays bit-identical
-  for (i = tid; i < nvec; i += WN_CLIP_THREADS) {
-    float4 x = pv[i];
-    x.x *= scale; x.y *= scale; x.z *= scale; x.w *= scale;
-    pv[i] = x;
-  }
-  if (tid < head) p[tid] *= scale;
-  if (tail + tid < d.len) p[tail + tid] *= scale;
-}
-int wn_launch_clip(float* g, const WnTensorDesc* d_table, int n, float clipnorm, float* norms2, hipStream_t s) {
-  if (n <= 0) return WN_OK;
-  hipLaunchKernelGGL(wn_clip_kernel, dim3(n), dim3(WN_CLIP_THREADS), 0, s, g, d_table, clipnorm, norms2);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-__global__ void wn_adam_kernel(float* p, const float* g, float* m, float* v, const WnTensorDesc* table,
-                               const float* norms2, float clipnorm, float alpha, float beta1,
-                               float beta2, float eps, const float* skip_flag) {
-  if (skip_flag && *skip_flag != 0.f) return;     // range guard tripped: the step is redone in exact fp32 (uniform)
-  const WnTensorDesc d = table[blockIdx.y];
-  float scale = 1.0f;
-  if (clipnorm > 0.f) {
-    const float nrm = sqrtf(norms2[blockIdx.y]);
-    scale = clipnorm / fmaxf(nrm, clipnorm);     // tf.clip_by_norm
-  }
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.len;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t k = d.off + i;
-    const float gi = g[k] * scale;
-    const float mi = m[k] + (gi - m[k]) * (1.0f - beta1);
-    const float vi = v[k] + (gi * gi - v[k]) * (1.0f - beta2);
-    m[k] = mi;
-    v[k] = vi;
-    p[k] = p[k] - alpha * mi / (sqrtf(vi) + eps);
-  }
-}
-int wn_launch_adam(float* p, const float* g, float* m, float* v, const WnTensorDesc* d_table, int n,
-                   const float* norms2, float clipnorm, float alpha, float beta1, float beta2,
-                   float eps, const float* skip_flag, hipStream_t s) {
-  if (n <= 0) return WN_OK;
-  hipLaunchKernelGGL(wn_adam_kernel, dim3(32, n), dim3(256), 0, s, p, g, m, v, d_table, norms2,
-                     clipnorm, alpha, beta1, beta2, eps, skip_flag);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// Adam(use_ema=True): the same update with the exponential moving average of the weights as one more stream of the same
-// launch -- a sibling of wn_adam_kernel picked by the host, so the default step runs the kernel above unchanged.  g, m, v
-// and p are evaluated with the expressions of wn_adam_kernel (the average observes, it never feeds back, unless
-// ``overwrite`` asks for p = a); a follows in the form m and v use: a + (p - a) * (1 - momentum), fp32.  ``first`` (step 1)
-// copies p instead: a multiply by zero would keep a NaN / inf of the initial average.  9 floats moved per parameter, 7
-// above; scalar accesses, since tensors start at arbitrary float offsets.
-__global__ void wn_adam_ema_kernel(float* p, const float* g, float* m, float* v, float* a, const WnTensorDesc* table,
-                                   const float* norms2, float clipnorm, float alpha, float beta1,
-                                   float beta2, float eps, float momentum, int first, int overwrite,
-                                   const float* skip_flag) {
-  if (skip_flag && *skip_flag != 0.f) return;     // range guard tripped: a stays put together with p, m, v (uniform)
-  const WnTensorDesc d = table[blockIdx.y];
-  float scale = 1.0f;
-  if (clipnorm > 0.f) {
-    const float nrm = sqrtf(norms2[blockIdx.y]);
-    scale = clipnorm / fmaxf(nrm, clipnorm);     // tf.clip_by_norm
-  }
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.len;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t k = d.off + i;
-    const float gi = g[k] * scale;
-    const float mi = m[k] + (gi - m[k]) * (1.0f - beta1);
-    const float vi = v[k] + (gi * gi - v[k]) * (1.0f - beta2);
-    m[k] = mi;
-    v[k] = vi;
-    const float pi = p[k] - alpha * mi / (sqrtf(vi) + eps);
-    const float ai = first ? pi : a[k] + (pi - a[k]) * (1.0f - momentum);
-    a[k] = ai;
-    p[k] = overwrite ? ai : pi;
-  }
-}
-int wn_launch_adam_ema(float* p, const float* g, float* m, float* v, float* a, const WnTensorDesc* d_table, int n,
-                       const float* norms2, float clipnorm, float alpha, float beta1, float beta2,
-                       float eps, float momentum, int first, int overwrite, const float* skip_flag, hipStream_t s) {
-  if (n <= 0) return WN_OK;
-  hipLaunchKernelGGL(wn_adam_ema_kernel, dim3(32, n), dim3(256), 0, s, p, g, m, v, a, d_table, norms2,
-                     clipnorm, alpha, beta1, beta2, eps, momentum, first, overwrite, skip_flag);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// Adam with the other Keras keywords -- global_clipnorm, clipvalue, weight_decay, amsgrad -- as further streams of the
-// same launch: a third sibling, picked by the host only when one of them is on, so the two kernels above run unchanged
-// for everybody else.  Clip mode, clip value, decay and the decay table are uniform per launch; EMA and AMSGRAD are
-// template arguments since each adds a stream (a: 2 floats per parameter, vhat: 2 more).
-//   global norm: norms2 holds the per-tensor sums of wn_sumsq_kernel; every workgroup adds the n floats itself, in double
-//     and in tensor order (uniform addresses: the same bits everywhere, no launch of its own), N = sqrtf((float)sum),
-//     scale = c / fmaxf(N, c) + (N - N): the last term is NaN for a non-finite norm and poisons the step as Keras does.
-//   value: g' = g < -c ? -c : (g > c ? c : g); both comparisons are false for a NaN, which therefore stays.
-//   decay: p0 = p - (p * wd) * lr on the tensors whose flag is set (no table: all), ahead of the update, under the
-//     same skip flag; it never enters g, m or v.
-//   amsgrad: vhat = fmaxf(vhat, v) feeds the denominator; v keeps its own recursion.
-// m, v, p and a in the expressions of the two kernels above.
-__device__ __forceinline__ float wn_global_clip_scale(const float* norms2, int n, float c) {
-  double n2 = 0.0;
-  for (int t = 0; t < n; ++t) n2 += (double)norms2[t];
-  const float N = sqrtf((float)n2);
-  return c / fmaxf(N, c) + (N - N);
-}
-
-template <bool EMA, bool AMSGRAD>
-__global__ void wn_adam_ext_kernel(float* p, const float* g, float* m, float* v, float* vhat, float* a,
-                                   const WnTensorDesc* table, int n, const float* norms2, int clip_mode, float clip,
-                                   float lr, float wd, const int32_t* decay_flags, float alpha, float beta1, float beta2,
-                                   float eps, float momentum, int first, int overwrite, const float* skip_flag) {
-  if (skip_flag && *skip_flag != 0.f) return;     // range guard tripped: nothing moves, the decay included (uniform)
-  const WnTensorDesc d = table[blockIdx.y];
-  float scale = 1.0f;
-  if (clip_mode == WN_CLIP_NORM) {
-    const float nrm = sqrtf(norms2[blockIdx.y]);
-    scale = clip / fmaxf(nrm, clip);     // tf.clip_by_norm
-  } else if (clip_mode == WN_CLIP_GLOBAL_NORM) {
-    scale = wn_global_clip_scale(norms2, n, clip);
-  }
-  const bool by_value = clip_mode == WN_CLIP_VALUE;
-  const bool decays = wd > 0.f && (!decay_flags || decay_flags[blockIdx.y] != 0);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.len;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t k = d.off + i;
-    const float gr = g[k];
-    const float gi = by_value ? (gr < -clip ? -clip : (gr > clip ? clip : gr)) : gr * scale;
-    const float mi = m[k] + (gi - m[k]) * (1.0f - beta1);
-    const float vi = v[k] + (gi * gi - v[k]) * (1.0f - beta2);
-    m[k] = mi;
-    v[k] = vi;
-    float den = vi;
-    if (AMSGRAD) {
-      den = fmaxf(vhat[k], vi);
-      vhat[k] = den;
-    }
-    const float p0 = decays ? p[k] - (p[k] * wd) * lr : p[k];
-    const float pi = p0 - alpha * mi / (sqrtf(den) + eps);
-    if (EMA) {
-      const float ai = first ? pi : a[k] + (pi - a[k]) * (1.0f - momentum);
-      a[k] = ai;
-      p[k] = overwrite ? ai : pi;
-    } else {
-      p[k] = pi;
-    }
-  }
-}
-int wn_launch_adam_ext(float* p, const float* g, float* m, float* v, float* vhat, float* a, const WnTensorDesc* d_table,
-                       int n, const float* norms2, int clip_mode, float clip, float lr, float wd, const int32_t* decay_flags,
-                       float alpha, float beta1, float beta2, float eps, float momentum, int first, int overwrite,
-                       const float* skip_flag, hipStream_t s) {
-  if (n <= 0) return WN_OK;
-  auto k = a ? (vhat ? wn_adam_ext_kernel<true, true> : wn_adam_ext_kernel<true, false>)
-             : (vhat ? wn_adam_ext_kernel<false, true> : wn_adam_ext_kernel<false, false>);
-  hipLaunchKernelGGL(k, dim3(32, n), dim3(256), 0, s, p, g, m, v, vhat, a, d_table, n, norms2, clip_mode, clip, lr, wd,
-                     decay_flags, alpha, beta1, beta2, eps, momentum, first, overwrite, skip_flag);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-
-// The two new clips ahead of the data-parallel all-reduce (Adam(clip_before_reduce=True)), in place on the replica's own
-// gradient.  Scalar accesses over the tensors of the table, as the Adam kernels above: every access lies inside
-// [off, off + len) of a tensor, so nothing behind the last gradient (the step's scalars) is read or written.  The global
-// form runs behind wn_sumsq_kernel and writes nothing when the gradient is inside the bound (scale exactly 1.0f); the
-// value form writes only the elements it clamps.
-__global__ void wn_scale_global_kernel(float* g, const WnTensorDesc* table, int n, const float* norms2, float clip) {
-  const float scale = wn_global_clip_scale(norms2, n, clip);
-  if (scale == 1.0f) return;       // uniform: the whole gradient stays bit-identical
-  const WnTensorDesc d = table[blockIdx.y];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.len;
-       i += (int64_t)gridDim.x * blockDim.x)
-    g[d.off + i] *= scale;
-}
-__global__ void wn_clip_value_kernel(float* g, const WnTensorDesc* table, float clip) {
-  const WnTensorDesc d = table[blockIdx.y];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.len;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float gr = g[d.off + i];
-    if (gr < -clip) g[d.off + i] = -clip;
-    else if (gr > clip) g[d.off + i] = clip;
-  }
-}
-int wn_launch_scale_global(float* g, const WnTensorDesc* d_table, int n, const float* norms2, float clip, hipStream_t s) {
-  if (n <= 0) return WN_OK;
-  hipLaunchKernelGGL(wn_scale_global_kernel, dim3(32, n), dim3(256), 0, s, g, d_table, n, norms2, clip);
-  WN_HIP_CHECK(hipGetLastError());
-  return WN_OK;
-}
-int wn_launch_clip_value(float* g, const WnTensorDesc* d_table, int n, float clip, hipStream_t s) {
-  if (n <= 0) return WN_OK;
-  hipLaunchKernelGGL(wn_clip_value_kernel, dim3(32, n), dim3(256), 0, s, g, d_table, clip);
   WN_HIP_CHECK(hipGetLastError());
   return WN_OK;
 }

@@ -485,20 +485,20 @@ int wn_launch_sumsq(const float* g, const WnTensorDesc* d_table, int n, float* n
 int wn_launch_clip(float* g, const WnTensorDesc* d_table, int n, float clipnorm, float* norms2, hipStream_t s);
 int wn_launch_axpy_table(float* y, const float* x, const WnTensorDesc* d_table, int n, float coef,
                          hipStream_t s);
-int wn_launch_adam(float* p, const float* g, float* m, float* v, const WnTensorDesc* d_table, int n,
-                   const float* norms2, float clipnorm, float alpha, float beta1, float beta2,
-                   float eps, const float* skip_flag, hipStream_t s);
-// the same step with the weights' exponential moving average a as one more stream (Adam(use_ema=True)); first: a = p
-int wn_launch_adam_ema(float* p, const float* g, float* m, float* v, float* a, const WnTensorDesc* d_table, int n,
-                       const float* norms2, float clipnorm, float alpha, float beta1, float beta2,
-                       float eps, float momentum, int first, int overwrite, const float* skip_flag, hipStream_t s);
-// the step with the other Keras keywords: clip_mode one WN_CLIP_* with its value clip (the two norm modes read norms2, the
-// global one all n of them), decay p -= (p * wd) * lr where decay_flags[t] != 0 (null: everywhere), vhat non-null =
-// amsgrad, a non-null = the moving average of wn_launch_adam_ema
-int wn_launch_adam_ext(float* p, const float* g, float* m, float* v, float* vhat, float* a, const WnTensorDesc* d_table,
-                       int n, const float* norms2, int clip_mode, float clip, float lr, float wd, const int32_t* decay_flags,
-                       float alpha, float beta1, float beta2, float eps, float momentum, int first, int overwrite,
-                       const float* skip_flag, hipStream_t s);
+// One Adam step over the tensors of the table (wn_optim.hip states every expression): clip_mode one WN_CLIP_* with its value
+// clip (the two norm modes read norms2, the global one all n of them), decay p -= (p * wd) * lr where decay_flags[t] != 0
+// (null: everywhere), vhat non-null = amsgrad, a non-null = the weights' exponential moving average as one more stream
+// (first: a = p; overwrite: p = a), a raised *skip_flag (null: never) = nothing moves
+struct WnAdamArgs {
+  float* p; const float* g; float* m; float* v; float* vhat; float* a;
+  const WnTensorDesc* table; int n;
+  const float* norms2; int clip_mode; float clip;
+  float lr, wd; const int32_t* decay_flags;
+  float alpha, beta1, beta2, eps;
+  float momentum; int first, overwrite;
+  const float* skip_flag;
+};
+int wn_launch_adam(const WnAdamArgs& x, hipStream_t s);
 // in place, inside the tensors of the table only: g *= c / max(N, c) + (N - N) from the n sums of wn_launch_sumsq (no
 // write when the factor is 1.0f); g clamped to [-c, c], NaN kept (only clamped elements are written)
 int wn_launch_scale_global(float* g, const WnTensorDesc* d_table, int n, const float* norms2, float clip, hipStream_t s);

@@ -1,7 +1,7 @@
 // Internal interface of the plan / orchestration translation units behind the C-ABI of include/wn_hip.h
 // (wn_plan.hip: plan + workspace layout; wn_block.hip: one residual block; wn_forward.hip: the model's forward pass and
-// loss; wn_train.hip: backward pass, weight gradients, optimizer; wn_generate.hip: generation; wn_cabi_ops.hip: the
-// elementwise entry points).  Host-side only.
+// loss; wn_train.hip: backward pass, weight gradients; wn_optim.hip: optimizer; wn_generate.hip: generation;
+// wn_cabi_ops.hip: the elementwise entry points).  Host-side only.
 #pragma once
 #include <math.h>
 #include <stdlib.h>

@@ -1,5 +1,5 @@
-// The gradient half of WaveNet.train_step (src/model.py:319-336): backward-data chain, deferred weight gradients, and the
-// optimizer step (Adam with per-tensor clipnorm, train.py:225-226).
+// The gradient half of WaveNet.train_step (src/model.py:319-336): backward-data chain and deferred weight gradients (the
+// optimizer step: wn_optim.hip).
 #include "wn_plan_internal.h"
 
 namespace {
@@ -777,125 +777,4 @@ extern "C" int wn_vjp(wn_plan* p, const float* params, const float* x, const flo
                                     g_kind == 0 && p->c.head == WN_HEAD_CATEGORICAL, workspace + c.L.GF.back(), c.am_GF(c.nf - 1), s);
   if (rc) return rc;
   return c.backward_from_logits();
-}
-
-extern "C" int wn_adam_step_guarded(wn_plan* p, float* params, const float* grads, float* m, float* v, int64_t step,
-                                    float lr, float beta1, float beta2, float eps, float clipnorm, float* scratch,
-                                    const float* skip_flag, void* stream) {
-  if (!p || !params || !grads || !m || !v || !scratch || step < 1) { wn_set_error("adam_step: bad arguments"); return WN_E_INVALID; }
-  hipStream_t s = (hipStream_t)stream;
-  int rc = ensure_device_tables(p);
-  if (rc) return rc;
-  const int n = (int)p->tdesc.size();
-  if (clipnorm > 0.f) {
-    rc = wn_launch_sumsq(grads, p->d_tdesc, n, scratch, s);
-    if (rc) return rc;
-  }
-  const double alpha = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
-  return wn_launch_adam(params, grads, m, v, p->d_tdesc, n, scratch, clipnorm, (float)alpha, beta1, beta2, eps, skip_flag, s);
-}
-
-extern "C" int wn_adam_step_ema(wn_plan* p, float* params, const float* grads, float* m, float* v, float* ema, int64_t step,
-                                float lr, float beta1, float beta2, float eps, float clipnorm, float ema_momentum,
-                                int32_t ema_overwrite, float* scratch, const float* skip_flag, void* stream) {
-  if (!p || !params || !grads || !m || !v || !ema || !scratch || step < 1) { wn_set_error("adam_step_ema: bad arguments"); return WN_E_INVALID; }
-  if (!std::isfinite(ema_momentum) || ema_momentum < 0.f || ema_momentum > 1.f) {
-    wn_set_error("adam_step_ema: ema_momentum must be finite and in [0, 1] (got %g)", (double)ema_momentum);
-    return WN_E_INVALID;
-  }
-  if (ema_overwrite != 0 && ema_overwrite != 1) { wn_set_error("adam_step_ema: ema_overwrite must be 0 or 1 (got %d)", (int)ema_overwrite); return WN_E_INVALID; }
-  hipStream_t s = (hipStream_t)stream;
-  int rc = ensure_device_tables(p);
-  if (rc) return rc;
-  const int n = (int)p->tdesc.size();
-  if (clipnorm > 0.f) {
-    rc = wn_launch_sumsq(grads, p->d_tdesc, n, scratch, s);
-    if (rc) return rc;
-  }
-  const double alpha = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
-  return wn_launch_adam_ema(params, grads, m, v, ema, p->d_tdesc, n, scratch, clipnorm, (float)alpha, beta1, beta2, eps,
-                            ema_momentum, step == 1 ? 1 : 0, (int)ema_overwrite, skip_flag, s);
-}
-
-extern "C" int wn_clip_gradients(wn_plan* p, float* grads, float clipnorm, float* scratch, void* stream) {
-  if (!p || !grads || !scratch) { wn_set_error("clip_gradients: bad arguments"); return WN_E_INVALID; }
-  if (!(clipnorm > 0.f) || !std::isfinite(clipnorm)) { wn_set_error("clip_gradients: clipnorm must be finite and > 0 (got %g)", (double)clipnorm); return WN_E_INVALID; }
-  int rc = ensure_device_tables(p);
-  if (rc) return rc;
-  return wn_launch_clip(grads, p->d_tdesc, (int)p->tdesc.size(), clipnorm, scratch, (hipStream_t)stream);
-}
-
-// one WN_CLIP_* bit with a finite value > 0 (or, where allowed, no bit at all)
-static int check_clip(const char* who, int32_t mode, float clip, bool none_ok) {
-  if (mode == WN_CLIP_NONE && none_ok) return WN_OK;
-  if (mode != WN_CLIP_NORM && mode != WN_CLIP_GLOBAL_NORM && mode != WN_CLIP_VALUE) {
-    wn_set_error("%s: clip_mode must be exactly one of WN_CLIP_NORM, WN_CLIP_GLOBAL_NORM, WN_CLIP_VALUE%s (got %d): only one "
-                 "of clipnorm, clipvalue and global_clipnorm can be set", who, none_ok ? " or WN_CLIP_NONE" : "", (int)mode);
-    return WN_E_INVALID;
-  }
-  if (!(clip > 0.f) || !std::isfinite(clip)) {
-    wn_set_error("%s: clip must be finite and > 0 (got %g)", who, (double)clip);
-    return WN_E_INVALID;
-  }
-  return WN_OK;
-}
-
-extern "C" int wn_adam_step_ext(wn_plan* p, float* params, const float* grads, float* m, float* v, float* vhat, float* ema,
-                                int64_t step, const wn_adam_options* o, float* scratch, const float* skip_flag,
-                                void* stream) {
-  const char* null_arg = !p ? "plan" : !params ? "params" : !grads ? "grads" : !m ? "m" : !v ? "v" : !o ? "options"
-                         : !scratch ? "scratch" : nullptr;
-  if (null_arg) { wn_set_error("adam_step_ext: %s is NULL", null_arg); return WN_E_INVALID; }
-  if (step < 1) { wn_set_error("adam_step_ext: step must be >= 1 (got %lld)", (long long)step); return WN_E_INVALID; }
-  int rc = check_clip("adam_step_ext", o->clip_mode, o->clip, true);
-  if (rc) return rc;
-  if (!(o->weight_decay >= 0.f) || !std::isfinite(o->weight_decay)) {
-    wn_set_error("adam_step_ext: weight_decay must be finite and >= 0 (got %g)", (double)o->weight_decay);
-    return WN_E_INVALID;
-  }
-  if (o->amsgrad != 0 && o->amsgrad != 1) { wn_set_error("adam_step_ext: amsgrad must be 0 or 1 (got %d)", (int)o->amsgrad); return WN_E_INVALID; }
-  if (o->amsgrad && !vhat) { wn_set_error("adam_step_ext: amsgrad without vhat (vhat is NULL)"); return WN_E_INVALID; }
-  if (!std::isfinite(o->ema_momentum) || o->ema_momentum < 0.f || o->ema_momentum > 1.f) {
-    wn_set_error("adam_step_ext: ema_momentum must be finite and in [0, 1] (got %g)", (double)o->ema_momentum);
-    return WN_E_INVALID;
-  }
-  if (o->ema_overwrite != 0 && o->ema_overwrite != 1) { wn_set_error("adam_step_ext: ema_overwrite must be 0 or 1 (got %d)", (int)o->ema_overwrite); return WN_E_INVALID; }
-  if (!ema && (o->ema_momentum != 0.f || o->ema_overwrite != 0)) {
-    wn_set_error("adam_step_ext: ema_momentum / ema_overwrite set without ema (ema is NULL)");
-    return WN_E_INVALID;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  rc = ensure_device_tables(p);
-  if (rc) return rc;
-  const int n = (int)p->tdesc.size();
-  if (o->clip_mode == WN_CLIP_NORM || o->clip_mode == WN_CLIP_GLOBAL_NORM) {
-    rc = wn_launch_sumsq(grads, p->d_tdesc, n, scratch, s);
-    if (rc) return rc;
-  }
-  const double alpha = (double)o->lr * sqrt(1.0 - pow((double)o->beta2, (double)step)) / (1.0 - pow((double)o->beta1, (double)step));
-  return wn_launch_adam_ext(params, grads, m, v, o->amsgrad ? vhat : nullptr, ema, p->d_tdesc, n, scratch, o->clip_mode,
-                            o->clip, o->lr, o->weight_decay, o->decay_flags, (float)alpha, o->beta1, o->beta2, o->eps,
-                            o->ema_momentum, step == 1 ? 1 : 0, (int)o->ema_overwrite, skip_flag, s);
-}
-
-extern "C" int wn_clip_gradients_ext(wn_plan* p, float* grads, int32_t clip_mode, float clip, float* scratch, void* stream) {
-  const char* null_arg = !p ? "plan" : !grads ? "grads" : !scratch ? "scratch" : nullptr;
-  if (null_arg) { wn_set_error("clip_gradients_ext: %s is NULL", null_arg); return WN_E_INVALID; }
-  int rc = check_clip("clip_gradients_ext", clip_mode, clip, false);
-  if (rc) return rc;
-  rc = ensure_device_tables(p);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int n = (int)p->tdesc.size();
-  if (clip_mode == WN_CLIP_NORM) return wn_launch_clip(grads, p->d_tdesc, n, clip, scratch, s);
-  if (clip_mode == WN_CLIP_VALUE) return wn_launch_clip_value(grads, p->d_tdesc, n, clip, s);
-  rc = wn_launch_sumsq(grads, p->d_tdesc, n, scratch, s);
-  if (rc) return rc;
-  return wn_launch_scale_global(grads, p->d_tdesc, n, scratch, clip, s);
-}
-
-extern "C" int wn_adam_step(wn_plan* p, float* params, const float* grads, float* m, float* v, int64_t step,
-                            float lr, float beta1, float beta2, float eps, float clipnorm, float* scratch,
-                            void* stream) {
-  return wn_adam_step_guarded(p, params, grads, m, v, step, lr, beta1, beta2, eps, clipnorm, scratch, nullptr, stream);
 }

@@ -150,21 +150,27 @@ class Adam:
     """Is a keyword on that only wn_adam_step_ext serves?  (weight_decay 0.0 is off.)"""
     return bool(self.global_clipnorm or self.clipvalue or self.weight_decay or self.amsgrad)
 
+  def _clip_in_step(self, c):
+    """Does the clip value ``c`` act inside the Adam launch?  (clip_local_gradients has clipped already: no second clip.)"""
+    return bool(c) and not self.clip_before_reduce
+
+  def _overwrite_now(self):
+    """1 when this step (``iterations``, already counted) ends with p = ema, else 0."""
+    f = self.ema_overwrite_frequency
+    return 1 if f is not None and self.iterations % f == 0 else 0
+
   def _options(self):
     o = _lib.WnAdamOptions()
     o.lr, o.beta1, o.beta2, o.eps = self.learning_rate, self.beta_1, self.beta_2, self.epsilon
-    if not self.clip_before_reduce:                  # (clip_local_gradients has clipped already: no second clip)
-      for mode, c in ((_lib.WN_CLIP_NORM, self.clipnorm), (_lib.WN_CLIP_GLOBAL_NORM, self.global_clipnorm),
-                      (_lib.WN_CLIP_VALUE, self.clipvalue)):
-        if c:
-          o.clip_mode, o.clip = mode, float(c)
+    for mode, c in ((_lib.WN_CLIP_NORM, self.clipnorm), (_lib.WN_CLIP_GLOBAL_NORM, self.global_clipnorm),
+                    (_lib.WN_CLIP_VALUE, self.clipvalue)):
+      if self._clip_in_step(c):
+        o.clip_mode, o.clip = mode, float(c)
     o.weight_decay = self.weight_decay or 0.0
     o.amsgrad = int(self.amsgrad)
     o.decay_flags = None if self._decay_flags is None else self._decay_flags.data_ptr()
     if self.use_ema:
-      f = self.ema_overwrite_frequency
-      o.ema_momentum = float(self.ema_momentum)
-      o.ema_overwrite = 1 if f is not None and self.iterations % f == 0 else 0
+      o.ema_momentum, o.ema_overwrite = float(self.ema_momentum), self._overwrite_now()
     return o
 
   def apply_gradients(self, model, skip_flag=None):
@@ -182,20 +188,18 @@ class Adam:
           _lib.ptr(self.vhat if self.amsgrad else None), _lib.ptr(self.ema if self.use_ema else None), self.iterations,
           C.byref(o), _lib.ptr(self._scratch), _lib.ptr(skip_flag), _lib.stream_ptr()))
       return
+    clipnorm = float(self.clipnorm) if self._clip_in_step(self.clipnorm) else 0.0
     if self.use_ema:
-      f = self.ema_overwrite_frequency
       _lib.check(_lib.lib().wn_adam_step_ema(
           model._plan, _lib.ptr(model.flat_params), _lib.ptr(model.flat_grads), _lib.ptr(self.m), _lib.ptr(self.v),
           _lib.ptr(self.ema), self.iterations, self.learning_rate, self.beta_1, self.beta_2, self.epsilon,
-          float(self.clipnorm) if self.clipnorm and not self.clip_before_reduce else 0.0, float(self.ema_momentum),
-          1 if f is not None and self.iterations % f == 0 else 0,
-          _lib.ptr(self._scratch), _lib.ptr(skip_flag), _lib.stream_ptr()))
+          clipnorm, float(self.ema_momentum), self._overwrite_now(), _lib.ptr(self._scratch), _lib.ptr(skip_flag),
+          _lib.stream_ptr()))
       return
     _lib.check(_lib.lib().wn_adam_step_guarded(
         model._plan, _lib.ptr(model.flat_params), _lib.ptr(model.flat_grads), _lib.ptr(self.m),
         _lib.ptr(self.v), self.iterations, self.learning_rate, self.beta_1, self.beta_2, self.epsilon,
-        float(self.clipnorm) if self.clipnorm and not self.clip_before_reduce else 0.0,     # no second clip
-        _lib.ptr(self._scratch), _lib.ptr(skip_flag), _lib.stream_ptr()))
+        clipnorm, _lib.ptr(self._scratch), _lib.ptr(skip_flag), _lib.stream_ptr()))
 
   def finalize_variable_values(self, model):
     """Keras's name: the weights become their average (p <- ema), e.g. at the end of training.  Nothing happens without
