@@ -312,6 +312,28 @@ int wn_adam_step_ext(wn_plan* p, float* params, const float* grads, float* m, fl
  * wn_plan_param_count floats is read or written.  scratch: >= num_tensors floats. */
 int wn_clip_gradients_ext(wn_plan* p, float* grads, int32_t clip_mode, float clip, float* scratch, void* stream);
 
+/* ---- gradient accumulation: Adam(gradient_accumulation_steps=k), Keras's keyword ----
+ * The optimizer is called once per micro-step.  Calls 1 .. k-1 of a cycle only store the gradient; call k forms the mean
+ * g = (g_k + acc) / k, clips THAT with whichever clip is set (Keras 3 base_optimizer: divide, then _clip_gradients), runs
+ * the Adam step above exactly as it is (decay, amsgrad and ema unchanged) and starts a new cycle.  The step number of
+ * wn_adam_step* counts updates, not calls.  The accumulator is state of the caller's: one buffer of wn_plan_param_count
+ * floats.  This entry point is the arithmetic of one micro-step, over two flat buffers of n floats (it takes no plan):
+ *   WN_ACCUM_FIRST   acc = g                   the first micro-step of a cycle OVERWRITES: no memset, acc is not read
+ *   WN_ACCUM_ADD     acc = acc + g             every later storing micro-step
+ *   WN_ACCUM_FINISH  g = (g + acc) / (float)steps, acc untouched: the mean is left in grads, where the step reads it
+ * fp32, one correctly rounded add or IEEE division per element, nothing fused.
+ *   guard   *skip_flag != 0 (skip_flag may be NULL) leaves both buffers untouched in every mode: a pass whose range flag is
+ *           up does not reach the accumulator (the caller repeats it with the exact-fp32 kernels).
+ * float4 accesses when both pointers are 16-byte aligned, scalar ones otherwise; no access outside [0, n) of either buffer.
+ * One pass of the largest grid covers WN_ACCUM_ONE_PASS floats; beyond it the grid strides.
+ * WN_E_INVALID, checked before the device is touched and named in wn_last_error_string: a NULL acc or grads; n < 0; a mode
+ * other than the three; steps < 2 in WN_ACCUM_FINISH (the other modes do not look at steps).  n == 0 is WN_OK, no launch. */
+#define WN_ACCUM_FIRST 0
+#define WN_ACCUM_ADD 1
+#define WN_ACCUM_FINISH 2
+#define WN_ACCUM_ONE_PASS 2097152
+int wn_grad_accumulate(float* acc, float* grads, int64_t n, int32_t mode, int32_t steps, const float* skip_flag, void* stream);
+
 /* ---- forward range guard of the split-precision mode ----
  * The default kernels evaluate fp32 products from fp16 hi|lo operand splits; an activation beyond the fp16 range
  * (65504) would turn into inf/NaN.  Every forward pass therefore keeps the running max-abs of the tensors that feed

@@ -44,6 +44,9 @@ config = {                       # defaults of the reference, train.py:22-50
     # replaces that clip (only one of the three can be set).  exclude_from_weight_decay: patterns searched in the
     # variable names, e.g. ['bias']
     'global_clipnorm': None, 'clipvalue': None, 'weight_decay': None, 'amsgrad': False, 'exclude_from_weight_decay': None,
+    # Adam(gradient_accumulation_steps=k): the weights move every k-th batch, on the mean of the k gradients; an int >= 2.
+    # Checkpoints carry the cycle under way (adam_accum); not with clip_before_reduce
+    'gradient_accumulation_steps': None,
     # hold the last n utterances' frames out of training and report val_loss (test_step) after every epoch; the monitored
     # quantity of checkpointing, plateau and early stop stays loss, as in the reference
     'validation_utterances': 0,
@@ -193,7 +196,8 @@ def main():
              clip_before_reduce=config['clip_before_reduce'], use_ema=config['use_ema'],
              ema_momentum=config['ema_momentum'], ema_overwrite_frequency=config['ema_overwrite_frequency'],
              global_clipnorm=config['global_clipnorm'], clipvalue=config['clipvalue'],
-             weight_decay=config['weight_decay'], amsgrad=config['amsgrad'])
+             weight_decay=config['weight_decay'], amsgrad=config['amsgrad'],
+             gradient_accumulation_steps=config['gradient_accumulation_steps'])
   if config['exclude_from_weight_decay']:
     opt.exclude_from_weight_decay(var_names=list(config['exclude_from_weight_decay']))
   averaged = model.averaged_weights if config['use_ema'] else contextlib.nullcontext

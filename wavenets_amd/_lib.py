@@ -59,6 +59,8 @@ class WnAdamOptions(C.Structure):
 
 
 WN_CLIP_NONE, WN_CLIP_NORM, WN_CLIP_GLOBAL_NORM, WN_CLIP_VALUE = 0, 1, 2, 4      # bits of wn_adam_options.clip_mode
+WN_ACCUM_FIRST, WN_ACCUM_ADD, WN_ACCUM_FINISH = 0, 1, 2                          # modes of wn_grad_accumulate
+WN_ACCUM_ONE_PASS = 2097152                                                      # floats one pass of its largest grid covers
 
 
 class WnLayerDesc(C.Structure):
@@ -129,6 +131,7 @@ _SIGS = {
     'wn_clip_gradients': (C.c_int, [_P, _P, C.c_float, _P, _P]),
     'wn_adam_step_ext': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(WnAdamOptions), _P, _P, _P]),
     'wn_clip_gradients_ext': (C.c_int, [_P, _P, C.c_int32, C.c_float, _P, _P]),
+    'wn_grad_accumulate': (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     'wn_plan_range_slot': (C.c_int64, [_P, C.c_int32, C.c_int32, C.c_int32]),
     'wn_range_limit': (C.c_float, []),
     'wn_generate': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _P,

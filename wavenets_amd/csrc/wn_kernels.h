@@ -503,3 +503,6 @@ int wn_launch_adam(const WnAdamArgs& x, hipStream_t s);
 // write when the factor is 1.0f); g clamped to [-c, c], NaN kept (only clamped elements are written)
 int wn_launch_scale_global(float* g, const WnTensorDesc* d_table, int n, const float* norms2, float clip, hipStream_t s);
 int wn_launch_clip_value(float* g, const WnTensorDesc* d_table, int n, float clip, hipStream_t s);
+// gradient accumulation over two flat buffers of n floats, mode one WN_ACCUM_*: acc = g; acc = acc + g; g = (g + acc) / steps.
+// float4 when both pointers are 16-byte aligned, scalar otherwise; nothing outside [0, n); a raised *skip_flag = nothing moves
+int wn_launch_grad_accumulate(float* acc, float* g, int64_t n, int mode, float steps, const float* skip_flag, hipStream_t s);

@@ -225,6 +225,62 @@ int wn_launch_clip_value(float* g, const WnTensorDesc* d_table, int n, float cli
   return WN_OK;
 }
 
+// Gradient accumulation (Adam(gradient_accumulation_steps=k)), beside the Adam launch and not inside it.  One grid-stride
+// kernel over two flat buffers of n floats, the mode a template argument; per element, fp32, one correctly rounded operation
+// each and nothing fused:
+//   WN_ACCUM_FIRST   acc = g                       (an overwrite: whatever acc held is not read)
+//   WN_ACCUM_ADD     acc = acc + g
+//   WN_ACCUM_FINISH  g = (g + acc) / steps         (acc is not written)
+// A raised skip_flag leaves both buffers alone (uniform).  vec: both pointers are 16-byte aligned, the first n / 4 * 4
+// elements move as float4 and the second loop takes the n % 4 behind them; otherwise the second loop takes all n.  No access
+// leaves [0, n) of either buffer: the step's scalars sit right behind the gradient.
+// WN_ACCUM_ONE_PASS (include/wn_hip.h) = WN_ACCUM_MAX_BLOCKS * WN_ACCUM_THREADS * 4 floats is what the largest grid covers
+// without a second trip round the loop: the 1.25 M parameters of the benchmarked network take one.
+#define WN_ACCUM_THREADS 256
+#define WN_ACCUM_MAX_BLOCKS 2048
+static_assert((int64_t)WN_ACCUM_MAX_BLOCKS * WN_ACCUM_THREADS * 4 == WN_ACCUM_ONE_PASS, "wn_hip.h states the coverage");
+template <int MODE>
+__device__ __forceinline__ void wn_accum_one(float& a, float& g, float steps) {
+  if (MODE == WN_ACCUM_FIRST) a = g;
+  else if (MODE == WN_ACCUM_ADD) a = a + g;
+  else g = (g + a) / steps;
+}
+template <int MODE>
+__global__ void __launch_bounds__(WN_ACCUM_THREADS)
+wn_grad_accumulate_kernel(float* acc, float* g, int64_t n, float steps, int vec, const float* skip_flag) {
+  if (skip_flag && *skip_flag != 0.f) return;     // range guard tripped: the pass does not reach the accumulator
+  const int64_t tid = (int64_t)blockIdx.x * WN_ACCUM_THREADS + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * WN_ACCUM_THREADS;
+  const int64_t nvec = vec ? n >> 2 : 0;
+  float4* av = reinterpret_cast<float4*>(acc);
+  float4* gv = reinterpret_cast<float4*>(g);
+  for (int64_t i = tid; i < nvec; i += stride) {
+    float4 x = gv[i];
+    float4 a = MODE == WN_ACCUM_FIRST ? x : av[i];
+    wn_accum_one<MODE>(a.x, x.x, steps); wn_accum_one<MODE>(a.y, x.y, steps);
+    wn_accum_one<MODE>(a.z, x.z, steps); wn_accum_one<MODE>(a.w, x.w, steps);
+    if (MODE == WN_ACCUM_FINISH) gv[i] = x; else av[i] = a;
+  }
+  for (int64_t i = 4 * nvec + tid; i < n; i += stride) {
+    float x = g[i];
+    float a = MODE == WN_ACCUM_FIRST ? x : acc[i];
+    wn_accum_one<MODE>(a, x, steps);
+    if (MODE == WN_ACCUM_FINISH) g[i] = x; else acc[i] = a;
+  }
+}
+int wn_launch_grad_accumulate(float* acc, float* g, int64_t n, int mode, float steps, const float* skip_flag, hipStream_t s) {
+  if (n <= 0) return WN_OK;
+  const int vec = (((uintptr_t)acc | (uintptr_t)g) & 15u) == 0;
+  const int64_t units = vec ? (n >> 2) + (n & 3) : n;       // threads that have an element of either loop
+  int64_t blocks = (units + WN_ACCUM_THREADS - 1) / WN_ACCUM_THREADS;
+  if (blocks > WN_ACCUM_MAX_BLOCKS) blocks = WN_ACCUM_MAX_BLOCKS;
+  auto k = mode == WN_ACCUM_FIRST ? wn_grad_accumulate_kernel<WN_ACCUM_FIRST>
+           : mode == WN_ACCUM_ADD ? wn_grad_accumulate_kernel<WN_ACCUM_ADD> : wn_grad_accumulate_kernel<WN_ACCUM_FINISH>;
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(WN_ACCUM_THREADS), 0, s, acc, g, n, steps, vec, skip_flag);
+  WN_HIP_CHECK(hipGetLastError());
+  return WN_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // C-ABI (include/wn_hip.h): every entry point validates its own arguments under its own name, fills a wn_adam_options and
 // calls adam_apply / clip_apply.
@@ -352,4 +408,21 @@ extern "C" int wn_clip_gradients_ext(wn_plan* p, float* grads, int32_t clip_mode
   if (null_arg) { wn_set_error("clip_gradients_ext: %s is NULL", null_arg); return WN_E_INVALID; }
   if (check_clip("clip_gradients_ext", clip_mode, clip, false)) return WN_E_INVALID;
   return clip_apply(p, grads, clip_mode, clip, scratch, (hipStream_t)stream);
+}
+
+// Takes no plan: two flat buffers and a count.  Everything is checked before the device is touched.
+extern "C" int wn_grad_accumulate(float* acc, float* grads, int64_t n, int32_t mode, int32_t steps, const float* skip_flag,
+                                  void* stream) {
+  const char* null_arg = !acc ? "acc" : !grads ? "grads" : nullptr;
+  if (null_arg) { wn_set_error("grad_accumulate: %s is NULL", null_arg); return WN_E_INVALID; }
+  if (n < 0) { wn_set_error("grad_accumulate: n must be >= 0 (got %lld)", (long long)n); return WN_E_INVALID; }
+  if (mode != WN_ACCUM_FIRST && mode != WN_ACCUM_ADD && mode != WN_ACCUM_FINISH) {
+    wn_set_error("grad_accumulate: mode must be WN_ACCUM_FIRST, WN_ACCUM_ADD or WN_ACCUM_FINISH (got %d)", (int)mode);
+    return WN_E_INVALID;
+  }
+  if (mode == WN_ACCUM_FINISH && steps < 2) {
+    wn_set_error("grad_accumulate: steps must be >= 2 in WN_ACCUM_FINISH (got %d)", (int)steps);
+    return WN_E_INVALID;
+  }
+  return wn_launch_grad_accumulate(acc, grads, n, mode, (float)steps, skip_flag, (hipStream_t)stream);
 }

@@ -146,6 +146,10 @@ def save_weights(model, path: str, optimizer=None) -> None:
       arrays['adam_ema'] = optimizer.ema.detach().cpu().numpy()
     if getattr(optimizer, 'vhat', None) is not None:         # Adam(amsgrad=True): the running maximum of v
       arrays['adam_vhat'] = optimizer.vhat.detach().cpu().numpy()
+    if getattr(optimizer, 'accum', None) is not None:        # Adam(gradient_accumulation_steps=k): the cycle under way
+      held = int(optimizer.accumulated)                      # (with none held the buffer's contents mean nothing: zeros)
+      arrays['adam_accum'] = optimizer.accum.detach().cpu().numpy() if held else np.zeros(optimizer.accum.numel(), np.float32)
+      arrays['adam_accumulated'] = np.int64(held)
   if getattr(model, 'dropout', 0) > 0:
     arrays['drop_step'] = np.int64(getattr(model, '_drop_step', 0))
   # write beside the target and rename: a kill mid-write must not leave a truncated file that sorts last and
@@ -179,6 +183,15 @@ def load_weights(model, path: str, optimizer=None) -> None:
       if getattr(optimizer, 'amsgrad', False):   # a checkpoint without the maximum starts from vhat = v; without amsgrad
         src = d['adam_vhat'] if 'adam_vhat' in d else d['adam_v']                         # a stored one is ignored
         optimizer.vhat.copy_(torch.from_numpy(src).to(optimizer.vhat.device))
+      k = getattr(optimizer, 'gradient_accumulation_steps', None)
+      if k:                                      # a checkpoint without an accumulator starts a cycle; without the keyword a
+        held = int(d['adam_accumulated']) if 'adam_accum' in d and 'adam_accumulated' in d else 0     # stored one is ignored
+        if not 0 <= held < k:
+          raise ValueError(f'checkpoint holds adam_accumulated={held}, which is no micro-step count of a cycle of '
+                           f'gradient_accumulation_steps={k} (0 .. {k - 1})')
+        optimizer.accumulated = held
+        if held:
+          optimizer.accum.copy_(torch.from_numpy(d['adam_accum']).to(optimizer.accum.device))
     if optimizer is not None and getattr(optimizer, 'use_ema', False):
       optimizer.build(model)
       if 'adam_ema' in d:

@@ -1140,7 +1140,7 @@ class WaveNet(torch.nn.Module):
     lv, pending, y_true, sample = self._train_step_once(data, sample_weight)
     if lv[2] > 0:                                    # tripped on some replica -> on all of them after the SUM
       self.train_guard_trips += 1
-      self.optimizer.iterations -= 1
+      self.optimizer.undo_last_apply()               # (iterations, accumulated) as before the skipped launch
       self._drop_step -= 1 if self.dropout > 0 else 0
       with self.exact_fp32():
         lv, pending, y_true, sample = self._train_step_once(data, sample_weight)
@@ -1195,18 +1195,40 @@ class WaveNet(torch.nn.Module):
       for i, m in enumerate(dev_metrics):
         m.update_state_device(y_true, sample, out=tail[3 + i:4 + i], scale=1.0 / world, **wkw)
 
+    # Adam(gradient_accumulation_steps=k): micro-steps 1 .. k-1 only store the gradient and do not reduce it; what is
+    # reduced is a clone of the few scalars, whose flag then guards the store on every replica alike.  On micro-step k each
+    # replica forms its own mean ahead of the bucket's all-reduce (it writes flat_grads only, which a repeated step
+    # recomputes).  Without the keyword ``updates`` is always True and form_mean does nothing.
+    updates = self.optimizer.updates_next()
+    reduced = []                                        # the early branch's reduced scalars, for a storing micro-step
+
+    def scalars_alone():
+      vec = tail[:nt]
+      if dp.initialized():
+        vec = vec.clone()
+        dp.allreduce_bucket(vec)
+      return vec
+
     if early:
       def between(loss, sample, y_true):
         queue_metrics(sample, y_true)
-        vec = tail[:nt]
-        if dp.initialized():
-          vec = vec.clone()
-          dp.allreduce_bucket(vec)
+        vec = scalars_alone()
+        reduced.append(vec)
         self._mirror(vec)
       loss, sample, y_true = self.loss_and_grads(data, want_sample=want_metric, _loss_in_bucket=True, _between=between, **wkw)
-      self.optimizer.clip_local_gradients(self)         # clip_before_reduce only; in place, see the note below
-      dp.allreduce_bucket(self._grad_bucket)            # gradients + tail; no-op without a process group
-      self.optimizer.apply_gradients(self, skip_flag=tail[2:3])
+      if updates:
+        self.optimizer.clip_local_gradients(self)       # clip_before_reduce only; in place, see the note below
+        self.optimizer.form_mean(self, skip_flag=tail[2:3])
+        dp.allreduce_bucket(self._grad_bucket)          # gradients + tail; no-op without a process group
+        self.optimizer.apply_gradients(self, skip_flag=tail[2:3])
+      else:
+        self.optimizer.apply_gradients(self, skip_flag=reduced[0][2:3])
+    elif not updates:
+      loss, sample, y_true = self.loss_and_grads(data, want_sample=want_metric, _loss_in_bucket=True, **wkw)
+      queue_metrics(sample, y_true)
+      vec = scalars_alone()                             # the micro-step's only collective: a few floats
+      self._mirror(vec)
+      self.optimizer.apply_gradients(self, skip_flag=vec[2:3])
     else:
       loss, sample, y_true = self.loss_and_grads(data, want_sample=want_metric, _loss_in_bucket=True, **wkw)
       queue_metrics(sample, y_true)
@@ -1214,6 +1236,7 @@ class WaveNet(torch.nn.Module):
       # process group; the tail behind the gradient is not touched).  In place is safe under the range guard: a tripped
       # step is skipped by the flag and repeated from scratch, gradients recomputed, so nothing is clipped twice.
       self.optimizer.clip_local_gradients(self)
+      self.optimizer.form_mean(self, skip_flag=tail[2:3])
       dp.allreduce_bucket(self._grad_bucket)            # the step's ONE collective: gradients + {loss, reg_loss, flag, metrics}
       self._mirror(tail[:nt])
       self.optimizer.apply_gradients(self, skip_flag=tail[2:3])

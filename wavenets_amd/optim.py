@@ -24,6 +24,19 @@ The other Keras keywords ride in a sibling of the same launch (``wn_adam_step_ex
 * ``weight_decay=wd`` (AdamW): ``p = p - (p * wd) * lr`` ahead of the Adam update of the same step, on every tensor not
   named to ``exclude_from_weight_decay`` (before ``build``, as in Keras).  It never enters the gradient or the moments.
 * ``amsgrad=True``: ``vhat = max(vhat, v)`` is one more state stream (``adam_vhat`` in checkpoints) and the denominator.
+
+``gradient_accumulation_steps=k`` (Keras's keyword; ``None`` or an int >= 2): ``apply_gradients`` is still called once per
+micro-step.  Calls 1 .. k-1 of a cycle only store the gradient (``wn_grad_accumulate``); call k forms the mean
+``g = (g_k + acc) / k``, leaves it in ``model.flat_grads``, clips THAT with whichever clip is set (Keras 3
+``base_optimizer``: divide, then ``_clip_gradients``), runs the Adam step exactly as it is -- decay, amsgrad and ema
+unchanged -- and starts a new cycle.  ``iterations`` stays the number of UPDATES applied: Adam's ``t``, the clock of
+``ema_overwrite_frequency`` and ``adam_iterations`` in checkpoints; ``accumulated`` (0 .. k-1) is the number of micro-steps
+held in the accumulator.  The accumulator ``accum`` is state (``adam_accum`` / ``adam_accumulated`` in checkpoints): one fp32
+buffer of the parameters' size that ``build`` allocates only with ``k``; the first micro-step of a cycle overwrites it (no
+memset, no read of what it held).  fp32 throughout, in a fixed order: ``acc = g_1``, then ``acc = acc + g_j``, then
+``(g_k + acc) / (float)k``, one correctly rounded operation per element and nothing fused.  A micro-step whose range flag is
+up reaches neither buffer.  Not with ``clip_before_reduce``: the clips act on the accumulated mean and there is no
+per-replica, per-micro-batch clip to define.
 """
 from __future__ import annotations
 
@@ -40,7 +53,8 @@ class Adam:
   def __init__(self, learning_rate: float = 0.001, beta_1: float = 0.9, beta_2: float = 0.999,
                epsilon: float = 1e-7, clipnorm=None, clip_before_reduce: bool = False,
                use_ema: bool = False, ema_momentum: float = 0.99, ema_overwrite_frequency=None,
-               global_clipnorm=None, clipvalue=None, weight_decay=None, amsgrad: bool = False):
+               global_clipnorm=None, clipvalue=None, weight_decay=None, amsgrad: bool = False,
+               gradient_accumulation_steps=None):
     if not isinstance(clip_before_reduce, bool):
       raise ValueError(f'clip_before_reduce must be a bool, got {clip_before_reduce!r}')
     if not isinstance(use_ema, bool):
@@ -63,6 +77,12 @@ class Adam:
       raise ValueError(f'weight_decay must be None or a finite number >= 0, got {wd!r}')
     if not isinstance(amsgrad, bool):
       raise ValueError(f'amsgrad must be a bool, got {amsgrad!r}')
+    k = gradient_accumulation_steps
+    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 2):
+      raise ValueError(f'`gradient_accumulation_steps` must be an integer >= 2. Received: gradient_accumulation_steps={k!r}')
+    if k is not None and clip_before_reduce:
+      raise ValueError('gradient_accumulation_steps and clip_before_reduce=True cannot be combined: with accumulation the '
+                       'clips act on the accumulated mean, there is no per-replica, per-micro-batch clip')
     self.learning_rate = float(learning_rate)
     self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
     self.clipnorm = clipnorm
@@ -73,8 +93,12 @@ class Adam:
     self.weight_decay = None if weight_decay is None else float(weight_decay)
     self.amsgrad = amsgrad
     self._exclude_vars, self._exclude_names = [], []
-    self.iterations = 0
-    self.m = self.v = self.vhat = self.ema = self._scratch = self._decay_flags = None
+    self.gradient_accumulation_steps = k
+    self.iterations = 0                              # updates applied (with accumulation: not calls)
+    self.accumulated = 0                             # micro-steps held in ``accum``, 0 .. k-1
+    self._before = (0, 0)                            # (iterations, accumulated) ahead of the last apply_gradients
+    self._mean_formed = False                        # form_mean() ran for the micro-step that apply_gradients finishes
+    self.m = self.v = self.vhat = self.ema = self.accum = self._scratch = self._decay_flags = None
     self.ext_steps = 0                               # steps that took wn_adam_step_ext (the default path never counts)
 
   def exclude_from_weight_decay(self, var_list=None, var_names=None):
@@ -117,7 +141,10 @@ class Adam:
       self.v = torch.zeros_like(model.flat_params.data)
       self._scratch = torch.zeros(len(model.variable_names) + 8, dtype=torch.float32,
                                   device=model.flat_params.device)
-      self.ema = self.vhat = self._decay_flags = None
+      self.ema = self.vhat = self.accum = self._decay_flags = None
+      self.accumulated = 0                           # another model's sums are gone with the buffer: a new cycle
+    if self.gradient_accumulation_steps and self.accum is None:
+      self.accum = torch.empty_like(model.flat_params.data)        # the first micro-step of a cycle overwrites it
     if self.amsgrad and self.vhat is None:
       self.vhat = torch.zeros_like(model.flat_params.data)
     if self.weight_decay and self._decay_flags is None and (self._exclude_vars or self._exclude_names):
@@ -173,11 +200,46 @@ class Adam:
       o.ema_momentum, o.ema_overwrite = float(self.ema_momentum), self._overwrite_now()
     return o
 
+  def updates_next(self):
+    """Will the next ``apply_gradients`` move the weights?  (Always, without ``gradient_accumulation_steps``.)"""
+    k = self.gradient_accumulation_steps
+    return not k or self.accumulated == k - 1
+
+  def _accumulate(self, model, mode, skip_flag):
+    _lib.check(_lib.lib().wn_grad_accumulate(_lib.ptr(self.accum), _lib.ptr(model.flat_grads), model.flat_grads.numel(), mode,
+                                             self.gradient_accumulation_steps, _lib.ptr(skip_flag), _lib.stream_ptr()))
+
+  def form_mean(self, model, skip_flag=None):
+    """On the last micro-step of a cycle: ``model.flat_grads = (flat_grads + accum) / k``, once.  ``apply_gradients`` does
+    this itself; a data-parallel caller calls it ahead of the all-reduce (every replica forms its own mean, the SUM of the
+    means is reduced) and ``apply_gradients`` then finds it done.  Writes ``flat_grads`` only.  Nothing happens without
+    ``gradient_accumulation_steps`` or on a storing micro-step."""
+    if not self.gradient_accumulation_steps or not self.updates_next() or self._mean_formed:
+      return
+    self.build(model)
+    self._accumulate(model, _lib.WN_ACCUM_FINISH, skip_flag)
+    self._mean_formed = True
+
+  def undo_last_apply(self):
+    """The ``(iterations, accumulated)`` pair from before the last ``apply_gradients``: the counters of a micro-step that the
+    range guard skipped on the device and that is about to be repeated.  Without accumulation: ``iterations -= 1``."""
+    self.iterations, self.accumulated = self._before
+
   def apply_gradients(self, model, skip_flag=None):
     """One update of model.flat_params from model.flat_grads (src/model.py:336).  ``skip_flag``: a device float;
     when it is non-zero the kernel leaves parameters and moments untouched (the range guard of the split-precision
     mode tripped and the caller repeats the step with the exact-fp32 kernels, see WaveNet.train_step)."""
     self.build(model)
+    self._before = (self.iterations, self.accumulated)
+    k = self.gradient_accumulation_steps
+    if k:
+      if not self.updates_next():                    # micro-steps 1 .. k-1: store and return; nothing else moves
+        self._accumulate(model, _lib.WN_ACCUM_ADD if self.accumulated else _lib.WN_ACCUM_FIRST, skip_flag)
+        self.accumulated += 1
+        return
+      self.form_mean(model, skip_flag)
+      self._mean_formed = False
+      self.accumulated = 0
     self.iterations += 1
     model._train_gen = getattr(model, '_train_gen', 0) + 1      # the weights move: a differentiable() graph of the old ones is void
     if self._extended():
