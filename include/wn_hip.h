@@ -153,6 +153,14 @@ int wn_debug_eval_region(const wn_plan* p, int32_t B, int32_t T, int32_t what, i
  *   prep=none|inline|side  drop=0|1  deep16=0|1  skip=none|folded/planes|folded/rows|sum  first_final=<i>  hc0=<width>
  *   head=<epilogue|planes|rows of every head layer from first_final on, in order, comma separated> */
 int wn_debug_fwd_paths(const wn_plan* p, int32_t B, int32_t T, int32_t training, int32_t loss, char* buf, int32_t len);
+/* test / diagnosis hook, host only: which kernels block 0 takes in a model pass over (B, T) under the calling thread's
+ * switches, without dropout -- the decisions the launches of the block's forward and (training != 0) backward read:
+ *   inner=<planes|rows16|rows32 of every non-gated conv, in order, comma separated; none>
+ *   gate=s128|gen128|two|fused16|fused32|composed
+ *   go=xout|sum|skip  gu=fold|pad|image|fp32|zero  gu_pad=0|1  gu_am=<none|gxout|gskip|gfold>,<...>
+ *   data=<planes|rows16|rows32 of the backward-data product of conv 1.., comma separated; none>
+ *   gx=none|g16x|deep|fp32+absmax|fp32  drop=0|1 */
+int wn_debug_block_paths(const wn_plan* p, int32_t B, int32_t T, int32_t training, char* buf, int32_t len);
 /* the whole residual-block stack of a forward pass: one event pair per pass from the first block launch to
  * the end of the folded skip contraction = t_stack_fwd of SURVEY.md 8(d); read returns passes and the average */
 int wn_stack_prof_enable(wn_plan* p, int32_t max_passes);

@@ -1246,6 +1246,65 @@ def test_forward_paths_follow_every_key_change(net):
       assert err < 1e-4 * scale + 1e-7, (n, err, scale)
 
 
+@pytest.mark.parametrize('net', ['r64_d128', 'r64_d128_cond'])
+def test_block_paths_follow_every_key_change(net):
+  """The kernels of a block are decided per call of block_forward / block_backward (wnp::block_fwd_path, block_bwd_path) from
+  the math mode, the bound images and biases and the buffers of the call: ONE model with dropout 0.1 through logits in split
+  precision (two contractions; composed under the conditioning bias) -> logits in exact fp32 (composed) -> loss_and_grads
+  (training forward on the dropped copies, per-block backward through g_xd) -> call(training=True) -> six steps of queued
+  generate (one row per utterance on the ring taps) -> the first state again.  B = 2, T = 97: four 32-row tiles per utterance,
+  the last one ragged.  The dropout states start from set_drop_step(0), so every visit draws the first mask.  Every revisit
+  gives the bits of the first visit, and every first visit those of a fresh model built directly in that state.
+  Correctness against the oracle is the job of tests/test_gpu_rect_blocks.py."""
+  import contextlib
+  from wavenets_amd import WaveNet
+  from test_rect_blocks_cpu import CASES
+  kw = dict(CASES[net])
+  B, T = 2, 97
+  ocfg = O.OracleConfig(**kw)
+  params = O.init_params(ocfg, seed=23, bias_range=0.2)
+  x, cond = _inputs(kw, B, T + 1, seed=31)
+  x = x.to(dev())
+  cond = cond.to(dev()) if cond is not None else None
+  pack = lambda t: (t, cond) if cond is not None else t
+
+  def fresh():
+    m = WaveNet(**{k: v for k, v in kw.items() if k != 'cond_inputs'}, dropout=0.1, device=dev(), seed=77)
+    if cond is not None:
+      m.build([(1, 8, 1), (1, kw['cond_inputs'])])
+    m.set_weights([p.numpy() for p in params])
+    return m
+
+  def run(m, state):
+    what, exact = state
+    with (m.exact_fp32() if exact else contextlib.nullcontext()):
+      if what == 'logits':
+        return [m.logits(pack(x[:, :-1].contiguous())).clone()]
+      if what == 'generate':
+        w = x[:, :m.receptive_field].contiguous()
+        return [m.generate(6, sample=w, condition=cond, use_queues=True, deterministic=True).clone()]
+      m.set_drop_step(0)
+      if what == 'call':
+        return [m.call(pack(x[:, :-1].contiguous()), training=True).clone()]
+      loss, _, _ = m.loss_and_grads(pack(x))
+      return [loss.clone()] + [g.clone() for g in m.gradients()]
+  model = fresh()
+  states = [('logits', False), ('logits', True), ('grads', False), ('call', False), ('generate', False), ('logits', False)]
+  first = {}
+  for state in states:
+    got = run(model, state)
+    assert all(bool(torch.isfinite(t).all()) for t in got), state
+    if state not in first:
+      first[state] = got
+      other = run(fresh(), state)
+      assert len(got) == len(other) and all(torch.equal(a, b) for a, b in zip(got, other)), ('fresh', state)
+    assert len(got) == len(first[state]) and all(torch.equal(a, b) for a, b in zip(got, first[state])), ('revisit', state)
+  assert not torch.equal(first[('logits', False)][0], first[('logits', True)][0])      # two math modes really ran
+  assert float(first[('grads', False)][0][2]) == 0.0                                     # range flag
+  # the dropped copies really fed the training pass
+  assert not torch.equal(first[('call', False)][0], model.call(pack(x[:, :-1].contiguous())))
+
+
 @pytest.mark.parametrize('B,T', [(1, 20), (3, 97)])
 def test_wide_blocks_gradients_ragged(B, T, math_mode):
   """128-channel blocks (BASELINE configs[3] width): the forward is two split-precision contractions with the

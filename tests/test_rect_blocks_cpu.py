@@ -88,8 +88,8 @@ SPLIT_PATHS = {
     'r64_d32': (FWD_COMPOSED, SKIP_SUM, BWD_ROWS16, WG_GENERIC, 'sum', ['rows', 'rows']),
     'r96': (FWD_COMPOSED, SKIP_SUM, BWD_ROWS16, WG_GENERIC, 'sum', ['rows', 'epilogue']),
     'r48_d64': (FWD_COMPOSED, SKIP_SUM, BWD_ROWS16, WG_GENERIC, 'sum', ['rows', 'rows']),
-    # (the plan holds the two-contraction images; block_forward refuses them for a per-utterance condition bias and runs the
-    # composed kernels: a decision of the launch, which the GPU file's mode comparison sees)
+    # (the plan holds the two-contraction images; block_forward declines them for a per-utterance condition bias and runs the
+    # composed kernels: tests/test_block_paths_cpu.py::test_describe_and_the_launch_disagree_on_the_conditioned_net)
     'r64_d128_cond': (FWD_TWO, SKIP_FOLDED, BWD_ROWS16, WG_GENERIC, 'folded/planes', ['planes', 'epilogue']),
     'r128_d64_mol': (FWD_TWO, SKIP_FOLDED, BWD_ROWS16, WG_GENERIC, 'folded/planes', ['planes', 'rows']),      # 30 output columns
     'r64_d32_lpb2': (FWD_PER_CONV, SKIP_SUM, BWD_PER_CONV, WG_GENERIC_FP32, 'sum', ['rows', 'rows']),

@@ -110,6 +110,7 @@ _SIGS = {
                                      C.POINTER(C.c_int64)]),
     'wn_debug_eval_region': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'wn_debug_fwd_paths': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
+    'wn_debug_block_paths': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
     'wn_stack_prof_enable': (C.c_int, [_P, C.c_int32]),
     'wn_stack_prof_read': (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     'wn_stack_prof_read_foldprep': (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),

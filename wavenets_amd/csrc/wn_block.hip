@@ -50,79 +50,107 @@ int wgrad(const float* x, int ldx, int K, int shift, const float* g, int ldg, in
   return rc;
 }
 
-int block_forward(const BlockPtrs& k, const BlockBufs& f, hipStream_t s) {
+// Which kernels block_forward(k, f) takes under knob 1 (launches nothing).  Every term stands as it stood in front of its
+// launch.
+BlockFwdPath block_fwd_path(const BlockPtrs& k, const BlockBufs& f) {
+  BlockFwdPath p;
   const int64_t rows = (int64_t)k.B * k.T;
-  const float* h = f.x;
   int hc = k.Cin;
-  int rc;
-  if (f.pre_done && k.depth > 1) { h = nullptr; hc = k.D; }
+  if (f.pre_done && k.depth > 1) hc = k.D;
   for (int i = 0; i + 1 < k.depth && !f.pre_done; ++i) {
     const bool i16 = k.F16i[i] != nullptr;            // (training passes of deep stacks: split-precision, see deep16_ptrs)
     // 32 / 64 channels: the streamed kernel's second form with the taps as shifted planes (the rows GEMM for other widths)
-    if (i16 && k.JTi[i] == 2 && k.KS <= 4 && Planes::takes(true, k.D, hc, k.KS, hc, k.D, rows, {hc})) {
-      rc = Planes(k.B, k.T, k.D).operand(h, hc, hc).taps(k.KS, k.dil[i]).w16(k.F16i[i]).bias(k.bd[i]).act(k.act).run(f.P[i], k.D, s);
-      if (rc) return rc;
-      h = f.P[i]; hc = k.D;
-      continue;
-    }
-    Gemm g(k.B, k.T, k.D, i16 ? k.JTi[i] : ceil32(k.D));
-    for (int t = 0; t < k.KS; ++t) g.seg(h, hc, hc, (k.KS - 1 - t) * k.dil[i], i16 ? nullptr : k.Fd[i] + t * k.Fd_stride[i]);
-    if (i16) g.w16(k.F16i[i]);
-    rc = g.bias(k.bd[i]).act(k.act).run(f.P[i], k.D, s);
-    if (rc) return rc;
-    h = f.P[i]; hc = k.D;
+    p.inner[i] = (i16 && k.JTi[i] == 2 && k.KS <= 4 && Planes::takes(true, k.D, hc, k.KS, hc, k.D, rows, {hc})) ? BLK_CONV_PLANES
+                 : i16 ? BLK_CONV_ROWS16 : BLK_CONV_ROWS32;
+    p.ninner = i + 1;
+    hc = k.D;
   }
-  const int li = k.depth - 1;
   // blocks too wide for LDS-resident weights (R = D = 128): one kernel that streams the fp16 hi|lo images through an LDS
   // ring and keeps u and z on chip (wn_layer16s.hip)
   if (k.F16n && k.F16r && k.depth == 1 && k.Cc == 0 && hc == k.R && k.Cin == k.R && f.ldz % 4 == 0 && wn_debug_get(1) != 1 &&
       wn_layer_fwd_s128_supported(k.R, k.D, k.KS) && (int64_t)rows * k.R * 4 < ((int64_t)1 << 32)) {
-    WnLayerFwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = h; a.frag_d = k.F16n; a.frag_r = k.F16r;
-    a.bias_d = k.bd[li]; a.bias_r = k.br; a.cb = k.cb; a.cb_frames = k.cb_frames; a.cb_hop = k.cb_hop;
-    a.x_out = f.x_out; a.o_out = f.O; a.z_out = f.Z; a.ldz = f.ldz; a.ag_out = f.AG;
-    a.res = f.res;                                      // (null: the residual is the conv input itself)
-    a.xt[0] = f.xt[0]; a.xt[1] = f.xt[1]; a.xt[2] = nullptr;
-    a.B = k.B; a.T = k.T; a.R = k.R; a.D = k.D; a.KS = k.KS; a.dilation = k.dil[li]; a.residual = k.residual;
-    a.absmax_out = f.fwd_absmax;
     // one row per utterance (a queued-generation step): the whole block in one workgroup with every weight fragment
     // requested up front instead of the streamed pipeline (wn_gen128.hip, same arithmetic)
-    if (k.T == 1 && f.xt[0] && f.xt[1] && !f.AG && wn_gen_block128_supported(k.R, k.D, k.KS))
-      return wn_launch_gen_block128(a, s);
-    return wn_launch_layer_fwd_s128(a, s);
-  }
-  // wider blocks (or other kernel sizes) as [gated conv + gate] -> [1x1 + residual], two split-precision contractions, ahead of
-  // the exact-fp32 one-kernel forward
-  if (k.F16g && k.F16r && k.Cc == 0 && !k.cb && !f.O && hc == k.R && f.ldz % 4 == 0 && wn_debug_get(1) != 1) {
-    Gemm g(k.B, k.T, 2 * k.D, ceil32(2 * k.D));
-    for (int t = 0; t < k.KS; ++t) {
-      if (f.xt[t]) g.seg(f.xt[t], hc, hc, 0, nullptr);
-      else g.seg(h, hc, hc, (k.KS - 1 - t) * k.dil[li], nullptr);
-    }
-    rc = g.bias(k.bd[li]).w16(k.F16g).gate_fwd(f.AG, k.D).run(f.Z, f.ldz, s);
-    if (rc) return rc;
-    Gemm r(k.B, k.T, k.R, ceil32(k.R));
-    r.seg(f.Z, f.ldz, k.D, 0, k.Fr).bias(k.br).w16(k.F16r);
-    if (k.residual) r.addc(f.res ? f.res : f.x, k.Cin);
-    if (f.fwd_absmax) r.absmax_fwd(f.fwd_absmax);
-    return r.run(f.x_out, k.R, s);
-  }
-  if (k.fused && k.Cc == 0 && hc == k.R) {
-    WnLayerFwdArgs a;
-    memset(&a, 0, sizeof(a));
+    p.gate = (k.T == 1 && f.xt[0] && f.xt[1] && !f.AG && wn_gen_block128_supported(k.R, k.D, k.KS)) ? BLK_GATE_GEN128 : BLK_GATE_S128;
+  } else if (k.F16g && k.F16r && k.Cc == 0 && !k.cb && !f.O && hc == k.R && f.ldz % 4 == 0 && wn_debug_get(1) != 1) {
+    // wider blocks (or other kernel sizes) as [gated conv + gate] -> [1x1 + residual], two split-precision contractions,
+    // ahead of the exact-fp32 one-kernel forward
+    p.gate = BLK_GATE_TWO;
+  } else if (k.fused && k.Cc == 0 && hc == k.R) {
     // knob 1 = 1 forces the exact-fp32 MFMA kernel
-    const bool use16 = k.F16d && k.F16r && wn_debug_get(1) != 1;
-    a.x = h; a.frag_d = use16 ? k.F16d : k.Fd[li]; a.frag_r = use16 ? k.F16r : k.Fr;
-    a.bias_d = k.bd[li]; a.bias_r = k.br; a.cb = k.cb; a.cb_frames = k.cb_frames; a.cb_hop = k.cb_hop;
-    a.x_out = f.x_out; a.o_out = f.O; a.z_out = f.Z; a.ldz = f.ldz; a.ag_out = f.AG;
-    a.res = f.res ? f.res : ((k.depth > 1) ? f.x : nullptr);
-    a.xt[0] = f.xt[0]; a.xt[1] = f.xt[1]; a.xt[2] = f.xt[2];
-    a.B = k.B; a.T = k.T; a.R = k.R; a.D = k.D; a.KS = k.KS; a.dilation = k.dil[li]; a.residual = k.residual;
-    a.absmax_out = f.fwd_absmax;
-    return use16 ? wn_launch_layer_fwd_f16(a, s) : wn_launch_layer_fwd(a, s);
+    p.gate = (k.F16d && k.F16r && wn_debug_get(1) != 1) ? BLK_GATE_FUSED16 : BLK_GATE_FUSED32;
+  } else {
+    p.gate = BLK_GATE_COMPOSED;
   }
-  // composed path: u -> gate -> 1x1
+  return p;
+}
+
+namespace {
+
+// non-gated conv i of the stack: h [rows][hc] -> P[i] [rows][D]
+int fwd_inner(const BlockPtrs& k, const BlockBufs& f, BlkConv path, int i, const float* h, int hc, hipStream_t s) {
+  if (path == BLK_CONV_PLANES)
+    return Planes(k.B, k.T, k.D).operand(h, hc, hc).taps(k.KS, k.dil[i]).w16(k.F16i[i]).bias(k.bd[i]).act(k.act).run(f.P[i], k.D, s);
+  const bool i16 = path == BLK_CONV_ROWS16;
+  Gemm g(k.B, k.T, k.D, i16 ? k.JTi[i] : ceil32(k.D));
+  for (int t = 0; t < k.KS; ++t) g.seg(h, hc, hc, (k.KS - 1 - t) * k.dil[i], i16 ? nullptr : k.Fd[i] + t * k.Fd_stride[i]);
+  if (i16) g.w16(k.F16i[i]);
+  return g.bias(k.bd[i]).act(k.act).run(f.P[i], k.D, s);
+}
+
+// the one-kernel forms: everything of WnLayerFwdArgs but the two weight images and the third tap's rows
+WnLayerFwdArgs layer_fwd_args(const BlockPtrs& k, const BlockBufs& f, const float* h) {
+  const int li = k.depth - 1;
+  WnLayerFwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = h;
+  a.bias_d = k.bd[li]; a.bias_r = k.br; a.cb = k.cb; a.cb_frames = k.cb_frames; a.cb_hop = k.cb_hop;
+  a.x_out = f.x_out; a.o_out = f.O; a.z_out = f.Z; a.ldz = f.ldz; a.ag_out = f.AG;
+  a.res = f.res ? f.res : ((k.depth > 1) ? f.x : nullptr);   // (null: the residual is the conv input itself)
+  a.xt[0] = f.xt[0]; a.xt[1] = f.xt[1];
+  a.B = k.B; a.T = k.T; a.R = k.R; a.D = k.D; a.KS = k.KS; a.dilation = k.dil[li]; a.residual = k.residual;
+  a.absmax_out = f.fwd_absmax;
+  return a;
+}
+
+// streamed weights (depth 1, kernel size 2): wn_layer16s.hip, or its one-row form wn_gen128.hip
+int fwd_streamed(const BlockPtrs& k, const BlockBufs& f, BlkGate gate, const float* h, hipStream_t s) {
+  WnLayerFwdArgs a = layer_fwd_args(k, f, h);
+  a.frag_d = k.F16n; a.frag_r = k.F16r;
+  return gate == BLK_GATE_GEN128 ? wn_launch_gen_block128(a, s) : wn_launch_layer_fwd_s128(a, s);
+}
+
+// LDS-resident weights: fp16 hi|lo images, or the exact-fp32 MFMA kernel on the fp32 fragments
+int fwd_fused(const BlockPtrs& k, const BlockBufs& f, BlkGate gate, const float* h, hipStream_t s) {
+  const bool use16 = gate == BLK_GATE_FUSED16;
+  WnLayerFwdArgs a = layer_fwd_args(k, f, h);
+  a.frag_d = use16 ? k.F16d : k.Fd[k.depth - 1]; a.frag_r = use16 ? k.F16r : k.Fr;
+  a.xt[2] = f.xt[2];
+  return use16 ? wn_launch_layer_fwd_f16(a, s) : wn_launch_layer_fwd(a, s);
+}
+
+// [gated conv + gate] -> [1x1 + residual] on the split-precision rows kernel
+int fwd_two(const BlockPtrs& k, const BlockBufs& f, const float* h, int hc, hipStream_t s) {
+  const int li = k.depth - 1;
+  Gemm g(k.B, k.T, 2 * k.D, ceil32(2 * k.D));
+  for (int t = 0; t < k.KS; ++t) {
+    if (f.xt[t]) g.seg(f.xt[t], hc, hc, 0, nullptr);
+    else g.seg(h, hc, hc, (k.KS - 1 - t) * k.dil[li], nullptr);
+  }
+  const int rc = g.bias(k.bd[li]).w16(k.F16g).gate_fwd(f.AG, k.D).run(f.Z, f.ldz, s);
+  if (rc) return rc;
+  Gemm r(k.B, k.T, k.R, ceil32(k.R));
+  r.seg(f.Z, f.ldz, k.D, 0, k.Fr).bias(k.br).w16(k.F16r);
+  if (k.residual) r.addc(f.res ? f.res : f.x, k.Cin);
+  if (f.fwd_absmax) r.absmax_fwd(f.fwd_absmax);
+  return r.run(f.x_out, k.R, s);
+}
+
+// u -> gate -> 1x1 in exact fp32
+int fwd_composed(const BlockPtrs& k, const BlockBufs& f, const float* h, int hc, hipStream_t s) {
+  const int64_t rows = (int64_t)k.B * k.T;
+  const int li = k.depth - 1;
+  int rc;
   {
     Gemm g(k.B, k.T, 2 * k.D, ceil32(2 * k.D));
     for (int t = 0; t < k.KS; ++t) {
@@ -151,53 +179,111 @@ int block_forward(const BlockPtrs& k, const BlockBufs& f, hipStream_t s) {
   }
 }
 
-int block_backward(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, hipStream_t s) {
-  const int64_t rows = (int64_t)k.B * k.T;
-  int rc;
-  const int li = k.depth - 1;
-  const float* hin_last = (k.depth > 1) ? f.P[li - 1] : f.x;
-  const int hc_last = (k.depth > 1) ? k.D : k.Cin;
-  // gradient w.r.t. the conv1 output o
-  const float* g_o = g.g_xout;
-  if (k.S == 0 && g.g_skip) {
-    if (g.g_xout) {
-      rc = wn_launch_add(g.g_xout, g.g_skip, g.g_o_tmp, rows * k.R, s);
-      if (rc) return rc;
-      g_o = g.g_o_tmp;
-    } else {
-      g_o = g.g_skip;
-    }
-  }
-  // g_u = gate'( W_r g_o + W_s g_skip )
-  {
-    // (deep stacks in training: the [W_r | W_s] image may be padded to two row tiles; it is only set when it will be used)
-    const bool full_u = (k.S > 0) ? (g_o && g.g_skip) : (g_o != nullptr);
-    const bool pad_u = k.JTu > 0 && k.G16u && full_u && k.Cc == 0 && g.am_gu &&
-                       ((g_o == g.g_xout) ? g.am_gxout : (g_o == g.g_skip ? g.am_gskip : g.am_gxout)) != nullptr;
-    Gemm gm(k.B, k.T, k.D, pad_u ? k.JTu : ceil32(k.D));
-    const bool use_fold = g.g_fold && g_o && k.G16uf && g.am_gu && g.am_gxout && g.am_gfold && k.Cc == 0;
-    if (g_o) gm.seg(g_o, k.R, k.R, 0, (use_fold || pad_u) ? nullptr : k.Br_);
-    if (use_fold) gm.seg(g.g_fold, g.fold_F0, g.fold_F0, 0, nullptr).w16(k.G16uf).absmax(g.am_gxout, g.am_gfold, g.am_gu);
-    else if (k.S > 0 && g.g_skip) gm.seg(g.g_skip, k.S, k.S, 0, pad_u ? nullptr : k.Bs);
-    if (use_fold) {
-      rc = gm.gate_bwd(f.AG, k.D, f.Z, f.ldz).run(g.g_u, 2 * k.D, s);
-    } else if (gm.a.nseg == 0) {
-      rc = wn_launch_fill(g.g_u, 0.f, rows * 2 * k.D, s);
-    } else {
-      // the [W_r | W_s] image matches the segment list only when both (or, for S == 0, the single) operands exist
-      const bool full = (k.S > 0) ? (g_o && g.g_skip) : true;
-      if (k.G16u && full && k.Cc == 0 && (k.JTu == 0 || pad_u)) {
-        const float* a0 = (g_o == g.g_xout) ? g.am_gxout : (g_o == g.g_skip ? g.am_gskip : g.am_gxout);
-        const float* a1 = (k.S > 0 || g_o == g.g_o_tmp) ? g.am_gskip : nullptr;
-        if (g.am_gu && a0) gm.w16(k.G16u).absmax(a0, a1, g.am_gu);
-      }
-      // (no image for this shape: the exact-fp32 kernel, which still owes g_u's scale to the g_x product and the jobs)
-      if (!gm.w16_ && g.am_gu) gm.absmax(nullptr, nullptr, g.am_gu);
-      rc = gm.gate_bwd(f.AG, k.D, f.Z, f.ldz).run(g.g_u, 2 * k.D, s);
-    }
+}  // namespace
+
+int block_forward(const BlockPtrs& k, const BlockBufs& f, hipStream_t s) {
+  const BlockFwdPath p = block_fwd_path(k, f);
+  const float* h = f.x;
+  int hc = k.Cin;
+  if (f.pre_done && k.depth > 1) { h = nullptr; hc = k.D; }
+  for (int i = 0; i < p.ninner; ++i) {
+    const int rc = fwd_inner(k, f, p.inner[i], i, h, hc, s);
     if (rc) return rc;
+    h = f.P[i]; hc = k.D;
   }
-  // conv1 / conv_skip weight gradients
+  switch (p.gate) {
+    case BLK_GATE_S128: case BLK_GATE_GEN128: return fwd_streamed(k, f, p.gate, h, s);
+    case BLK_GATE_TWO: return fwd_two(k, f, h, hc, s);
+    case BLK_GATE_FUSED16: case BLK_GATE_FUSED32: return fwd_fused(k, f, p.gate, h, s);
+    case BLK_GATE_COMPOSED: break;
+  }
+  return fwd_composed(k, f, h, hc, s);
+}
+
+namespace {
+
+// gradient w.r.t. the conv1 output o
+const float* go_ptr(BlkGo go, const BlockGrads& g) { return go == BLK_GO_XOUT ? g.g_xout : go == BLK_GO_SUM ? g.g_o_tmp : g.g_skip; }
+
+const float* am_ptr(BlkAm a, const BlockGrads& g) {
+  return a == BLK_AM_GXOUT ? g.am_gxout : a == BLK_AM_GSKIP ? g.am_gskip : a == BLK_AM_GFOLD ? g.am_gfold : nullptr;
+}
+
+}  // namespace
+
+// Which kernels block_backward(k, f, g) takes (launches nothing).  Every term stands as it stood in front of its launch;
+// knob 1 is not among them: an image chosen here goes to Gemm::run, which has that test.
+BlockBwdPath block_bwd_path(const BlockPtrs& k, const BlockBufs&, const BlockGrads& g) {   // (no term reads the buffers today)
+  BlockBwdPath p;
+  const int64_t rows = (int64_t)k.B * k.T;
+  const int li = k.depth - 1;
+  if (k.S == 0 && g.g_skip) p.go = g.g_xout ? BLK_GO_SUM : BLK_GO_SKIP;
+  const float* g_o = go_ptr(p.go, g);
+  // g_u = gate'( W_r g_o + W_s g_skip ): the max-abs slots of its (up to) two operands
+  const BlkAm s0 = (g_o == g.g_xout) ? BLK_AM_GXOUT : (g_o == g.g_skip ? BLK_AM_GSKIP : BLK_AM_GXOUT);
+  const BlkAm s1 = (k.S > 0 || g_o == g.g_o_tmp) ? BLK_AM_GSKIP : BLK_AM_NONE;
+  // (deep stacks in training: the [W_r | W_s] image may be padded to two row tiles; it is only set when it will be used)
+  const bool full_u = (k.S > 0) ? (g_o && g.g_skip) : (g_o != nullptr);
+  p.gu_pad = k.JTu > 0 && k.G16u && full_u && k.Cc == 0 && g.am_gu && am_ptr(s0, g) != nullptr;
+  const bool use_fold = g.g_fold && g_o && k.G16uf && g.am_gu && g.am_gxout && g.am_gfold && k.Cc == 0;
+  if (use_fold) {
+    p.gu = BLK_GU_FOLD; p.gu_am[0] = BLK_AM_GXOUT; p.gu_am[1] = BLK_AM_GFOLD;
+  } else if (!g_o && !(k.S > 0 && g.g_skip)) {
+    p.gu = BLK_GU_ZERO;
+  } else {
+    // the [W_r | W_s] image matches the segment list only when both (or, for S == 0, the single) operands exist
+    const bool full = (k.S > 0) ? (g_o && g.g_skip) : true;
+    if (k.G16u && full && k.Cc == 0 && (k.JTu == 0 || p.gu_pad) && g.am_gu && am_ptr(s0, g)) {
+      p.gu = p.gu_pad ? BLK_GU_PAD : BLK_GU_IMAGE; p.gu_am[0] = s0; p.gu_am[1] = s1;
+    } else {
+      p.gu = BLK_GU_FP32;     // (no image for this shape)
+    }
+  }
+  // dilated stack, last (gated) conv first
+  int gc = 2 * k.D;
+  for (int i = li; i >= 0; --i) {
+    const int hc = (i > 0) ? k.D : k.Cin;
+    if (!((i > 0) || g.g_x)) break;
+    // deep stacks in training: split-precision product, operand scaled by the running max-abs of gcur, the result's
+    // max-abs published for the next product and for the weight-gradient jobs
+    const float* am_cur = (i == li) ? g.am_gu : g.am_gp[i];
+    const float* am_dst = (i > 0) ? g.am_gp[i - 1] : g.am_gx;
+    const bool b16 = k.depth > 1 && k.G16i[i] && am_cur && am_dst;
+    if (i > 0) {
+      // inner convs (their output gradient gets act' folded in): the streamed kernel's second form, backward-data
+      // instantiation with the taps as negatively shifted planes (the rows GEMM for other widths)
+      p.data[i] = (b16 && k.JTb[i] == 2 && k.KS <= 4 && Planes::takes(true, hc, gc, k.KS, gc, hc, rows, {gc})) ? BLK_CONV_PLANES
+                  : b16 ? BLK_CONV_ROWS16 : BLK_CONV_ROWS32;
+      gc = k.D;
+      continue;
+    }
+    p.drop = g.drop_rate > 0.f;
+    // (under dropout the dropout kernel publishes g_x's max-abs: the products publish none and G16x does not ask for the slot)
+    if (p.drop) p.gx = (k.G16x && k.depth == 1 && g.am_gu) ? BLK_GX_G16X : b16 ? BLK_GX_DEEP : BLK_GX_FP32;
+    else p.gx = (k.G16x && k.depth == 1 && g.am_gu && g.am_gx) ? BLK_GX_G16X : b16 ? BLK_GX_DEEP : g.am_gx ? BLK_GX_FP32_ABSMAX : BLK_GX_FP32;
+  }
+  return p;
+}
+
+namespace {
+
+// g_u = gate'( W_r g_o + W_s g_skip )
+int bwd_gu(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, const BlockBwdPath& p, const float* g_o, hipStream_t s) {
+  if (p.gu == BLK_GU_ZERO) return wn_launch_fill(g.g_u, 0.f, (int64_t)k.B * k.T * 2 * k.D, s);
+  const bool fold = p.gu == BLK_GU_FOLD;
+  Gemm gm(k.B, k.T, k.D, p.gu_pad ? k.JTu : ceil32(k.D));
+  if (g_o) gm.seg(g_o, k.R, k.R, 0, (fold || p.gu_pad) ? nullptr : k.Br_);
+  if (fold) gm.seg(g.g_fold, g.fold_F0, g.fold_F0, 0, nullptr);
+  else if (k.S > 0 && g.g_skip) gm.seg(g.g_skip, k.S, k.S, 0, p.gu_pad ? nullptr : k.Bs);
+  // (exact fp32: the kernel still owes g_u's scale to the g_x product and the jobs)
+  if (p.gu == BLK_GU_FP32) { if (g.am_gu) gm.absmax(nullptr, nullptr, g.am_gu); }
+  else gm.w16(fold ? k.G16uf : k.G16u).absmax(am_ptr(p.gu_am[0], g), am_ptr(p.gu_am[1], g), g.am_gu);
+  return gm.gate_bwd(f.AG, k.D, f.Z, f.ldz).run(g.g_u, 2 * k.D, s);
+}
+
+// conv1 / conv_skip weight gradients, and the time-varying condition's (standalone layer)
+int bwd_block_wgrads(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, const float* g_o, hipStream_t s) {
+  int rc = WN_OK;
   if (g.defer) {
     // batched later; only the per-utterance column sums of g_u are needed now (conditioning)
     if (g.dcb) {
@@ -229,6 +315,62 @@ int block_backward(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, 
       if (rc) return rc;
     }
   }
+  return WN_OK;
+}
+
+// backward data of conv i >= 1: gcur [rows][gc] -> dst, the gradient at conv i - 1's pre-activation output (act' folded in)
+int bwd_inner(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, BlkConv path, int i, const float* gcur, int gc,
+              float* dst, hipStream_t s) {
+  // deep stacks in training: split-precision product, operand scaled by the running max-abs of gcur, the result's
+  // max-abs published for the next product and for the weight-gradient jobs
+  const float* am_cur = (i == k.depth - 1) ? g.am_gu : g.am_gp[i];
+  float* am_dst = g.am_gp[i - 1];
+  if (path == BLK_CONV_PLANES)
+    return Planes(k.B, k.T, k.D).operand(gcur, gc, gc).taps(k.KS, -k.dil[i]).w16(k.G16i[i]).act(k.act)
+        .bwd(am_cur, am_dst, f.P[i - 1], k.D).run(dst, k.D, s);
+  const bool b16 = path == BLK_CONV_ROWS16;
+  Gemm gm(k.B, k.T, k.D, b16 ? k.JTb[i] : ceil32(k.D));
+  for (int t = 0; t < k.KS; ++t)
+    gm.seg(gcur, gc, gc, -(k.KS - 1 - t) * k.dil[i], b16 ? nullptr : k.Bd[i] + t * k.Bd_stride[i]);
+  if (b16) gm.w16(k.G16i[i]).absmax(am_cur, nullptr, am_dst);
+  return gm.dact(f.P[i - 1], k.D, k.act).run(dst, k.D, s);
+}
+
+// backward data of conv 0: gcur [rows][gc] -> g_x (+ the residual path); under dropout the conv-path gradient first, then
+// the keep-mask, then the (unmasked) residual path, and the dropout kernel publishes g_x's max-abs
+int bwd_gx(const BlockPtrs& k, const BlockGrads& g, const BlockBwdPath& p, const float* gcur, int gc, hipStream_t s) {
+  const int hc = k.Cin;
+  const bool b16 = p.gx == BLK_GX_DEEP;
+  const float* am_cur = (k.depth == 1) ? g.am_gu : g.am_gp[0];
+  float* am_out = p.drop ? nullptr : g.am_gx;
+  Gemm gm(k.B, k.T, hc, b16 ? k.JTb[0] : ceil32(hc));
+  for (int t = 0; t < k.KS; ++t)
+    gm.seg(gcur, gc, gc, -(k.KS - 1 - t) * k.dil[0], b16 ? nullptr : k.Bd[0] + t * k.Bd_stride[0]);
+  if (!p.drop && k.residual && g.g_xout) gm.addc(g.g_xout, k.R);
+  switch (p.gx) {
+    case BLK_GX_G16X: gm.w16(k.G16x).absmax(g.am_gu, nullptr, am_out); break;
+    case BLK_GX_DEEP: gm.w16(k.G16i[0]).absmax(am_cur, nullptr, am_out); break;
+    case BLK_GX_FP32_ABSMAX: gm.absmax(nullptr, nullptr, g.am_gx); break;   // (the next block's g_u product reads it)
+    case BLK_GX_FP32: case BLK_GX_NONE: break;
+  }
+  if (!p.drop) return gm.run(g.g_x, hc, s);
+  const int rc = gm.run(g.g_xd, hc, s);
+  if (rc) return rc;
+  return wn_launch_dropout(g.g_xd, (k.residual && g.g_xout) ? g.g_xout : nullptr, g.g_x, (int64_t)k.B * k.T * hc, g.drop_rate,
+                           g.drop_key, g.am_gx, s);
+}
+
+}  // namespace
+
+int block_backward(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, hipStream_t s) {
+  const BlockBwdPath p = block_bwd_path(k, f, g);
+  const int64_t rows = (int64_t)k.B * k.T;
+  const int li = k.depth - 1;
+  int rc;
+  const float* g_o = go_ptr(p.go, g);
+  if (p.go == BLK_GO_SUM && (rc = wn_launch_add(g.g_xout, g.g_skip, g.g_o_tmp, rows * k.R, s))) return rc;
+  if ((rc = bwd_gu(k, f, g, p, g_o, s))) return rc;
+  if ((rc = bwd_block_wgrads(k, f, g, g_o, s))) return rc;
   // dilated stack, last (gated) conv first
   const float* gcur = g.g_u;       // gradient w.r.t. the pre-activation output of conv i
   int gc = 2 * k.D;
@@ -242,54 +384,12 @@ int block_backward(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, 
                  (last_tap && i == li) ? g.dcb : nullptr, g.slab, s);
       if (rc) return rc;
     }
-    const bool need_gx = (i > 0) || g.g_x;
-    if (!need_gx) break;
-    // deep stacks in training: split-precision product, operand scaled by the running max-abs of gcur, the result's
-    // max-abs published for the next product and for the weight-gradient jobs
-    const float* am_cur = (i == li) ? g.am_gu : g.am_gp[i];
-    float* am_dst = (i > 0) ? g.am_gp[i - 1] : g.am_gx;
-    const bool b16 = k.depth > 1 && k.G16i[i] && am_cur && am_dst;
-    // inner convs (their output gradient gets act' folded in): the streamed kernel's second form, backward-data
-    // instantiation with the taps as negatively shifted planes (the rows GEMM for other widths)
-    if (b16 && i > 0 && k.JTb[i] == 2 && k.KS <= 4 && Planes::takes(true, hc, gc, k.KS, gc, hc, rows, {gc})) {
-      float* dst = g.g_pi[i - 1] ? g.g_pi[i - 1] : g.g_p + (int64_t)((i & 1) ? 0 : rows * k.D);
-      rc = Planes(k.B, k.T, hc).operand(gcur, gc, gc).taps(k.KS, -k.dil[i]).w16(k.G16i[i]).act(k.act)
-               .bwd(am_cur, am_dst, f.P[i - 1], k.D).run(dst, hc, s);
-      if (rc) return rc;
-      gcur = dst; gc = k.D;
-      continue;
-    }
-    Gemm gm(k.B, k.T, hc, b16 ? k.JTb[i] : ceil32(hc));
-    for (int t = 0; t < k.KS; ++t)
-      gm.seg(gcur, gc, gc, -(k.KS - 1 - t) * k.dil[i], b16 ? nullptr : k.Bd[i] + t * k.Bd_stride[i]);
-    if (i > 0) {
-      // output is the gradient w.r.t. P[i-1] (post-activation) -> fold act' in
-      float* dst = g.g_pi[i - 1] ? g.g_pi[i - 1] : g.g_p + (int64_t)((i & 1) ? 0 : rows * k.D);
-      if (b16) gm.w16(k.G16i[i]).absmax(am_cur, nullptr, am_dst);
-      rc = gm.dact(f.P[i - 1], k.D, k.act).run(dst, k.D, s);
-      if (rc) return rc;
-      gcur = dst; gc = k.D;
-    } else {
-      if (g.drop_rate > 0.f) {
-        // conv-path gradient first, then the keep-mask, then the (unmasked) residual path
-        if (k.G16x && k.depth == 1 && g.am_gu) gm.w16(k.G16x).absmax(g.am_gu, nullptr, nullptr);
-        else if (b16) gm.w16(k.G16i[0]).absmax(am_cur, nullptr, nullptr);      // (the dropout kernel publishes g_x's max-abs)
-        rc = gm.run(g.g_xd, hc, s);
-        if (rc) return rc;
-        rc = wn_launch_dropout(g.g_xd, (k.residual && g.g_xout) ? g.g_xout : nullptr, g.g_x, rows * hc, g.drop_rate,
-                               g.drop_key, g.am_gx, s);
-        if (rc) return rc;
-        continue;
-      }
-      if (k.residual && g.g_xout) gm.addc(g.g_xout, k.R);
-      if (k.G16x && k.depth == 1 && g.am_gu && g.am_gx) gm.w16(k.G16x).absmax(g.am_gu, nullptr, g.am_gx);
-      else if (b16) gm.w16(k.G16i[0]).absmax(am_cur, nullptr, am_dst);
-      else if (g.am_gx) gm.absmax(nullptr, nullptr, g.am_gx);       // (exact-fp32 kernel: the next block's g_u product reads it)
-      rc = gm.run(g.g_x, hc, s);
-      if (rc) return rc;
-    }
+    if (i == 0) return p.gx == BLK_GX_NONE ? WN_OK : bwd_gx(k, g, p, gcur, gc, s);
+    // where the gradient at conv i - 1's output goes: kept for the deferred weight gradients, or a half of g_p
+    float* dst = g.g_pi[i - 1] ? g.g_pi[i - 1] : g.g_p + (int64_t)((i & 1) ? 0 : rows * k.D);
+    if ((rc = bwd_inner(k, f, g, p.data[i], i, gcur, gc, dst, s))) return rc;
+    gcur = dst; gc = k.D;
   }
-  (void)hin_last; (void)hc_last;
   return WN_OK;
 }
 
@@ -448,6 +548,17 @@ void layer_ptrs(const wn_layer_desc* d, const LayerLayout& L, const float* param
   }
 }
 
+// the layer's input and its saved buffer (stack activations, sigmoid, z): what wn_layer_fwd writes and wn_layer_bwd reads
+BlockBufs layer_bufs(const wn_layer_desc* d, const LayerLayout& L, const float* x, float* saved) {
+  BlockBufs f;
+  memset(&f, 0, sizeof(f));
+  f.x = x;
+  for (int i = 0; i + 1 < d->depth; ++i) f.P[i] = saved + L.sP[i];
+  f.AG = saved + L.sAG;
+  f.Z = saved + L.sZ; f.ldz = d->dilation_channels > 0 ? d->dilation_channels : d->channels;
+  return f;
+}
+
 }  // namespace
 
 extern "C" int64_t wn_layer_param_count(const wn_layer_desc* d) {
@@ -514,17 +625,9 @@ extern "C" int wn_layer_fwd(const wn_layer_desc* d, const float* params, const f
   BlockPtrs k;
   layer_ptrs(d, L, params, workspace, cond, B, T, k);
   const int D = k.D;
-  const int64_t rows = (int64_t)B * T;
-  BlockBufs f;
-  memset(&f, 0, sizeof(f));
-  f.x = x;
-  // without a saved buffer the intermediates live in scratch carved after the u buffer
-  float* sv = saved;
-  for (int i = 0; i + 1 < d->depth; ++i) f.P[i] = sv ? sv + L.sP[i] : nullptr;
+  if (!saved) { wn_set_error("layer_fwd: saved buffer is required (holds z and the stack activations)"); return WN_E_INVALID; }
+  BlockBufs f = layer_bufs(d, L, x, saved);
   f.U = workspace + L.U;
-  f.AG = sv ? sv + L.sAG : nullptr;
-  f.Z = sv ? sv + L.sZ : nullptr; f.ldz = D;
-  if (!sv) { wn_set_error("layer_fwd: saved buffer is required (holds z and the stack activations)"); return WN_E_INVALID; }
   const bool skip_is_o = (d->skip_channels == 0);
   f.O = (skip_is_o && skip_out) ? skip_out : nullptr;
   f.x_out = x_out;
@@ -532,7 +635,6 @@ extern "C" int wn_layer_fwd(const wn_layer_desc* d, const float* params, const f
   if (!skip_is_o && skip_out) {
     rc = Gemm(B, T, d->skip_channels, ceil32(d->skip_channels)).seg(f.Z, D, D, 0, k.Fs).bias(k.bs).run(skip_out, d->skip_channels, s);
   }
-  (void)rows;
   return rc;
 }
 
@@ -547,12 +649,7 @@ extern "C" int wn_layer_bwd(const wn_layer_desc* d, const float* params, const f
   if ((rc = layer_prep(d, L, params, workspace, s))) return rc;
   BlockPtrs k;
   layer_ptrs(d, L, params, workspace, cond, B, T, k);
-  BlockBufs f;
-  memset(&f, 0, sizeof(f));
-  f.x = x;
-  float* sv = const_cast<float*>(saved);
-  for (int i = 0; i + 1 < d->depth; ++i) f.P[i] = sv + L.sP[i];
-  f.AG = sv + L.sAG; f.Z = sv + L.sZ; f.ldz = k.D;
+  const BlockBufs f = layer_bufs(d, L, x, const_cast<float*>(saved));
   BlockGrads g;
   memset(&g, 0, sizeof(g));
   g.g_xout = g_x_out; g.g_skip = g_skip; g.g_o_tmp = workspace + L.g_o; g.g_u = workspace + L.g_u;

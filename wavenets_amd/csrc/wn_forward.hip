@@ -68,6 +68,19 @@ void deep16_ptrs(const wn_plan* p, int b, const float* fragbase, BlockPtrs& k) {
   if (bi.g16u >= 0) { k.G16u = fragbase + bi.g16u; k.JTu = std::max(2, ceil32(p->D)); }
 }
 
+BlockBufs block_bufs(const wn_plan* p, const WsLayout& L, float* ws, int b, int64_t rows, bool training, bool drop) {
+  BlockBufs f;
+  memset(&f, 0, sizeof(f));
+  float* hin = ws + L.H[training ? b : (b & 1)];
+  f.x = hin;
+  // x = dropout(x) feeds the dilated stack; the residual keeps the original (src/layers.py:192-196)
+  if (drop) { f.x = ws + L.XD[b]; f.res = hin; }
+  for (int i = 0; i + 1 < p->LPB; ++i) f.P[i] = ws + L.P[b][i];
+  f.AG = training ? ws + L.AG[b] : nullptr;
+  f.Z = ws + L.Z + (int64_t)b * rows * p->Dp; f.ldz = p->Dp;      // block-major [N][rows][Dp]
+  return f;
+}
+
 int ring_capture(const float* src, int B, int T, int C, int nslots, float* ring, int64_t t0, hipStream_t s) {
   const int64_t n = (int64_t)nslots * B * C;
   hipLaunchKernelGGL(wn_ring_capture_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, s,
@@ -258,24 +271,14 @@ struct FwdCall {
         k.cb = ws + L.cb + (int64_t)b * Bc * 2 * p->D;
         k.cb_frames = F; k.cb_hop = hop;                 // (F == 1: the row is the utterance)
       }
-      BlockBufs f;
-      memset(&f, 0, sizeof(f));
-      const int hi = training ? b : (b & 1), ho = training ? b + 1 : ((b + 1) & 1);
-      f.x = ws + L.H[hi];
+      BlockBufs f = block_bufs(p, L, ws, b, rows, training, fp.drop);
       if (fp.drop) {
-        // x = dropout(x) feeds the dilated stack; the residual keeps the original (src/layers.py:192-196)
-        rc = wn_launch_dropout(ws + L.H[hi], nullptr, ws + L.XD[b], rows * p->R, e.drop_rate,
+        rc = wn_launch_dropout(f.res, nullptr, ws + L.XD[b], rows * p->R, e.drop_rate,
                                wn_dropout_key(e.drop_seed, b, e.drop_step), nullptr, s);
         if (rc) return rc;
-        f.x = ws + L.XD[b];
-        f.res = ws + L.H[hi];
       }
-      for (int i = 0; i + 1 < p->LPB; ++i) f.P[i] = ws + L.P[b][i];
       f.U = ws + L.U;
-      f.AG = training ? ws + L.AG[b] : nullptr;
-      f.Z = ws + L.Z + (int64_t)b * rows * p->Dp; f.ldz = p->Dp;      // block-major [N][rows][Dp]
-      f.O = nullptr;
-      f.x_out = ws + L.H[ho];
+      f.x_out = ws + L.H[training ? b + 1 : ((b + 1) & 1)];
       f.fwd_absmax = fam;
       // one event pair per block launch, or one around the whole chain
       const bool prof = e.prof_on && pair_free(e.prof_ev, e.prof_used);

@@ -155,6 +155,44 @@ struct FwdPaths {
   }
 };
 
+// Which kernels one residual block takes: decided once per call of block_forward / block_backward (block_fwd_path,
+// block_bwd_path, wn_block.hip), read by their launch functions and written out by wn_debug_block_paths.
+// a conv of the dilated stack, forward or backward data: the streamed kernel's second form with the taps as shifted planes |
+// rows GEMM on a split-precision image | rows GEMM in exact fp32
+enum BlkConv : uint8_t { BLK_CONV_PLANES, BLK_CONV_ROWS16, BLK_CONV_ROWS32 };
+// the gated conv + 1x1: streamed one-kernel forward (wn_layer16s.hip) | its one-row form (wn_gen128.hip) | two split-precision
+// contractions | LDS-resident one-kernel forward on fp16 images | ... in exact fp32 | rows GEMM -> gate kernel -> rows GEMM
+enum BlkGate : uint8_t { BLK_GATE_S128, BLK_GATE_GEN128, BLK_GATE_TWO, BLK_GATE_FUSED16, BLK_GATE_FUSED32, BLK_GATE_COMPOSED };
+struct BlockFwdPath {
+  int ninner = 0;                 // non-gated convs this call runs (none when the queued generation step ran them: pre_done)
+  BlkConv inner[16] = {};
+  BlkGate gate = BLK_GATE_COMPOSED;
+  bool operator==(const BlockFwdPath& o) const {
+    return ninner == o.ninner && std::equal(inner, inner + 16, o.inner) && gate == o.gate;
+  }
+};
+// g_o, the gradient at the 1x1 conv's output: g_xout | g_xout + g_skip into g_o_tmp (S == 0, both given) | g_skip (S == 0)
+enum BlkGo : uint8_t { BLK_GO_XOUT, BLK_GO_SUM, BLK_GO_SKIP };
+// the g_u product: [W_r | V(b)] image over (g_o, dL/da) | [W_r | W_s] image padded to two row tiles | [W_r | W_s] image |
+// exact fp32 | no operand: zero fill
+enum BlkGu : uint8_t { BLK_GU_FOLD, BLK_GU_PAD, BLK_GU_IMAGE, BLK_GU_FP32, BLK_GU_ZERO };
+enum BlkAm : uint8_t { BLK_AM_NONE, BLK_AM_GXOUT, BLK_AM_GSKIP, BLK_AM_GFOLD };   // an input max-abs slot of BlockGrads
+// the g_x product (conv 0's backward data): not formed | G16x | the deep stack's image | exact fp32 publishing g_x's max-abs | exact fp32
+enum BlkGx : uint8_t { BLK_GX_NONE, BLK_GX_G16X, BLK_GX_DEEP, BLK_GX_FP32_ABSMAX, BLK_GX_FP32 };
+struct BlockBwdPath {
+  BlkGo go = BLK_GO_XOUT;
+  BlkGu gu = BLK_GU_ZERO;
+  bool gu_pad = false;            // the g_u contraction walks JTu row tiles of an image without fp32 fragments
+  BlkAm gu_am[2] = {};            // the two input max-abs slots of an image form of the g_u product
+  BlkConv data[16] = {};          // backward data of conv i, depth > i >= 1 (its result gets act' folded in)
+  BlkGx gx = BLK_GX_NONE;
+  bool drop = false;              // g_x's conv path into g_xd, then the keep-mask and the residual path (wn_launch_dropout)
+  bool operator==(const BlockBwdPath& o) const {
+    return go == o.go && gu == o.gu && gu_pad == o.gu_pad && gu_am[0] == o.gu_am[0] && gu_am[1] == o.gu_am[1] &&
+           std::equal(data, data + 16, o.data) && gx == o.gx && drop == o.drop;
+  }
+};
+
 // owning device copy of a host table
 template <class T> struct DevTable {
   T* d = nullptr;
@@ -598,12 +636,18 @@ int64_t slab_need(int B, int T, int K, int N);
 // ---- wn_block.hip ----
 int wgrad(const float* x, int ldx, int K, int shift, const float* g, int ldg, int N, int B, int T,
           float* dW, float* db, float* per_batch, float* slab, hipStream_t s);
+BlockFwdPath block_fwd_path(const BlockPtrs& k, const BlockBufs& f);
+BlockBwdPath block_bwd_path(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g);
 int block_forward(const BlockPtrs& k, const BlockBufs& f, hipStream_t s);
 int block_backward(const BlockPtrs& k, const BlockBufs& f, const BlockGrads& g, hipStream_t s);
 // ---- wn_forward.hip ----
 bool loss_fusable(const wn_plan* p, int64_t rows);
 BlockPtrs block_ptrs(const wn_plan* p, int b, const float* params, const float* fragbase, int B, int T);
 void deep16_ptrs(const wn_plan* p, int b, const float* fragbase, BlockPtrs& k);
+// the buffers of block b in the workspace of layout L: its input (drop: the dropped copy, the original as the residual
+// source), the stack's activations, the saved sigmoid (training layouts) and its plane of Z -- what the forward pass writes
+// and the backward pass reads
+BlockBufs block_bufs(const wn_plan* p, const WsLayout& L, float* ws, int b, int64_t rows, bool training, bool drop);
 int forward_core(wn_plan* p, const float* params, const float* x, bool prep, const float* cond, int B,
                  int T, bool training, float* ws, const WsLayout& L, hipStream_t s, const GenRings* rings = nullptr,
                  LossFuse* lf = nullptr);

@@ -380,11 +380,45 @@ struct TrainCall {
     return WN_OK;
   }
 
+  // folded skip path: the gradient of the skip sum is never formed; the blocks contract dL/da = GF[0] with V(b)
+  const float* g_skipsum() const { return (p->c.use_skip && !tp.fold) ? ws + L.g_skipsum : nullptr; }
+
+  // what block_backward of block b reads and writes: gradients in the workspace, their max-abs slots (host only)
+  BlockGrads block_grads(int b) const {
+    const BlockInfo& bi = p->blocks[b];
+    const float* g_skip = g_skipsum();
+    BlockGrads bg;
+    memset(&bg, 0, sizeof(bg));
+    bg.defer = true;
+    for (int i = 0; i + 1 < p->LPB; ++i) bg.g_pi[i] = ws + L.GP[b][i];
+    if (tp.deep16)
+      for (int i = 0; i + 1 < p->LPB; ++i) bg.am_gp[i] = am_GP(b, i);
+    if (tp.drop) {
+      bg.drop_rate = e.drop_rate; bg.drop_key = wn_dropout_key(e.drop_seed, b, e.drop_step); bg.g_xd = ws + L.gxd;
+    }
+    // the last block's output gradient is identically zero when the head reads the skip sum
+    // (with the skip head nothing flows into the last block's output: GH[N] was zero-filled above.  It is
+    //  still passed as a gradient -- unless S == 0, where g_o is assembled from g_skip alone -- so that
+    //  the last block runs the same split-precision kernels as the others instead of the fp32 fallback
+    //  for the one-segment product)
+    bg.g_xout = (p->c.use_skip && b == p->N - 1 && p->S == 0) ? nullptr : ws + L.GH[b + 1];
+    bg.g_skip = g_skip;
+    bg.g_o_tmp = p->S == 0 ? ws + L.GO[b] : nullptr;
+    bg.g_u = ws + L.GU[b];
+    bg.g_x = tp.bwd_pairs() ? nullptr : ws + L.GH[b];     // (pairs: the next launch forms g_x of this block)
+    bg.dcb = (bi.has_cond && !cond_batched && F == 1) ? ws + L.dcb : nullptr;
+    bg.slab = slab;
+    bg.am_gxout = bg.g_xout ? am_GH(b + 1) : nullptr;
+    bg.am_gskip = g_skip ? am_gskip : nullptr;
+    bg.am_gu = am_GU(b); bg.am_gx = am_GH(b);
+    if (tp.fold) { bg.g_fold = ws + L.GF[0]; bg.fold_F0 = p->fold_F0; bg.am_gfold = am_GF(0); }
+    return bg;
+  }
+
   // ---- residual blocks, last to first: data gradients only, every g_u / g_x is kept for the deferred weight gradients ----
   int chain_backward() {
     int rc;
-    // folded skip path: the gradient of the skip sum is never formed; the blocks contract dL/da = GF[0] with V(b)
-    const float* g_skip = (p->c.use_skip && !tp.fold) ? ws + L.g_skipsum : nullptr;
+    const float* g_skip = g_skipsum();
     if (p->c.use_skip) {
       rc = wn_launch_fill(ws + L.GH[p->N], 0.f, rows * p->R, s);   // nothing flows into the last block output
       if (rc) return rc;
@@ -396,12 +430,13 @@ struct TrainCall {
       BlockPtrs k = block_ptrs(p, b, params, fragbase, B, T);
       deep16_ptrs(p, b, fragbase, k);
       const BlockInfo& bi = p->blocks[b];
+      const BlockBufs f = block_bufs(p, L, ws, b, rows, true, tp.drop);   // where the forward pass saved them
       if (pairk && b < p->N - 1) {
         const BlockPtrs k1 = block_ptrs(p, b + 1, params, fragbase, B, T);
         WnBwdPairArgs a;
         memset(&a, 0, sizeof(a));
         a.gu_in = ws + L.GU[b + 1]; a.gx_res = ws + L.GH[b + 2]; a.gf = ws + L.GF[0];
-        a.ag = ws + L.AG[b]; a.z = ws + L.Z + (int64_t)b * rows * p->Dp; a.ldz = p->Dp;
+        a.ag = f.AG; a.z = f.Z; a.ldz = f.ldz;
         a.gx_out = ws + L.GH[b + 1]; a.gu_out = ws + L.GU[b];
         a.wx16 = k1.G16x; a.wu16 = k.G16uf;
         a.am_gu_in = am_GU(b + 1); a.am_gf = am_GF(0); a.am_gx = am_GH(b + 1); a.am_gu = am_GU(b);
@@ -421,37 +456,7 @@ struct TrainCall {
         }
         continue;
       }
-      BlockBufs f;
-      memset(&f, 0, sizeof(f));
-      f.x = tp.drop ? ws + L.XD[b] : ws + L.H[b];
-      for (int i = 0; i + 1 < p->LPB; ++i) f.P[i] = ws + L.P[b][i];
-      f.AG = ws + L.AG[b];
-      f.Z = ws + L.Z + (int64_t)b * rows * p->Dp; f.ldz = p->Dp;
-      BlockGrads bg;
-      memset(&bg, 0, sizeof(bg));
-      bg.defer = true;
-      for (int i = 0; i + 1 < p->LPB; ++i) bg.g_pi[i] = ws + L.GP[b][i];
-      if (tp.deep16)
-        for (int i = 0; i + 1 < p->LPB; ++i) bg.am_gp[i] = am_GP(b, i);
-      if (tp.drop) {
-        bg.drop_rate = e.drop_rate; bg.drop_key = wn_dropout_key(e.drop_seed, b, e.drop_step); bg.g_xd = ws + L.gxd;
-      }
-      // the last block's output gradient is identically zero when the head reads the skip sum
-      // (with the skip head nothing flows into the last block's output: GH[N] was zero-filled above.  It is
-      //  still passed as a gradient -- unless S == 0, where g_o is assembled from g_skip alone -- so that
-      //  the last block runs the same split-precision kernels as the others instead of the fp32 fallback
-      //  for the one-segment product)
-      bg.g_xout = (p->c.use_skip && b == p->N - 1 && p->S == 0) ? nullptr : ws + L.GH[b + 1];
-      bg.g_skip = g_skip;
-      bg.g_o_tmp = p->S == 0 ? ws + L.GO[b] : nullptr;
-      bg.g_u = ws + L.GU[b];
-      bg.g_x = pairk ? nullptr : ws + L.GH[b];     // (pairs: the next launch forms g_x of this block)
-      bg.dcb = (bi.has_cond && !cond_batched && F == 1) ? ws + L.dcb : nullptr;
-      bg.slab = slab;
-      bg.am_gxout = bg.g_xout ? am_GH(b + 1) : nullptr;
-      bg.am_gskip = g_skip ? am_gskip : nullptr;
-      bg.am_gu = am_GU(b); bg.am_gx = am_GH(b);
-      if (tp.fold) { bg.g_fold = ws + L.GF[0]; bg.fold_F0 = p->fold_F0; bg.am_gfold = am_GF(0); }
+      const BlockGrads bg = block_grads(b);
       rc = block_backward(k, f, bg, s);
       if (rc) return rc;
       if (p->S == 0 && bg.g_xout == nullptr && g_skip) {
@@ -777,4 +782,48 @@ extern "C" int wn_vjp(wn_plan* p, const float* params, const float* x, const flo
                                     g_kind == 0 && p->c.head == WN_HEAD_CATEGORICAL, workspace + c.L.GF.back(), c.am_GF(c.nf - 1), s);
   if (rc) return rc;
   return c.backward_from_logits();
+}
+
+// block_fwd_path / block_bwd_path of block 0 as a model pass over B x T rows binds it, under the calling thread's knobs,
+// without dropout: one `name=value` token per decision, the convs of the stack in order (host only: the pointers are
+// offsets from a placeholder and never dereferenced)
+extern "C" int wn_debug_block_paths(const wn_plan* p, int32_t B, int32_t T, int32_t training, char* buf, int32_t len) {
+  if (!p || !buf || len < 1 || B < 1 || T < 1) return WN_E_INVALID;
+  static float placeholder[4];
+  float* const base = placeholder;
+  wn_exec none;                       // (a state of its own: no dropout)
+  TrainCall c{none};
+  c.bind(const_cast<wn_plan*>(p), base, base, B, T, base, base, nullptr);
+  c.fragbase = base + c.L.frag; c.slab = base + c.L.slab;
+  c.cond_batched = p->frag_condB >= 0;
+  c.tp = train_paths(p, none, c.L, c.rows);
+  static const char* const conv[] = {"planes", "rows16", "rows32"};
+  static const char* const gate[] = {"s128", "gen128", "two", "fused16", "fused32", "composed"};
+  static const char* const go[] = {"xout", "sum", "skip"};
+  static const char* const gu[] = {"fold", "pad", "image", "fp32", "zero"};
+  static const char* const am[] = {"none", "gxout", "gskip", "gfold"};
+  static const char* const gx[] = {"none", "g16x", "deep", "fp32+absmax", "fp32"};
+  auto list = [&](const BlkConv* v, int first, int end) {
+    std::string t;
+    for (int i = first; i < end; ++i) t += std::string(t.empty() ? "" : ",") + conv[v[i]];
+    return t.empty() ? std::string("none") : t;
+  };
+  // forward: FwdCall::blocks()
+  const FwdPaths fp = fwd_paths(p, none, B, T, training != 0, true, false, FWD_LOSS_NONE);
+  const WsLayout Lf = training ? c.L : make_layout(p, B, T, false);
+  BlockPtrs k = block_ptrs(p, 0, base, base + Lf.frag, B, T);
+  if (fp.deep16) deep16_ptrs(p, 0, base + Lf.frag, k);
+  if (fp.cond != FWD_COND_NONE) k.cb = base + Lf.cb;
+  const BlockFwdPath f = block_fwd_path(k, block_bufs(p, Lf, base, 0, c.rows, training != 0, false));
+  std::string out = "inner=" + list(f.inner, 0, f.ninner) + " gate=" + gate[f.gate];
+  if (training) {
+    // backward: TrainCall::chain_backward()
+    BlockPtrs kb = block_ptrs(p, 0, base, c.fragbase, B, T);
+    deep16_ptrs(p, 0, c.fragbase, kb);
+    const BlockBwdPath b = block_bwd_path(kb, block_bufs(p, c.L, base, 0, c.rows, true, false), c.block_grads(0));
+    out += std::string(" go=") + go[b.go] + " gu=" + gu[b.gu] + " gu_pad=" + (b.gu_pad ? "1" : "0") + " gu_am=" + am[b.gu_am[0]] + "," +
+           am[b.gu_am[1]] + " data=" + list(b.data, 1, p->LPB) + " gx=" + gx[b.gx] + " drop=" + (b.drop ? "1" : "0");
+  }
+  snprintf(buf, (size_t)len, "%s", out.c_str());
+  return WN_OK;
 }
