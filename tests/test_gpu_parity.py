@@ -825,6 +825,42 @@ def test_forward_range_guard_falls_back_to_exact_fp32(name):
   assert _lib.lib().wn_debug_value(1) == 0                       # the exact-fp32 switch is restored
 
 
+def test_forward_range_guard_deferred_check():
+  """range_check = False: call() reads nothing back and repeats nothing -- its result is the split-precision pass's, bytes
+  of wn_forward called directly -- and range_tripped_last_forward() answers afterwards from the guard float the pass
+  left.  Repeating the pass inside exact_fp32() then gives the bytes of a guarded call(); an in-range pass on the same
+  workspace clears the answer.  The input conv's bias puts the residual stream at +-1e5, as above."""
+  from wavenets_amd import _lib
+  kw = dict(MODEL_CASES['cat_r64'])
+  ocfg, params, model = make_pair(seed=6, **kw)
+  tripping = list(params)
+  big = torch.where(torch.arange(params[1].numel()) % 2 == 0, 1.0e5, -1.0e5).to(params[1].dtype)
+  tripping[1] = params[1] + big                                   # causal/bias
+  model.set_weights([p.numpy() for p in tripping])
+  B, T = 2, 64
+  x = _inputs(kw, B, T, seed=3)[0].to(dev()).contiguous()
+  bits = lambda t: t.contiguous().view(torch.int32).cpu()
+  guarded = model(x)                                              # range_check = True: tripped, repeated in exact fp32
+  # the split-precision pass itself, on a workspace of its own
+  L = _lib.lib()
+  ws = torch.empty(int(L.wn_plan_workspace_floats(model._plan, B, T, 0)), dtype=torch.float32, device=dev())
+  raw = torch.empty_like(guarded)
+  _lib.check(L.wn_forward(model._plan, _lib.ptr(model.flat_params), _lib.ptr(x), None, B, T, _lib.ptr(raw), None,
+                          _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+  assert not torch.equal(bits(raw), bits(guarded))
+  model.range_check = False
+  unchecked = model(x)
+  assert torch.equal(bits(unchecked), bits(raw))                  # no rerun
+  assert model.range_tripped_last_forward() is True
+  with model.exact_fp32():
+    again = model(x)
+  assert torch.equal(bits(again), bits(guarded))
+  assert L.wn_debug_value(1) == 0
+  model.set_weights([p.numpy() for p in params])                  # in range: the same workspace, the same slot
+  assert torch.isfinite(model.logits(x)).all()
+  assert model.range_tripped_last_forward() is False
+
+
 def test_forward_range_guard_quiet_for_tiny_activations():
   """A residual stream of 1e-6 loses nothing that matters (absolute error of the fp16 lo part <= 3e-8): no fallback."""
   kw = dict(MODEL_CASES['cat_r64'])
