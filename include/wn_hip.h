@@ -156,7 +156,7 @@ int wn_debug_fwd_paths(const wn_plan* p, int32_t B, int32_t T, int32_t training,
 /* test / diagnosis hook, host only: which kernels block 0 takes in a model pass over (B, T) under the calling thread's
  * switches, without dropout -- the decisions the launches of the block's forward and (training != 0) backward read:
  *   inner=<planes|rows16|rows32 of every non-gated conv, in order, comma separated; none>
- *   gate=s128|gen128|two|fused16|fused32|composed
+ *   gate=s128|two|fused16|fused32|composed
  *   go=xout|sum|skip  gu=fold|pad|image|fp32|zero  gu_pad=0|1  gu_am=<none|gxout|gskip|gfold>,<...>
  *   data=<planes|rows16|rows32 of the backward-data product of conv 1.., comma separated; none>
  *   gx=none|g16x|deep|fp32+absmax|fp32  drop=0|1 */

@@ -69,9 +69,8 @@ BlockFwdPath block_fwd_path(const BlockPtrs& k, const BlockBufs& f) {
   // ring and keeps u and z on chip (wn_layer16s.hip)
   if (k.F16n && k.F16r && k.depth == 1 && k.Cc == 0 && hc == k.R && k.Cin == k.R && f.ldz % 4 == 0 && wn_debug_get(1) != 1 &&
       wn_layer_fwd_s128_supported(k.R, k.D, k.KS) && (int64_t)rows * k.R * 4 < ((int64_t)1 << 32)) {
-    // one row per utterance (a queued-generation step): the whole block in one workgroup with every weight fragment
-    // requested up front instead of the streamed pipeline (wn_gen128.hip, same arithmetic)
-    p.gate = (k.T == 1 && f.xt[0] && f.xt[1] && !f.AG && wn_gen_block128_supported(k.R, k.D, k.KS)) ? BLK_GATE_GEN128 : BLK_GATE_S128;
+    // (also one block of a queued-generation step that no chain of wn_gen128.hip takes: T == 1 with the taps in f.xt[])
+    p.gate = BLK_GATE_S128;
   } else if (k.F16g && k.F16r && k.Cc == 0 && !k.cb && !f.O && hc == k.R && f.ldz % 4 == 0 && wn_debug_get(1) != 1) {
     // wider blocks (or other kernel sizes) as [gated conv + gate] -> [1x1 + residual], two split-precision contractions,
     // ahead of the exact-fp32 one-kernel forward
@@ -113,11 +112,11 @@ WnLayerFwdArgs layer_fwd_args(const BlockPtrs& k, const BlockBufs& f, const floa
   return a;
 }
 
-// streamed weights (depth 1, kernel size 2): wn_layer16s.hip, or its one-row form wn_gen128.hip
-int fwd_streamed(const BlockPtrs& k, const BlockBufs& f, BlkGate gate, const float* h, hipStream_t s) {
+// streamed weights (depth 1, kernel size 2): wn_layer16s.hip
+int fwd_streamed(const BlockPtrs& k, const BlockBufs& f, const float* h, hipStream_t s) {
   WnLayerFwdArgs a = layer_fwd_args(k, f, h);
   a.frag_d = k.F16n; a.frag_r = k.F16r;
-  return gate == BLK_GATE_GEN128 ? wn_launch_gen_block128(a, s) : wn_launch_layer_fwd_s128(a, s);
+  return wn_launch_layer_fwd_s128(a, s);
 }
 
 // LDS-resident weights: fp16 hi|lo images, or the exact-fp32 MFMA kernel on the fp32 fragments
@@ -192,7 +191,7 @@ int block_forward(const BlockPtrs& k, const BlockBufs& f, hipStream_t s) {
     h = f.P[i]; hc = k.D;
   }
   switch (p.gate) {
-    case BLK_GATE_S128: case BLK_GATE_GEN128: return fwd_streamed(k, f, p.gate, h, s);
+    case BLK_GATE_S128: return fwd_streamed(k, f, h, s);
     case BLK_GATE_TWO: return fwd_two(k, f, h, hc, s);
     case BLK_GATE_FUSED16: case BLK_GATE_FUSED32: return fwd_fused(k, f, p.gate, h, s);
     case BLK_GATE_COMPOSED: break;

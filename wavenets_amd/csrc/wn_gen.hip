@@ -69,19 +69,14 @@ __device__ __forceinline__ void gn_pre_body(const WnGenStepArgs& a, int tile, in
 #pragma unroll
   for (int j = 0; j < JU; ++j)
 #pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(bias_d + 32 * j + 8 * rq + 4 * h);
-      u[j][4 * rq + 0] = bv.x; u[j][4 * rq + 1] = bv.y; u[j][4 * rq + 2] = bv.z; u[j][4 * rq + 3] = bv.w;
-    }
+    for (int rq = 0; rq < 4; ++rq)
+      set_quad(u[j], rq, *reinterpret_cast<const f32x4*>(bias_d + 32 * j + 8 * rq + 4 * h));
   if (blk.cb_off >= 0) {
     const float* cbp = a.ws + blk.cb_off + (int64_t)ur * 2 * D + 4 * h;
 #pragma unroll
     for (int j = 0; j < JU; ++j)
 #pragma unroll
-      for (int rq = 0; rq < 4; ++rq) {
-        const f32x4 cv = *reinterpret_cast<const f32x4*>(cbp + 32 * j + 8 * rq);
-        u[j][4 * rq + 0] += cv.x; u[j][4 * rq + 1] += cv.y; u[j][4 * rq + 2] += cv.z; u[j][4 * rq + 3] += cv.w;
-      }
+      for (int rq = 0; rq < 4; ++rq) add_quad(u[j], rq, *reinterpret_cast<const f32x4*>(cbp + 32 * j + 8 * rq));
   }
   wn_static_for<KS0>([&](auto sc) {
     constexpr int ks = decltype(sc)::value;
@@ -99,7 +94,7 @@ __device__ __forceinline__ void gn_pre_body(const WnGenStepArgs& a, int tile, in
   for (int j = 0; j < JU; ++j)
 #pragma unroll
     for (int rq = 0; rq < 4; ++rq)
-      dst[(j * 4 + rq) * 64] = f32x4{u[j][4 * rq + 0], u[j][4 * rq + 1], u[j][4 * rq + 2], u[j][4 * rq + 3]};
+      dst[(j * 4 + rq) * 64] = get_quad(u[j], rq);
 }
 template <int R32, int D32, int KS>
 __global__ __launch_bounds__(64) void wn_gen_pre_kernel(WnGenStepArgs a) {
@@ -132,25 +127,6 @@ __global__ __launch_bounds__(64) void wn_gen_pre_kernel(WnGenStepArgs a) {
 // idle), the conv1 waves in phase A, the skip waves in phases A and B.  LDS only holds the exchange buffers (x operands,
 // 2 x z operands) and a copy of the block table.
 #define WN_GEN_CHAIN_MAX_BLOCKS 128
-// acc += W^T b over NK k-steps (hi|lo B operands in LDS, 2 KB a k-step), the three products of a k-step in the order of
-// the training kernels.  The operands of k-step k + 1 are requested BEFORE the products of k-step k are issued: written
-// the plain way the compiler reads, waits, multiplies, reads, ... and every k-step pays an LDS round trip (measured on
-// the conv1 waves: 1220 -> 550 cycles for the 12 products).
-template <int NK>
-__device__ __forceinline__ void gn_mac(f32x16& acc, const h8 (&w)[NK][2], const h8* zl) {
-  h8 bh[2], bl[2];
-  bh[0] = zl[0];
-  bl[0] = zl[64];
-  wn_static_for<NK>([&](auto kc) {
-    constexpr int ks = decltype(kc)::value;
-    if constexpr (ks + 1 < NK) {
-      bh[(ks + 1) & 1] = zl[((ks + 1) * 2 + 0) * 64];
-      bl[(ks + 1) & 1] = zl[((ks + 1) * 2 + 1) * 64];
-      __builtin_amdgcn_sched_barrier(0);            // keep the two reads above the products below
-    }
-    mfma3(w[ks][0], w[ks][1], bh[ks & 1], bl[ks & 1], acc);
-  });
-}
 #define WN_GEN_HELPERS_PER_XCD 2
 // The prefetches are issued as inline asm and waited for by hand: the compiler's own s_waitcnt placement drains vmcnt to 0
 // at every use inside a loop, which would cut the distance of a 3-blocks-ahead fetch to one block.  vmcnt retires in
@@ -241,10 +217,8 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
   auto put_xop = [&](const f32x16& x, int j) {
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
-      const f32x4 q0 = {x[8 * hf + 0], x[8 * hf + 1], x[8 * hf + 2], x[8 * hf + 3]};
-      const f32x4 q1 = {x[8 * hf + 4], x[8 * hf + 5], x[8 * hf + 6], x[8 * hf + 7]};
       h8 bh, bl;
-      split8(q0, q1, bh, bl);
+      split8(get_quad(x, 2 * hf), get_quad(x, 2 * hf + 1), bh, bl);
       h8* dst = reinterpret_cast<h8*>(xop + (2 * j + hf) * 2048) + lane;
       dst[0] = bh;
       dst[64] = bl;
@@ -313,14 +287,12 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
           for (int rq = 0; rq < 4; ++rq) gn_landed(u0q[s][rq]);
           f32x16 u;
 #pragma unroll
-          for (int rq = 0; rq < 4; ++rq) {
-            u[4 * rq + 0] = u0q[s][rq].x; u[4 * rq + 1] = u0q[s][rq].y; u[4 * rq + 2] = u0q[s][rq].z; u[4 * rq + 3] = u0q[s][rq].w;
-          }
-          gn_mac<KSR>(u, wa[s], reinterpret_cast<const h8*>(xop) + lane);
+          for (int rq = 0; rq < 4; ++rq) set_quad(u, rq, u0q[s][rq]);
+          mac_lds<0, KSR>(u, wa[s], reinterpret_cast<const h8*>(xop) + lane);
           if (wave == 0) GN_TS(0, b, 2);
           // the gate: accumulators 0..7 are filter channels 16 w + {4h.., 8 + 4h..}, 8..15 their gate channels
-          const f32x4 f0 = {u[0], u[1], u[2], u[3]}, f1 = {u[4], u[5], u[6], u[7]};
-          const f32x4 g0 = {u[8], u[9], u[10], u[11]}, g1 = {u[12], u[13], u[14], u[15]};
+          const f32x4 f0 = get_quad(u, 0), f1 = get_quad(u, 1);
+          const f32x4 g0 = get_quad(u, 2), g1 = get_quad(u, 3);
           f32x4 z0, z1;
           z0.x = wn_tanh_fast(f0.x) * wn_sigmoid_fast(g0.x); z0.y = wn_tanh_fast(f0.y) * wn_sigmoid_fast(g0.y);
           z0.z = wn_tanh_fast(f0.z) * wn_sigmoid_fast(g0.z); z0.w = wn_tanh_fast(f0.w) * wn_sigmoid_fast(g0.w);
@@ -433,7 +405,7 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
             float* dst = a.ws + cur.ring_off + ((int)((unsigned)(int)a.tau % (unsigned)cur.nslots) * a.B + utt) * R + 32 * cw + 4 * h;
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq)
-              *reinterpret_cast<f32x4*>(dst + 8 * rq) = f32x4{x[4 * rq + 0], x[4 * rq + 1], x[4 * rq + 2], x[4 * rq + 3]};
+              *reinterpret_cast<f32x4*>(dst + 8 * rq) = get_quad(x, rq);
           }
           if (cw == 0) GN_TS(1, b, 0);
           GN_BARRIER();                               // (2) z operands visible
@@ -444,11 +416,8 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
           for (int ks = 0; ks < KS2; ++ks) { gn_landed(wc[s][ks][0]); gn_landed(wc[s][ks][1]); }
           f32x16 o;
 #pragma unroll
-          for (int rq = 0; rq < 4; ++rq) {
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(bias_l + b * R + 32 * cw + 8 * rq + 4 * h);
-            o[4 * rq + 0] = bv.x; o[4 * rq + 1] = bv.y; o[4 * rq + 2] = bv.z; o[4 * rq + 3] = bv.w;
-          }
-          gn_mac<KS2>(o, wc[s], reinterpret_cast<const h8*>(zop + (b & 1) * ZOP_BYTES) + lane);
+          for (int rq = 0; rq < 4; ++rq) set_quad(o, rq, *reinterpret_cast<const f32x4*>(bias_l + b * R + 32 * cw + 8 * rq + 4 * h));
+          mac_lds<0, KS2>(o, wc[s], reinterpret_cast<const h8*>(zop + (b & 1) * ZOP_BYTES) + lane);
 #pragma unroll
           for (int r = 0; r < 16; ++r) x[r] = a.residual ? o[r] + x[r] : o[r];
           if (b + 1 < nblocks) put_xop(x, cw);
@@ -470,7 +439,7 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
       float* dst = a.ws + a.hrow_off + (int64_t)utt * R + 32 * cw + 4 * h;
 #pragma unroll
       for (int rq = 0; rq < 4; ++rq)
-        *reinterpret_cast<f32x4*>(dst + 8 * rq) = f32x4{x[4 * rq + 0], x[4 * rq + 1], x[4 * rq + 2], x[4 * rq + 3]};
+        *reinterpret_cast<f32x4*>(dst + 8 * rq) = get_quad(x, rq);
     }
     if (a.guard) wn_guard_publish_over(a.guard, live ? xm : 0.f);     // every step; an atomic only beyond the limit
   } else {
@@ -499,7 +468,7 @@ __global__ __launch_bounds__(64 * (2 * D32 + R32 + 4)) void wn_gen_chain3_kernel
       for (int ks = 0; ks < KS2; ++ks) { gn_landed(w[ks][0]); gn_landed(w[ks][1]); }
     };
     auto mac = [&](f32x16& acc, const h8 (&w)[KS2][2], int half) {
-      gn_mac<KS2>(acc, w, reinterpret_cast<const h8*>(zop + half * ZOP_BYTES) + lane);
+      mac_lds<0, KS2>(acc, w, reinterpret_cast<const h8*>(zop + half * ZOP_BYTES) + lane);
     };
     f32x16 acc0, acc1;
 #pragma unroll

@@ -80,7 +80,7 @@ GenLayout gen_layout(const wn_plan* p, int B, bool queued) {
     G.hrow1 = cv.take((int64_t)B * 2 * p->D);
     G.dummy = cv.take((int64_t)B * p->R);
     G.u0 = cv.take(wn_gen_u0_floats(B, p->N, p->D));
-    if (p->LPB == 1 && wn_gen_block128_supported(p->R, p->D, p->KS)) G.relay = cv.take(wn_gen_relay128_floats(B, p->N));
+    if (p->LPB == 1 && wn_gen_chain128_supported(p->R, p->D, p->KS)) G.relay = cv.take(wn_gen_relay128_floats(B, p->N));
     for (size_t i = 0; i + 1 < p->finals.size(); ++i) G.HArow.push_back(cv.take((int64_t)B * p->finals[i].cout));
   }
   G.total = cv.pos;

@@ -243,10 +243,6 @@ size_t wn_frag16_floats(int I, int KK);
 int wn_layer_fwd_s128_supported(int R, int D, int KS);
 int wn_launch_layer_fwd_s128(const WnLayerFwdArgs& a, hipStream_t s);
 int wn_launch_layer_fwd(const WnLayerFwdArgs& a, hipStream_t s);
-// one queued-generation step of a 128-channel block, rows = utterances (wn_gen128.hip): same arguments as the streamed
-// forward with T == 1 and both taps given as xt[0], xt[1]
-int wn_gen_block128_supported(int R, int D, int KS);
-int wn_launch_gen_block128(const WnLayerFwdArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- fused generation step (wn_gen.hip)
 struct WnGenBlock {
@@ -305,6 +301,7 @@ struct WnGen128Args {
   unsigned long long* ts;          // phase stamps (knob 24) or null
   int32_t mute_block;              // fault injection (knob 3): this block withholds its hand-over; -1 = none
 };
+int wn_gen_chain128_supported(int R, int D, int KS);   // the block shape both forms take: R = D = 128, kernel size 2
 int wn_launch_gen_chain128(const WnGen128Args& a, hipStream_t s);
 int wn_launch_gen_relay128(const WnGen128Args& a, hipStream_t s);
 int64_t wn_gen_relay128_floats(int B, int nblocks);

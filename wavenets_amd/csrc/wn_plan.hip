@@ -279,7 +279,7 @@ GenPaths gen_paths(const wn_plan* p, int B, int length, int cu_count, bool relay
   const bool chain64 = p->fused16_ok && p->LPB == 1 && split && fits32 && wn_gen_blocks_supported(p->R, p->D, p->KS) &&
                        p->N <= wn_gen_chain_max_blocks();
   // 128-channel blocks: every block of a step in one launch of wn_gen_chain128_kernel
-  const bool chain128 = !chain64 && p->LPB == 1 && p->Dp == p->D && wn_gen_block128_supported(p->R, p->D, p->KS) &&
+  const bool chain128 = !chain64 && p->LPB == 1 && p->Dp == p->D && wn_gen_chain128_supported(p->R, p->D, p->KS) &&
                         !p->blocks.empty() && p->blocks[0].f16nat >= 0 && p->blocks[0].conv1.frag16 >= 0 && split && fits32;
   // ... as a relay over one workgroup per block (wn_gen_relay128_kernel) unless knob 2 asks for the single workgroup
   // (only while every workgroup of a step can be resident at once -- one per CU: a workgroup waits for its predecessor

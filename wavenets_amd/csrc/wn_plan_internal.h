@@ -160,9 +160,9 @@ struct FwdPaths {
 // a conv of the dilated stack, forward or backward data: the streamed kernel's second form with the taps as shifted planes |
 // rows GEMM on a split-precision image | rows GEMM in exact fp32
 enum BlkConv : uint8_t { BLK_CONV_PLANES, BLK_CONV_ROWS16, BLK_CONV_ROWS32 };
-// the gated conv + 1x1: streamed one-kernel forward (wn_layer16s.hip) | its one-row form (wn_gen128.hip) | two split-precision
-// contractions | LDS-resident one-kernel forward on fp16 images | ... in exact fp32 | rows GEMM -> gate kernel -> rows GEMM
-enum BlkGate : uint8_t { BLK_GATE_S128, BLK_GATE_GEN128, BLK_GATE_TWO, BLK_GATE_FUSED16, BLK_GATE_FUSED32, BLK_GATE_COMPOSED };
+// the gated conv + 1x1: streamed one-kernel forward (wn_layer16s.hip) | two split-precision contractions | LDS-resident
+// one-kernel forward on fp16 images | ... in exact fp32 | rows GEMM -> gate kernel -> rows GEMM
+enum BlkGate : uint8_t { BLK_GATE_S128, BLK_GATE_TWO, BLK_GATE_FUSED16, BLK_GATE_FUSED32, BLK_GATE_COMPOSED };
 struct BlockFwdPath {
   int ninner = 0;                 // non-gated convs this call runs (none when the queued generation step ran them: pre_done)
   BlkConv inner[16] = {};

@@ -2,9 +2,11 @@
 // plus lo = fp16(v - hi), optionally scaled by an exact power of two of its running max-abs, and a product is three
 // v_mfma_f32_32x32x16_f16 into an fp32 accumulator, always in the order a_lo*b_hi, a_hi*b_lo, a_hi*b_hi.  This sets the
 // accuracy contract of both math modes, and the generation kernels reproduce the training-forward kernels bit for bit
-// only because both go through these definitions.  Also here: the 16-byte global load, LDS-DMA by inline assembly and the
-// store of a 32 x 32 accumulator tile as whole row segments from a scalar base (store_tile), or of a row of such tiles as
-// buffer stores on a descriptor that ends behind the last valid row (wn_store_tile: block forward and backward pair kernels).
+// only because both go through these definitions.  For the generation kernels (wn_gen.hip, wn_gen128.hip) also the quads
+// of a D-layout accumulator and the products over hi|lo operands in LDS (mac_lds).  Also here: the 16-byte global loads,
+// LDS-DMA by inline assembly and the store of a 32 x 32 accumulator tile as whole row segments from a scalar base
+// (store_tile), or of a row of such tiles as buffer stores on a descriptor that ends behind the last valid row
+// (wn_store_tile: block forward and backward pair kernels).
 #pragma once
 #include <hip/hip_fp16.h>
 
@@ -98,6 +100,42 @@ __device__ __forceinline__ void pow2_scale(float m, float& sc, float& inv) {
 __device__ __forceinline__ f32x4 ldg4(const float* p) { return *(const __attribute__((address_space(1))) f32x4*)(p); }
 __device__ __forceinline__ f32x4 ldg4(const __attribute__((address_space(1))) char* p) {
   return *(const __attribute__((address_space(1))) f32x4*)p;
+}
+// ... of eight halves: one hi or lo weight fragment of a lane (generation kernels)
+__device__ __forceinline__ h8 ldg_h8(const void* p) { return *(const __attribute__((address_space(1))) h8*)(p); }
+
+// Quad rq (0..3) of a D-layout accumulator tile: a lane's values 4 rq .. 4 rq + 3 are four consecutive channels
+// (8 rq + 4 h .. of the tile's 32), so a quad is what one 16-byte access of a bias, a row or an operand piece holds.
+__device__ __forceinline__ f32x4 get_quad(const f32x16& v, int rq) {
+  return f32x4{v[4 * rq + 0], v[4 * rq + 1], v[4 * rq + 2], v[4 * rq + 3]};
+}
+__device__ __forceinline__ void set_quad(f32x16& v, int rq, const f32x4& q) {
+  v[4 * rq + 0] = q.x; v[4 * rq + 1] = q.y; v[4 * rq + 2] = q.z; v[4 * rq + 3] = q.w;
+}
+__device__ __forceinline__ void add_quad(f32x16& v, int rq, const f32x4& q) {
+  v[4 * rq + 0] += q.x; v[4 * rq + 1] += q.y; v[4 * rq + 2] += q.z; v[4 * rq + 3] += q.w;
+}
+
+// acc += W^T b over k-steps K0 .. K0 + NK - 1: fragments w[k][hi, lo] in registers, hi|lo B operands in LDS (2 KB a k-step;
+// bl = this lane's hi operand of k-step 0, the lo operand 64 further), the three products of a k-step in the order of the
+// training kernels.  The operands of k-step k + 1 are requested BEFORE the products of k-step k are issued: written the
+// plain way the compiler reads, waits, multiplies, reads, ... and every k-step pays an LDS round trip (measured on the
+// conv1 waves of wn_gen_chain3_kernel: 1220 -> 550 cycles for the 12 products).
+template <int K0, int NK, int NW>
+__device__ __forceinline__ void mac_lds(f32x16& acc, const h8 (&w)[NW][2], const h8* bl) {
+  static_assert(K0 + NK <= NW, "k-steps beyond the fragments");
+  h8 bh[2], blo[2];
+  bh[0] = bl[(K0 * 2 + 0) * 64];
+  blo[0] = bl[(K0 * 2 + 1) * 64];
+  wn_static_for<NK>([&](auto kc) {
+    constexpr int ks = decltype(kc)::value;
+    if constexpr (ks + 1 < NK) {
+      bh[(ks + 1) & 1] = bl[((K0 + ks + 1) * 2 + 0) * 64];
+      blo[(ks + 1) & 1] = bl[((K0 + ks + 1) * 2 + 1) * 64];
+      __builtin_amdgcn_sched_barrier(0);            // keep the two reads above the products below
+    }
+    mfma3(w[K0 + ks][0], w[K0 + ks][1], bh[ks & 1], blo[ks & 1], acc);
+  });
 }
 
 // LDS-DMA of 16 bytes per lane: global address = scalar base + 32-bit lane offset, LDS address = M0 + lane * 16.

@@ -798,7 +798,7 @@ extern "C" int wn_debug_block_paths(const wn_plan* p, int32_t B, int32_t T, int3
   c.cond_batched = p->frag_condB >= 0;
   c.tp = train_paths(p, none, c.L, c.rows);
   static const char* const conv[] = {"planes", "rows16", "rows32"};
-  static const char* const gate[] = {"s128", "gen128", "two", "fused16", "fused32", "composed"};
+  static const char* const gate[] = {"s128", "two", "fused16", "fused32", "composed"};
   static const char* const go[] = {"xout", "sum", "skip"};
   static const char* const gu[] = {"fold", "pad", "image", "fp32", "zero"};
   static const char* const am[] = {"none", "gxout", "gskip", "gfold"};
