@@ -559,6 +559,65 @@ int wn_generate_admit_origin(wn_plan* p, const float* params, const float* windo
  * queued == 0; a plan without conditioning; condition frames armed; a workspace too small; a workspace not primed. */
 int wn_generate_set_condition(wn_plan* p, const float* params, const float* cond, int32_t B, int32_t queued,
                               float* workspace, int64_t ws_floats, void* stream);
+/* ---- frame schedules of queued generation: a schedule per row, advanced on the device ----
+ * A request's bias rows are computed once for all of its frames, into a table the request keeps; during the step loop a
+ * small copy kernel moves every scheduled row's current frame into the compact table cb[N][B][2D] of the workspace, which
+ * is all the step kernels ever read (they are the kernels of the calls without a schedule).
+ *
+ * wn_generate_frames_floats(plan, rows): the floats of a frame table for `rows` condition rows (requests x frames): the bias
+ *   rows [N][rows][2D] and, behind them, the scratch of the conditioning phase at that row count.  0 for a null plan, a plan
+ *   without conditioning or rows < 1.
+ * wn_generate_frames_build: the conditioning phase (mapping stack, every block's conv_cond, biases, scatter) over the k * F
+ *   rows of cond (k, F, cond_inputs), into `table` (device, 16-byte aligned, >= wn_generate_frames_floats(plan, k * F)
+ *   floats): row (j, f) of block n is the 2D floats at table + (n * k * F + j * F + f) * 2D, so request j's record is
+ *   rows = table + j * F * 2D with block_stride = k * F * 2D.  It runs in the calling thread's math mode (wn_debug_set(1, .)).
+ *   The weight images it reads are those a priming pass left in `workspace`, a queued generation workspace of batch size B
+ *   in which a sequence has begun with these parameters (any queued call that begins a sequence primes): read only --
+ *   nothing in any workspace is written.  That the workspace has been primed is the caller's word: unlike
+ *   wn_generate_set_condition this call does not ask for the calling state's last primed workspace, so that a session
+ *   can build a request's table while other sequences run on the same state; an unprimed workspace gives rows without
+ *   meaning and no fault (ws_floats is checked against the layout of B).  Every row is bit for bit the row
+ *   wn_generate_set_condition writes into cb for that condition alone: which kernel a product takes does not depend on the
+ *   row count.
+ *   WN_E_INVALID, before the device is touched, the message naming the cause and its numbers: a null plan / params / cond /
+ *   table / workspace; k < 1 or F < 1; k * F * blocks * 2D beyond 2^31 - 1; a plan without conditioning; condition frames
+ *   armed (wn_plan_set_cond_frames); table not aligned to 16 bytes; table_floats too small; B < 1; a workspace too small.
+ * struct wn_frame_row: the schedule of one row of the batch.  rows == NULL: the row is off the schedule and its cb rows are
+ *   left as they are.  Otherwise block n's row of frame f is the 2D floats at rows + n * block_stride + f * 2D; origin is the
+ *   sequence index of the row's sample 0, and the step that emits sample t uses frame (t - origin) / hop (frame 0 where
+ *   t < origin).  The table belongs to the caller and must outlive every call made while the record is armed; the session
+ *   has no table of its own, no cap on frames and copies nothing at admission.
+ * wn_plan_arm_gen_frames(plan, records (host, B of them), B) arms the calling thread's execution state, in the manner of
+ *   wn_plan_arm_row_weights; records == NULL or B == 0 disarms.  Host only: the library copies the records, and uploads
+ *   them inside the first queued call that needs them (a blocking copy behind a stream synchronise, made only when the
+ *   records differ from those it uploaded last).  The device copy is one per execution state, like the cached block
+ *   table of the chains, and the upload waits for the CALLING stream alone: sequences that share a state must run on one
+ *   stream (or take a wn_exec each), and two sessions that alternate on one state pay the synchronise and the upload at
+ *   every change of hands.  While armed, the queued forms of wn_generate_chunk,
+ *   wn_generate_rows_chunk[_origin] and wn_generate_rows_begin[_origin]
+ *     launch the copy kernel in front of whichever launch reads cb for step t -- the head launch of step t - 1 where that
+ *     launch carries the next step's pre work, the chain, relay or first block launch of step t otherwise -- at the call's
+ *     first step behind the priming pass, and at every later step t of the call where some scheduled row has
+ *     (t - origin) % hop == 0 (computed on the host from the records).  The priming pass of a call that begins a sequence
+ *     takes `cond` as ever (a frame schedule hands it frame 0);
+ *     return WN_E_INVALID, before anything is launched, when a scheduled row would need a frame >= frames at one of the
+ *     call's steps: the message names the row, its frames and its hop;
+ *     return WN_E_INVALID when armed with another B than the call's, and for a sliding-window call (queued == 0).
+ *   wn_generate_admit[_origin] ignores the armed schedule (its scratch pass at k rows takes cond).
+ *   With nothing armed every entry point queues exactly the launches it queues without this entry point.
+ *   WN_E_INVALID: a null plan; B < 0; records != NULL on a plan without conditioning or while condition frames are armed; a
+ *   scheduled record with frames < 1, hop < 1, or block_stride < frames * 2D; the message names the row. */
+typedef struct wn_frame_row {
+  const float* rows;
+  int64_t block_stride;
+  int64_t origin;
+  int32_t frames;
+  int32_t hop;
+} wn_frame_row;
+int64_t wn_generate_frames_floats(const wn_plan* p, int64_t rows);
+int wn_generate_frames_build(wn_plan* p, const float* params, const float* cond, int32_t k, int32_t F, float* table,
+                             int64_t table_floats, const float* workspace, int64_t ws_floats, int32_t B, void* stream);
+int wn_plan_arm_gen_frames(wn_plan* p, const wn_frame_row* records, int32_t B);
 int64_t wn_generate_workspace_floats(const wn_plan* p, int32_t B, int32_t queued);
 /* The one contiguous part of the generation workspace that steps write and a continuation reads, as a float offset and a
  * float count.  queued: from the raw-sample slots to the end of the layout (rings, inner rings, per-step rows, partial

@@ -2,10 +2,12 @@
 the globally conditioned network, of the same network with conditioning='local' at hop = 320 (F = 50) and hop = 32
 (F = 500), and the frame-sum kernel's own time and GB/s (device time from torch.profiler).
 
-  python tools/time_local_cond.py [--steps 50] [--warmup 10] [--global-only] [--generation]
+  python tools/time_local_cond.py [--steps 50] [--warmup 10] [--global-only] [--generation [--hop 256]]
 
---generation times the queued generation step instead: 2048 samples at B = 8, the global network against the local one
-on a frame schedule of hop = 256 (eight table rewrites), three alternating runs.
+--generation times the queued generation step instead: 2048 samples at B = 8, three alternating runs of the global
+network, the local one on a frame schedule of --hop samples a frame (every row crosses its boundaries at the same steps),
+and the local one with unaligned rows: row j admitted by admit_own_clock hop / 8 * j samples into
+a frame, with frames of its own, so the eight rows cross their boundaries at eight different steps.
 
 --global-only times the global network alone: the form a library built before local conditioning can run (WN_HIP_LIB)."""
 import argparse
@@ -23,6 +25,7 @@ ap.add_argument('--steps', type=int, default=50)
 ap.add_argument('--warmup', type=int, default=10)
 ap.add_argument('--global-only', action='store_true')
 ap.add_argument('--generation', action='store_true')
+ap.add_argument('--hop', type=int, default=256)
 args = ap.parse_args()
 
 dev = torch.device('cuda', 0)
@@ -51,11 +54,28 @@ def build(conditioning):
 
 
 if args.generation:
-  n, hop = 2048, 256
+  n, hop = 2048, args.hop
   gl, lo = build('global'), build('local')
   held = torch.rand(B, CIN, generator=g).to(dev)
-  frames = torch.rand(B, n // hop, CIN, generator=g).to(dev)
+  frames = torch.rand(B, -(-n // hop), CIN, generator=g).to(dev)
   w = x[:, :gl.receptive_field].contiguous()
+  shift = max(1, hop // 8)
+  lead = hop + B * shift                               # samples the session makes before the timed ones
+  long_frames = torch.rand(B, -(-(lead + n) // hop) + 1, CIN, generator=g).to(dev)
+  own = -(-(n + B * shift) // hop) + 1                 # frames a request brings: its timed samples and its lead inside the session
+
+  def unaligned():
+    """A session whose row j was admitted j * shift samples into a frame of the session; returns its timed n samples' time."""
+    s = lo.generation_session(sample=w, condition=long_frames, hop=hop, use_queues=True, stream=list(range(B)))
+    s.generate(hop)
+    for j in range(B):
+      s.generate(shift)
+      s.admit_own_clock(j, w[j:j + 1], condition=long_frames[j:j + 1, :own], stream=[100 + j])
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    s.generate(n)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n * 1e6
 
   def us_per_step(fn):
     fn()                                               # (builds the model, primes the caches)
@@ -67,7 +87,11 @@ if args.generation:
   for run in range(3):
     a = us_per_step(lambda: gl.generate(n, sample=w, condition=held, use_queues=True, seed=1))
     b = us_per_step(lambda: lo.generate(n, sample=w, condition=frames, hop=hop, use_queues=True, seed=1))
-    print(f'generation run {run + 1}: global {a:.1f} us/step, local hop={hop} {b:.1f} us/step', flush=True)
+    if run == 0:
+      unaligned()                                      # (warms the admission's scratch and tables)
+    c = unaligned()
+    print(f'generation run {run + 1}: global {a:.1f} us/step, local hop={hop} {b:.1f} us/step, '
+          f'local hop={hop} unaligned rows {c:.1f} us/step', flush=True)
   sys.exit(0)
 
 spk = torch.nn.functional.one_hot(torch.randint(0, CIN, (B,), generator=g), CIN).float().to(dev)

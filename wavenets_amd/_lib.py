@@ -51,6 +51,12 @@ class WnSamplingRow(C.Structure):
 WN_SAMPLING_ROWS_ON, WN_SAMPLING_ROWS_TOP_P = 1, 2
 
 
+class WnFrameRow(C.Structure):
+  """struct wn_frame_row (include/wn_hip.h): the frame schedule of one row of a queued generation batch; rows = None is off."""
+  _fields_ = [('rows', C.c_void_p), ('block_stride', C.c_int64), ('origin', C.c_int64), ('frames', C.c_int32),
+              ('hop', C.c_int32)]
+
+
 class WnAdamOptions(C.Structure):
   """struct wn_adam_options (include/wn_hip.h): what wn_adam_step_ext takes beyond the buffers and the step."""
   _fields_ = [('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
@@ -180,6 +186,9 @@ _SIGS = {
     'wn_plan_arm_row_weights': (C.c_int, [_P, _P, C.c_int64]),
     'wn_plan_set_cond_frames': (C.c_int, [_P, C.c_int32]),
     'wn_generate_set_condition': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    'wn_generate_frames_floats': (C.c_int64, [_P, C.c_int64]),
+    'wn_generate_frames_build': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
+    'wn_plan_arm_gen_frames': (C.c_int, [_P, C.POINTER(WnFrameRow), C.c_int32]),
     'wn_weighted_squared_error': (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, _P, _P, _P]),
     'wn_sample_waveform': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_uint64, C.c_uint64, _P, _P]),

@@ -450,6 +450,14 @@ int condition_only(wn_plan* p, const float* params, const float* cond, int B, in
   return c.condition();
 }
 
+int condition_rows(wn_plan* p, const float* params, const float* cond, int rows, const float* fragbase, float* buf,
+                   const WsLayout& L, hipStream_t s) {
+  // (B = rows utterances of one time step, one frame each: Bc = rows; condition() only reads the images)
+  FwdCall c(p, params, nullptr, false, cond, rows, 1, false, buf, L, s, nullptr, nullptr);
+  c.fragbase = const_cast<float*>(fragbase);
+  return c.condition();
+}
+
 int cond_frames_check(const char* who, const wn_plan* p, int T) {
   const int F = ex(p).cond_frames;
   if (F <= 1 || p->c.cond_inputs <= 0) return 1;

@@ -149,6 +149,79 @@ int ensure_gen_table(const wn_plan* p, wn_exec& e, const GenLayout& G, const WsL
   return WN_OK;
 }
 
+// ---- frame schedules ----
+// the frame table of `rows` condition rows as offsets into the caller's buffer: the bias rows first (what the records point
+// into), the conditioning phase's scratch at that row count behind them
+WsLayout frame_table_layout(const wn_plan* p, int64_t rows) {
+  WsLayout L{};
+  Carver cv;
+  L.frames = 1;
+  L.cb = cv.take((int64_t)p->N * rows * 2 * p->D);
+  for (const ConvInfo& c : p->mapping) L.M.push_back(cv.take(rows * c.cout));
+  L.cbt = cv.take(rows * p->N * 2 * p->D);
+  L.total = cv.pos;
+  return L;
+}
+
+// the armed schedules against a call of B rows over the steps [first, first + length): WN_E_INVALID with the numbers
+int frames_call_check(const GenFrames& fr, int B, int64_t first, int length, bool queued) {
+  if (!queued) {
+    wn_set_error("generate: frame schedules are armed (wn_plan_arm_gen_frames); the sliding window takes none (queued = 0)");
+    return WN_E_INVALID;
+  }
+  if ((int64_t)fr.host.size() != B) {
+    wn_set_error("generate: frame schedules are armed for B = %d rows, the call has B = %d", (int)fr.host.size(), B);
+    return WN_E_INVALID;
+  }
+  if (length < 1) return WN_OK;
+  const int64_t last = first + length - 1;
+  for (int b = 0; b < B; ++b) {
+    const wn_frame_row& r = fr.host[b];
+    if (!r.rows || last < r.origin) continue;
+    const int64_t f = (last - r.origin) / r.hop;
+    if (f >= r.frames) {
+      wn_set_error("generate: row %d runs past its condition frames: sample %lld is in frame %lld, the row has frames = %d of hop = %d "
+                   "from origin %lld (its last sample is %lld)", b, (long long)last, (long long)f, (int)r.frames, (int)r.hop,
+                   (long long)r.origin, (long long)(r.origin + (int64_t)r.frames * r.hop - 1));
+      return WN_E_INVALID;
+    }
+  }
+  return WN_OK;
+}
+
+// the device copy of the armed records: uploaded when it holds other records than the armed ones.  A blocking copy, behind
+// everything the stream still has queued (an earlier call's copy kernels read the table)
+int ensure_frame_table(GenFrames& fr, hipStream_t s) {
+  const size_t n = fr.host.size();
+  if (fr.dev.d && fr.on_dev.size() == n && memcmp(fr.on_dev.data(), fr.host.data(), n * sizeof(wn_frame_row)) == 0) return WN_OK;
+  WN_HIP_CHECK(hipStreamSynchronize(s));
+  if (fr.dev.d && fr.on_dev.size() == n) {
+    fr.on_dev.clear();
+    WN_HIP_CHECK(hipMemcpy(fr.dev.d, fr.host.data(), n * sizeof(wn_frame_row), hipMemcpyHostToDevice));
+  } else {
+    fr.on_dev.clear();
+    const int rc = fr.dev.upload(fr.host);
+    if (rc) return rc;
+  }
+  fr.on_dev = fr.host;
+  return WN_OK;
+}
+
+// marks[t - first] != 0: the copy kernel runs for step t -- the call's first queued step step0, and every later step at
+// which some scheduled row begins a frame
+std::vector<uint8_t> frame_marks(const GenFrames& fr, int first, int step0, int end) {
+  std::vector<uint8_t> m((size_t)(end - first), 0);
+  m[(size_t)(step0 - first)] = 1;
+  for (const wn_frame_row& r : fr.host) {
+    if (!r.rows) continue;
+    int64_t t = (int64_t)step0 + 1;
+    if (t <= r.origin) t = r.origin;
+    else t += (r.hop - (t - r.origin) % r.hop) % r.hop;
+    for (; t < end; t += r.hop) m[(size_t)(t - first)] = 1;
+  }
+  return m;
+}
+
 // ------------------------------------------------------------------------------------------
 // One call of wn_generate_chunk: the caller's buffers, the generation layout of B, the priming layout, the rings and
 // the kernel paths of the call; its phases are the member functions, in launch order.  A call makes the samples
@@ -337,6 +410,11 @@ struct GenCall {
       ha.inv_lv = 1.0f / (float)(1 << (p->c.bits - 1));
     }
     if (ha.tail) { ha.seed = seed; ha.ctl = ctl; ha.samp = samp; }
+  }
+
+  // frame schedules: the scheduled rows' frames of step `step` into cb, in front of the launch that reads cb for that step
+  int frame_copy(int step) {
+    return wn_launch_gen_frame_copy(e.frames.dev.d, e.frames.vec, B, p->N, 2 * p->D, (int64_t)step, pws + L.cb, s);
   }
 
   // the input conv and every block of the step: x[tau] -> the rings' slots tau, the gated activations Zrow
@@ -528,7 +606,8 @@ enum GenEntry { GEN_ENTRY_ONE, GEN_ENTRY_CHUNK, GEN_ENTRY_BEGIN };
 static int generate_call(GenEntry entry, wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
                          int64_t first, int32_t length, int32_t deterministic, int32_t queued, const wn_sampling* sampling,
                          float* out, float* workspace, int64_t ws_floats, void* stream,
-                         const WnSampleRow* rows = nullptr, int32_t rows_flags = 0, const uint64_t* origin = nullptr) {
+                         const WnSampleRow* rows = nullptr, int32_t rows_flags = 0, const uint64_t* origin = nullptr,
+                         bool scheduled = true) {
   const bool chunk = entry != GEN_ENTRY_ONE, begins = entry == GEN_ENTRY_BEGIN;
   WnSampleCtl ctl = WN_SAMPLE_CTL_OFF;
   if (rows) {
@@ -560,9 +639,19 @@ static int generate_call(GenEntry entry, wn_plan* p, const float* params, const 
     wn_set_error("generate: %d condition frames are armed (wn_plan_set_cond_frames); generation takes one condition row per utterance", wnp::ex(p).cond_frames);
     return WN_E_INVALID;
   }
+  // the armed frame schedules (wn_plan_arm_gen_frames; scheduled = false: an admission's scratch pass takes cond)
+  GenFrames* fr = (scheduled && wnp::ex(p).frames.armed) ? &wnp::ex(p).frames : nullptr;
+  if (fr) {
+    const int rc = frames_call_check(*fr, B, first, length, queued != 0);
+    if (rc) return rc;
+  }
   GenLayout G = gen_layout(p, B, queued != 0);
   if (ws_floats < G.total) { wn_set_error("generate: workspace too small"); return WN_E_INVALID; }
   if (length == 0) return WN_OK;
+  if (fr) {                                  // (a blocking copy when the records changed: nothing of this call is queued yet)
+    const int rc = ensure_frame_table(*fr, (hipStream_t)stream);
+    if (rc) return rc;
+  }
   GenCall c{wnp::ex(p)};
   c.bind(p, params, cond, B, (int)first, length, window != nullptr, deterministic != 0, rows ? 0 : sampling->seed, ctl, out, workspace,
          (hipStream_t)stream, std::move(G));
@@ -586,9 +675,15 @@ static int generate_call(GenEntry entry, wn_plan* p, const float* params, const 
     if (rc) return rc;
   }
   c.build_args();
+  // frame schedules: the copy kernel in front of the launch that reads cb for a marked step -- the head launch of the step
+  // before where it carries the pre work (never for step0, which does its own), the chain / relay / block launch otherwise
+  const std::vector<uint8_t> marks = fr ? frame_marks(*fr, c.first, c.step0, c.end) : std::vector<uint8_t>();
+  const bool in_head = fr && c.gp.pre_in_head;
   for (int step = c.step0; step < c.end; ++step) {
+    if (fr && marks[step - c.first] && (!in_head || step == c.step0) && (rc = c.frame_copy(step)) != WN_OK) return rc;
     if ((rc = c.blocks(step)) != WN_OK) return rc;
     if ((rc = c.skip(step)) != WN_OK) return rc;
+    if (in_head && step + 1 < c.end && marks[step + 1 - c.first] && (rc = c.frame_copy(step + 1)) != WN_OK) return rc;
     if ((rc = c.head(step)) != WN_OK) return rc;
     if ((rc = c.sample(step)) != WN_OK) return rc;
   }
@@ -618,6 +713,88 @@ extern "C" int wn_generate_set_condition(wn_plan* p, const float* params, const 
   const int RF = wn_plan_receptive_field(p);
   const WsLayout L = make_layout(p, B, RF, false);
   return condition_only(p, params, cond, B, RF, workspace + G.prime, L, (hipStream_t)stream);
+}
+
+// ---- frame schedules: a request's table, and the records of the batch (include/wn_hip.h) ----
+extern "C" int64_t wn_generate_frames_floats(const wn_plan* p, int64_t rows) {
+  if (!p || p->c.cond_inputs <= 0 || rows < 1) return 0;
+  return frame_table_layout(p, rows).total;
+}
+
+// The conditioning phase of wn_generate_set_condition over k * F rows, into the caller's table.  The weight images are the
+// ones the priming pass left in the primed workspace (FwdCall::condition reads them and nothing else of it).
+extern "C" int wn_generate_frames_build(wn_plan* p, const float* params, const float* cond, int32_t k, int32_t F, float* table,
+                                        int64_t table_floats, const float* workspace, int64_t ws_floats, int32_t B, void* stream) {
+  if (!p || !params || !cond || !table || !workspace) {
+    wn_set_error("generate_frames_build: null %s", !p ? "plan" : !params ? "params" : !cond ? "cond" : !table ? "table" : "workspace");
+    return WN_E_INVALID;
+  }
+  if (k < 1 || F < 1) { wn_set_error("generate_frames_build: k and F must be >= 1 (got k = %d, F = %d)", (int)k, (int)F); return WN_E_INVALID; }
+  if (p->c.cond_inputs <= 0) { wn_set_error("generate_frames_build: the plan has no conditioning"); return WN_E_INVALID; }
+  const int64_t rows = (int64_t)k * F;
+  // (the products and the scatter index their rows with 32-bit arithmetic)
+  if (rows * p->N * 2 * p->D > 0x7fffffffLL) {
+    wn_set_error("generate_frames_build: k * F * blocks * 2D must not exceed 2147483647 (got k = %d, F = %d: %lld rows of %d blocks, 2D = %d)",
+                 (int)k, (int)F, (long long)rows, p->N, 2 * p->D);
+    return WN_E_INVALID;
+  }
+  if (wnp::ex(p).cond_frames > 1) {
+    wn_set_error("generate_frames_build: %d condition frames are armed (wn_plan_set_cond_frames); disarm them first", wnp::ex(p).cond_frames);
+    return WN_E_INVALID;
+  }
+  if ((uintptr_t)table % 16 != 0) { wn_set_error("generate_frames_build: table must be aligned to 16 bytes"); return WN_E_INVALID; }
+  const WsLayout T = frame_table_layout(p, rows);
+  if (table_floats < T.total) {
+    wn_set_error("generate_frames_build: table too small (%lld floats, wn_generate_frames_floats(p, %lld) is %lld)", (long long)table_floats,
+                 (long long)rows, (long long)T.total);
+    return WN_E_INVALID;
+  }
+  if (B < 1) { wn_set_error("generate_frames_build: B must be >= 1 (got %d)", (int)B); return WN_E_INVALID; }
+  const GenLayout G = gen_layout(p, B, true);
+  if (ws_floats < G.total) {
+    wn_set_error("generate_frames_build: workspace too small (%lld < %lld floats)", (long long)ws_floats, (long long)G.total);
+    return WN_E_INVALID;
+  }
+  // (no look at the primed mark of the calling state: other sequences of the same state may have begun since, and the images
+  // of this workspace are as good as they were -- that it has been primed is the caller's word)
+  const WsLayout L = make_layout(p, B, wn_plan_receptive_field(p), false);
+  return condition_rows(p, params, cond, (int)rows, workspace + G.prime + L.frag, table, T, (hipStream_t)stream);
+}
+
+extern "C" int wn_plan_arm_gen_frames(wn_plan* p, const wn_frame_row* records, int32_t B) {
+  if (!p) { wn_set_error("arm_gen_frames: null plan"); return WN_E_INVALID; }
+  if (B < 0) { wn_set_error("arm_gen_frames: B must be >= 0 (got %d)", (int)B); return WN_E_INVALID; }
+  GenFrames& fr = wnp::ex(p).frames;
+  if (!records || B == 0) {            // disarm (the device copy stays: the next arming of the same records uploads nothing)
+    fr.armed = false; fr.host.clear();
+    return WN_OK;
+  }
+  if (p->c.cond_inputs <= 0) { wn_set_error("arm_gen_frames: %d frame schedules on a plan without conditioning", (int)B); return WN_E_INVALID; }
+  if (wnp::ex(p).cond_frames > 1) {
+    wn_set_error("arm_gen_frames: %d condition frames are armed (wn_plan_set_cond_frames); a generation step takes one row per utterance",
+                 wnp::ex(p).cond_frames);
+    return WN_E_INVALID;
+  }
+  const int64_t D2 = 2 * p->D;
+  bool vec = true;
+  for (int32_t b = 0; b < B; ++b) {
+    const wn_frame_row& r = records[b];
+    if (!r.rows) continue;
+    if (r.frames < 1 || r.hop < 1) {
+      wn_set_error("arm_gen_frames: row %d: frames and hop must be >= 1 (got frames = %d, hop = %d)", (int)b, (int)r.frames, (int)r.hop);
+      return WN_E_INVALID;
+    }
+    if (r.block_stride < (int64_t)r.frames * D2) {
+      wn_set_error("arm_gen_frames: row %d: block_stride = %lld is below frames * 2D = %d * %d", (int)b, (long long)r.block_stride, (int)r.frames, (int)D2);
+      return WN_E_INVALID;
+    }
+    if ((uintptr_t)r.rows % 4 != 0) { wn_set_error("arm_gen_frames: row %d: rows must be aligned to 4 bytes", (int)b); return WN_E_INVALID; }
+    vec = vec && (uintptr_t)r.rows % 16 == 0 && r.block_stride % 4 == 0;
+  }
+  fr.host.assign(records, records + B);
+  fr.vec = vec;
+  fr.armed = true;
+  return WN_OK;
 }
 
 extern "C" int wn_generate_sampled(wn_plan* p, const float* params, const float* window, const float* cond, int32_t B,
@@ -904,7 +1081,7 @@ extern "C" int wn_generate_admit_origin(wn_plan* p, const float* params, const f
   rc = ensure_admit_table(e, segs, k, B, slots);
   if (rc) return rc;
   rc = generate_call(GEN_ENTRY_BEGIN, p, params, windows, cond, k, position - 1, 1, deterministic, 1, nullptr, first_out, scratch,
-                     scratch_floats, stream, reinterpret_cast<const WnSampleRow*>(rows_k), rows_flags_k, origin_k);
+                     scratch_floats, stream, reinterpret_cast<const WnSampleRow*>(rows_k), rows_flags_k, origin_k, false);
   if (rc) return rc;
   e.primed_ws = workspace; e.primed_B = B;             // (the scratch's priming pass moved the mark: back to the session)
   int64_t widest = 1;

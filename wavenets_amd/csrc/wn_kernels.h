@@ -392,6 +392,10 @@ int wn_launch_cond_wgrad(const float* m, const float* dcb, int B, int Cc, int N,
 // utterance b, all N blocks in one launch, fixed summation order; block n's g_u [B*T][D2] at gu + n * gu_stride
 int wn_launch_cond_frame_sum(const float* gu, int64_t gu_stride, int B, int T, int F, int N, int D2, float* dcb,
                              hipStream_t s);
+// frame schedules of queued generation (wn_gen_frames.hip): cb[n][b][0 .. D2) = the row of frame (t - origin_b) / hop_b, clamped
+// to the record's frames, out of record b's own table, for every block n and every record with rows != null; all N blocks in
+// one launch.  recs: B records on the device; recs_vec: every record's rows are 16-byte aligned at a stride of whole float4
+int wn_launch_gen_frame_copy(const wn_frame_row* recs, bool recs_vec, int B, int N, int D2, int64_t t, float* cb, hipStream_t s);
 // skip path folded into the head's first convolution (wn_elem.hip): V(b) = W_s(b) W_f0, b' = b_f0 + W_f0^T sum b_s;
 // and the weight gradients of conv_skip (all blocks) and of that convolution from M = Z^T dL/da
 int wn_launch_skip_fold(const float* params, int64_t ws_off0, int64_t ws_stride, int64_t wf0_off, int64_t bf0_off,

@@ -150,6 +150,7 @@ void exec_release(wn_exec* e) {
   if (e->side) (void)hipStreamDestroy(e->side);
   e->gen.release();
   e->admit.release();
+  e->frames.release();
   if (g_bound_exec == e) g_bound_exec = nullptr;
   delete e;
 }

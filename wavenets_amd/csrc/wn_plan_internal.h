@@ -260,6 +260,18 @@ struct AdmitTable {
   void release() { valid = false; segs.release(); slots_d.release(); }
 };
 
+// The frame schedules armed by wn_plan_arm_gen_frames: the caller's records as armed (host), and the
+// device copy the copy kernel reads.  Arming touches no device (a plan can be armed without one): the queued call that finds
+// `dev` holding other records than `host` uploads them before it queues anything (ensure_frame_table, wn_generate.hip).
+struct GenFrames {
+  bool armed = false;
+  bool vec = false;                    // every scheduled record: rows 16-byte aligned, block_stride % 4 == 0
+  std::vector<wn_frame_row> host;      // B records
+  std::vector<wn_frame_row> on_dev;    // what `dev` holds
+  DevTable<wn_frame_row> dev;
+  void release() { armed = false; host.clear(); on_dev.clear(); dev.release(); }
+};
+
 }  // namespace wnp
 
 // The mutable side of a plan: per-caller state of the orchestration ("a wn_plan is immutable and shareable
@@ -286,6 +298,7 @@ struct wn_exec {
   wnp::WgSchedule wg;           // the cached weight-gradient schedule of the last (B, T) layout it trained
   wnp::GenTable gen;            // the cached block table of the generation chains, for the last batch size it generated
   wnp::AdmitTable admit;        // the cached segment and slot tables of the last admission (wn_generate_admit)
+  wnp::GenFrames frames;        // the frame schedules armed by wn_plan_arm_gen_frames and their device copy
   // side stream: the side spans of the weight-gradient schedule run beside the per-block / skip kernels
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -654,6 +667,10 @@ int forward_core(wn_plan* p, const float* params, const float* x, bool prep, con
 // the conditioning phase of a forward pass alone: mapping stack and the blocks' bias table cb into the workspace of layout L
 // (wn_generate_set_condition: a new condition into the table a queued generation step reads)
 int condition_only(wn_plan* p, const float* params, const float* cond, int B, int T, float* ws, const WsLayout& L, hipStream_t s);
+// ... over `rows` condition rows into a buffer of the caller's (wn_generate_frames_build): M, cb and cbt of L are offsets into
+// `buf` (L.frames = 1), the weight images are read at `fragbase`, which belongs to a primed workspace and is not written
+int condition_rows(wn_plan* p, const float* params, const float* cond, int rows, const float* fragbase, float* buf,
+                   const WsLayout& L, hipStream_t s);
 // what a pass hands back from the logits in the workspace: a copy of them, and the model output (their softmax for a
 // categorical head, the logits themselves for a mixture head); either may be null
 int emit_outputs(const wn_plan* p, const float* ws, const WsLayout& L, int64_t rows, float* logits_out, float* out, hipStream_t s);

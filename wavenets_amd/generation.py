@@ -72,6 +72,40 @@ class _RowControls:
     return torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.float32).to(device)
 
 
+class _FrameSchedule:
+  """The frame schedule of one request: its condition frames (k, F, Cin), kept for the rebuild of
+  an exact-fp32 turn, and the table of its bias rows for every frame (wn_generate_frames_build), made once.  Row j of the
+  request uses frame (t - origin) // hop at the step that emits sample t."""
+
+  def __init__(self, cond, origin, hop):
+    self.cond, self.origin, self.hop = cond.contiguous(), int(origin), int(hop)
+    self.k, self.frames = int(cond.shape[0]), int(cond.shape[1])
+    self.table = None
+
+  def build(self, session, exact):
+    """The table, in exact-fp32 mode or the calling context's, from the weight images of the session's primed workspace
+    (read only).  In place once it exists: the records keep pointing at it."""
+    m, L = session._model, _lib.lib()
+    if self.table is None:
+      self.table = torch.empty(int(L.wn_generate_frames_floats(m._plan, self.k * self.frames)), dtype=torch.float32,
+                               device=m._device)
+
+    def run():
+      _lib.check(L.wn_generate_frames_build(m._plan, _lib.ptr(m.flat_params), _lib.ptr(self.cond), self.k, self.frames,
+                                            _lib.ptr(self.table), self.table.numel(), _lib.ptr(session._ws), session._ws.numel(),
+                                            session._B, _lib.stream_ptr()))
+    if exact:
+      with m.exact_fp32():
+        run()
+    else:
+      run()
+
+  def record(self, j, width):
+    """struct wn_frame_row of the request's row j (width = 2 * dilation channels floats per bias row)."""
+    return _lib.WnFrameRow(self.table.data_ptr() + 4 * j * self.frames * width, self.k * self.frames * width, self.origin,
+                           self.frames, self.hop)
+
+
 def _as_rows(name, v):
   """None for a scalar argument, else the entries of a list, tuple, numpy array or 1-D tensor as Python values."""
   if isinstance(v, torch.Tensor):
@@ -105,11 +139,16 @@ class GenerationSession:
                frames=None, hop=None):
     L = _lib.lib()
     self._model, self._sampling, self._cond, self._window = model, sampling, condition, window
-    # local conditioning: frames (B, F, Cin) and the samples per frame.  The step that emits sample g,
-    # counted from `start`, uses frame g // hop; the priming pass uses frame 0 (`condition`).  A row an admission replaced
-    # has left the schedule and keeps the condition set_condition gives it.
-    self._frames, self._hop, self._frame = frames, hop, 0
-    self._off_schedule = set()
+    # local conditioning (DESIGN.md sections 36 and 42): frames (B, F, Cin) and the samples per frame.  The step that emits
+    # sample g, counted from `start`, uses frame g // hop; the priming pass uses frame 0 (`condition`).  Every row has a
+    # schedule of its own: _sched[b] is (schedule, its row of that schedule) or None -- a row admitted with a held condition,
+    # or taken off by set_condition(slots=), keeps the condition set_condition gives it.  The schedules are armed around every
+    # chunk (wn_plan_arm_gen_frames) and advanced by the copy kernel inside it.
+    self._hop = hop
+    self._own = None if frames is None else _FrameSchedule(frames, start, hop)     # of the rows the session begins with
+    self._sched = [None if self._own is None else (self._own, b) for b in range(int(batch_size))]
+    # set_condition on a scheduled row: the row keeps that condition until the position held here, its next frame boundary
+    self._held = {}
     # per-row controls: the device table of the session, read by every chunk (and by the exact-fp32 rerun of one)
     self._rows = sampling.device_table(model._device) if isinstance(sampling, _RowControls) else None
     self._B, self._queued, self._det = int(batch_size), int(bool(use_queues)), int(bool(deterministic))
@@ -150,31 +189,40 @@ class GenerationSession:
     would run past the last frame raises ValueError before anything is made."""
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
       raise ValueError(f'n must be an int >= 1 (got {n!r})')
-    if self._frames is None:
-      return self._generate_chunk(int(n))
-    n, hop, F = int(n), self._hop, self._frames.shape[1]
-    done = self.position - self._start
-    if done + n > F * hop:
-      raise ValueError(f'generation session: {done} + {n} samples run past the {F} condition frames of hop {hop} '
-                       f'({F * hop} samples)')
+    n = int(n)
+    for b, entry in enumerate(self._sched):
+      if entry is None:
+        continue
+      sch, done = entry[0], self.position - entry[0].origin
+      if done + n > sch.frames * sch.hop:
+        raise ValueError(f'generation session: row {b}: {done} + {n} samples run past the {sch.frames} condition frames '
+                         f'of hop {sch.hop} ({sch.frames * sch.hop} samples)')
+    # (one chunk whatever frame boundaries it crosses: the copy kernel advances the rows inside it.  Only a row that
+    # set_condition holds until its next boundary ends a chunk there: it goes back on its schedule between two calls)
     pieces = []
     while n > 0:
-      g = self.position - self._start
-      f = g // hop
-      if f != self._frame:
-        self._to_frame(f)
-      take = min(n, (f + 1) * hop - g)
+      self._held = {b: end for b, end in self._held.items() if end > self.position}
+      take = min([n] + [end - self.position for end in self._held.values()])
       pieces.append(self._generate_chunk(take))
       n -= take
     return pieces[0] if len(pieces) == 1 else torch.cat(pieces, 1)
 
-  def _to_frame(self, f):
-    cond = self._frames[:, f, :].clone()
-    if self._off_schedule:
-      keep = torch.tensor(sorted(self._off_schedule), device=cond.device)
-      cond[keep] = self._cond[keep]
-    self._write_condition(cond)
-    self._frame = f
+  def _build_tables(self, exact):
+    """Every schedule's table (again): in the math mode the session runs in from here on."""
+    for sch in {id(e[0]): e[0] for e in self._sched if e is not None}.values():
+      sch.build(self, exact)
+
+  def _frame_records(self):
+    """The B struct wn_frame_row of the next chunk, or None when no row is on a schedule with a table (nothing is armed
+    then, and the chunk queues what it queues without schedules)."""
+    width = 2 * self._model.spec.D
+    recs = (_lib.WnFrameRow * self._B)()
+    some = False
+    for b, entry in enumerate(self._sched):
+      if entry is not None and entry[0].table is not None and self._held.get(b, 0) <= self.position:
+        recs[b] = entry[0].record(entry[1], width)
+        some = True
+    return recs if some else None
 
   def _write_condition(self, cond):
     """self._cond = cond, and into the bias table of the workspace when the sequence has begun (the priming pass of a
@@ -218,9 +266,39 @@ class GenerationSession:
       if tuple(condition.shape) != (len(slot_list), cond.shape[1]):
         raise ValueError(f'condition must have shape {(len(slot_list), cond.shape[1])} (got {tuple(condition.shape)})')
       cond[torch.tensor(slot_list, device=m._device)] = condition
+    # (the table of the workspace again for all B rows: the rows on a schedule take their frames back at the first step of
+    # the next chunk, which always runs the copy kernel)
     self._write_condition(cond)
+    for b in (range(self._B) if slots is None else slot_list):
+      if self._sched[b] is None:
+        continue
+      sch = self._sched[b][0]
+      if sch is not self._own:
+        self._sched[b] = None                 # a request admitted on a schedule: this call ends it
+      else:
+        # a row the session began with: the condition stands until the row's next frame boundary, as it did when a
+        # boundary was a rewrite of the table between two chunks
+        g = self.position - sch.origin
+        self._held[b] = sch.origin + (((g - 1) // sch.hop + 1) if g > 0 else 1) * sch.hop
 
   def _generate_chunk(self, n):
+    if self.position != self._start or self._own is None or not self._queued:
+      return self._chunk(n)
+    # The chunk that begins a sequence on a frame schedule: the tables are built from the weight images its priming pass
+    # leaves, in the math mode that pass ended in, so the priming step is a call of its own and the steps behind it the
+    # next one (the chunks of a sequence, concatenated, are the one call bit for bit: DESIGN.md section 23).
+    # Nothing is committed until both have returned: if the table build or the second call raises, position is back at
+    # the start, where the next chunk begins the sequence again from the window (a chunk that raises leaves position where
+    # it was).
+    try:
+      head = self._chunk(1)
+      self._build_tables(self.exact)
+      return head if n == 1 else torch.cat([head, self._chunk(n - 1)], 1)
+    except BaseException:
+      self.position = self._start
+      raise
+
+  def _chunk(self, n):
     m, L, first = self._model, _lib.lib(), self.position
     self._check_usable()
     out = torch.empty(self._B, n, 1, dtype=torch.float32, device=m._device)
@@ -233,7 +311,15 @@ class GenerationSession:
           'begin' if begins and first > 0 else 'chunk',
           (m._plan, _lib.ptr(m.flat_params), window, _lib.ptr(self._cond), self._B, first, n, self._det, self._queued),
           self._sampling, self._rows, self._origin, (_lib.ptr(out), _lib.ptr(self._ws), self._ws.numel(), _lib.stream_ptr()))
-      _lib.check(entry(*args))
+      # the rows' frame schedules, armed for this call alone (the rerun arms the tables the exact-fp32 turn rebuilt)
+      records = None if begins else self._frame_records()
+      try:
+        if records is not None:
+          _lib.check(L.wn_plan_arm_gen_frames(m._plan, records, self._B))
+        _lib.check(entry(*args))
+      finally:
+        if records is not None:
+          L.wn_plan_arm_gen_frames(m._plan, None, 0)
 
     def tripped():
       return _guard_words(self._ws[self._slot:self._slot + 2], 'chunk', lambda: setattr(self, '_failed', True))
@@ -244,6 +330,9 @@ class GenerationSession:
       # samples already handed out stand
       if not begins:
         self._state.copy_(self._shadow)
+        # the tables were built in split precision: again from the kept frames, in the mode the session is turning to
+        # (the compact table needs no place in the shadow: the rerun's first step runs the copy kernel)
+        self._build_tables(True)
     if self.exact or L.wn_debug_value(1) == 1:
       # exact fp32 cannot trip: no shadow copy, no host read
       with m.exact_fp32():
@@ -312,10 +401,21 @@ class GenerationSession:
     sample = sample[:, -rf:, :].contiguous()
     if m.conditioning is not None and condition is None:
       raise ValueError('Conditioning must be provided.')
+    req_frames = None                        # (k, F, Cin), F > 1: the requests bring a frame schedule of their own
     if condition is not None:
       condition = torch.as_tensor(condition, dtype=torch.float32, device=m._device).contiguous()
-      if m.conditioning == 'local' and condition.dim() == 3 and condition.shape[1] == 1:
-        condition = condition[:, 0, :].contiguous()          # a held condition as one frame, (k, 1, Cin)
+      if m.conditioning == 'local' and self._cond is not None:
+        cin = int(self._cond.shape[1])
+        if condition.dim() == 2 and cin == 1 and condition.shape[1] > 1:
+          condition = condition[:, :, None].contiguous()     # (k, F) frames of one input
+        if condition.dim() == 3 and condition.shape[1] == 1:
+          condition = condition[:, 0, :].contiguous()        # a held condition as one frame, (k, 1, Cin)
+        elif condition.dim() == 3 and condition.shape[1] > 1 and tuple(condition.shape[::2]) == (k, cin):
+          if self._hop is None:
+            raise ValueError(f'condition holds {int(condition.shape[1])} frames per request: the session needs hop= '
+                             '(generation_session(..., hop=h): the samples generated per frame)')
+          req_frames = condition
+          condition = req_frames[:, 0, :].contiguous()       # the priming pass takes frame 0, as in generate
       if self._cond is None or tuple(condition.shape) != (k,) + tuple(self._cond.shape[1:]):
         want = None if self._cond is None else (k,) + tuple(self._cond.shape[1:])
         raise ValueError(f'condition must have shape {want} (got {tuple(condition.shape)})')
@@ -359,8 +459,9 @@ class GenerationSession:
         run()
     elif _guard.guarded(m, run, tripped, counter='generation_guard_trips'):
       # the admission's priming pass left the range of the split-precision kernels: it ran again on the exact-fp32 kernels
-      # (the move overwrites the same rows: nothing to restore), and the session stays there
+      # (the move overwrites the same rows: nothing to restore), and the session stays there, with its tables built again
       self.exact = True
+      self._build_tables(True)
     # the session's own records: rows slots[j] of the device table (in place: the chunks read this tensor) and of the condition
     self._sampling = table
     self._rows.copy_(table.device_table(m._device))
@@ -373,7 +474,15 @@ class GenerationSession:
       if not self._admitted:
         self._cond = self._cond.clone()          # (the caller's tensor stays as it is)
       self._cond[torch.tensor(slot_list, device=m._device)] = condition
-      self._off_schedule.update(slot_list)         # (a frame schedule per admitted request is a follow-up: section 36)
+      # the rows leave whatever schedule they were on: a held condition is driven by set_condition alone, frames go on a
+      # schedule of the request's own that counts from its first sample, index position - 1, whichever clock its draws follow
+      sch = None
+      if req_frames is not None:
+        sch = _FrameSchedule(req_frames, self.position - 1, self._hop)
+        sch.build(self, self.exact)
+      for j, b in enumerate(slot_list):
+        self._sched[b] = None if sch is None else (sch, j)
+        self._held.pop(b, None)
     self._admitted = True
     return first_out
 
@@ -385,6 +494,7 @@ class GenerationSession:
                          'start a new session')
     self.position = self._start
     self._failed = False
+    self._held = {}
 
 
 class _Generation:
